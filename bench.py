@@ -14,7 +14,12 @@ Modes:
   --config c5: the 100 GiB streaming run (100 x a 1 GiB block, pre-filter on): each GPU processes
     its 1/8 share (12.5 GiB) as device-resident stream windows (stream.rs window_matches).
 
-    python bench.py [--gpus N --steps K --warmup W --config c3 --mib 256 --shard]
+    python bench.py [--gpus N --steps K --warmup W --config c3 --mib 256 --shard --full --dump-outputs DIR]
+
+A plain run does what the headline needs and no more: set-up, the warm-up steps, the K timed steps,
+the result line. `--full` adds every other leg to the line (the CPU baselines, the fresh-word, C2 / C5
+and strong-scaling diagnostics; `--no-cpu-baseline` / `--no-fresh-diag` drop some of them again).
+`--dump-outputs DIR` writes the Match records the last timed step delivered (dump_outputs below).
 
 `--gpus N` with N > 1 outside torchrun re-launches this script under torch.distributed.run with N
 ranks (before any GPU call); under torchrun, --gpus must equal WORLD_SIZE.
@@ -73,6 +78,12 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=16, help="all-cores CPU baseline threads (box share: 16)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--traffic-json", default=None, help="default: profiles/traffic_<config>.json")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the CPU baselines (cpu_baseline) and the extra "
+                         "diagnostics legs (fresh_words, strong_emulated / strong, the default run's c2 / c5 legs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the Match records of the last timed step to DIR/matches.npy "
+                         "(float64, sorted by start, end, pattern; see dump_outputs) and DIR/match_count.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/gather plumbing only (gloo, no GPU, no search): for CPU tests of --gpus N")
     return ap.parse_args()
@@ -170,12 +181,15 @@ def main():
     windows = staged.owned_windows  # graphemes this rank searches per step
     host_buf = [None]  # rank 0: pinned landing buffer of the gathered records
     stage_ms = [0.0]
+    last = [None]  # the records the latest step delivered (rank 0): --dump-outputs
 
     def step():
+        last[0] = None  # the previous step's result buffer goes back to the library before this search
         if args.end_to_end:  # search_raw from host bytes: staging (H2D, UTF-8 check, segmentation + fold) + search
             hs = StagedHaystack(engine, wl.haystack)
             rows, st = hs.search_windows_records(wl.threshold, stream=stream)
             del hs
+            last[0] = rows
             return len(rows), st
         hs = staged
         if device_staging:  # synchronous: its kernels are done on return
@@ -188,6 +202,7 @@ def main():
         if world == 1:  # records D2H into the library's pooled pinned buffers
             rows, st = (hs.search_prefiltered_records(wl.threshold, stream=stream) if wl.prefilter
                         else hs.search_windows_records(wl.threshold, stream=stream))
+            last[0] = rows
             return len(rows), st
         recs, n, st = hs.search_device(wl.threshold, stream=stream)
         got = gather_device(recs, n, 0)  # RCCL: counts all-gather + point-to-point sends to rank 0
@@ -195,6 +210,7 @@ def main():
             if host_buf[0] is None or host_buf[0].numel() < got.numel():
                 host_buf[0] = torch.empty(int(got.numel() * 1.25) + 4096, dtype=torch.uint8, pin_memory=True)
             host_buf[0][: got.numel()].copy_(got)
+            last[0] = host_buf[0][: got.numel()]
             return got.numel() // 32, st
         return n, st
 
@@ -243,22 +259,26 @@ def main():
     bytes_step = rank_bytes + 32 * recs_rank
     achieved = bytes_step / (step_dev_ms / 1e3) / 1e9 if step_dev_ms > 0 else 0.0
     traffic, traffic_note = load_traffic(args, mib)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
+    last[0] = None
 
     fresh = strong = legs = None
-    if (world == 1 and args.config in ("c2", "c3") and args.vocab and device_staging and not args.no_fresh_diag):
+    diag = args.full and not args.no_fresh_diag  # the legs beside the headline run only with --full
+    if (world == 1 and args.config in ("c2", "c3") and args.vocab and device_staging and diag):
         fresh = fresh_words_diag(args, engine, nbytes, local, stream)
-    if args.config in ("c2", "c3", "c4") and device_staging and not args.shard and not args.no_fresh_diag:
+    if args.config in ("c2", "c3", "c4") and device_staging and not args.shard and diag:
         base_hay = wl.haystack if world == 1 else base_haystack(args, nbytes, vocab)
         if world == 1:  # every shard of N in {2, 4, 8} on this GPU, one after another
             strong = strong_emulated(engine, base_hay, wl.threshold, local, stream, elapsed / args.steps * 1e3)
         else:  # the --shard step on the same ranks, beside the weak one
             strong = strong_measured(engine, base_hay, wl.threshold, world, rank, local, stream, args.steps)
         del base_hay
-    if world == 1 and args.config == "c3" and device_staging and not args.no_fresh_diag and args.mib is None:
+    if world == 1 and args.config == "c3" and device_staging and diag and args.mib is None:
         legs = default_legs(args, local)  # C2 (1 GiB) and C5 (one GPU's 12.5 GiB share) in the driver's run
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         min_mib = args.cpu_min_mib if args.cpu_min_mib is not None else 2.0  # at least 2 MiB single-thread
         cpu = cpu_baseline(wl, args.cpu_seconds, args.cpu_threads, int(min_mib * (1 << 20)))
 
@@ -330,6 +350,43 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much is written
+DUMP_FIELDS = ("start", "end", "pattern_index", "similarity", "insertions", "deletions", "substitutions", "swaps",
+               "edits")
+
+
+def dump_outputs(path, recs):
+    """--dump-outputs: what the timed path delivered in its last step, the 32-byte Match records a
+    caller of search_raw receives (NumPy MATCH_DTYPE records, or the gathered record bytes as a uint8
+    tensor / array), written as
+      path/matches.npy      float64 [k, 9], columns DUMP_FIELDS (every field is exact in a float64),
+      path/match_count.npy  float64 [1], the number of records of the step.
+    search_raw's order is unspecified (search.rs:1105-1110) and the device appends records as waves
+    finish, so the rows are sorted by (start, end, pattern_index), unique per record, to make two runs
+    comparable row for row. k = the record count unless that exceeds DUMP_MAX_BYTES: then a fixed
+    (seed 0) sample of the sorted rows, in order."""
+    import numpy as np
+    from fuzzy_aho_corasick._native import MATCH_DTYPE
+    if recs is None:
+        recs = np.zeros(0, dtype=MATCH_DTYPE)
+    if hasattr(recs, "numpy"):  # a torch uint8 tensor of gathered records
+        recs = recs.cpu().numpy()
+    recs = np.ascontiguousarray(recs)
+    if recs.dtype != MATCH_DTYPE:
+        recs = recs.view(np.uint8).reshape(-1).view(MATCH_DTYPE)
+    recs = recs[np.lexsort((recs["pattern_index"], recs["end"], recs["start"]))]
+    n = len(recs)
+    cap = (DUMP_MAX_BYTES - 4096) // (8 * len(DUMP_FIELDS))
+    if n > cap:
+        recs = recs[np.sort(np.random.default_rng(0).choice(n, size=cap, replace=False))]
+    out = np.empty((len(recs), len(DUMP_FIELDS)), dtype=np.float64)
+    for i, f in enumerate(DUMP_FIELDS):
+        out[:, i] = recs[f]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "matches.npy"), out)
+    np.save(os.path.join(path, "match_count.npy"), np.array([n], dtype=np.float64))
 
 
 def timed_step_desc(args) -> str:
@@ -559,6 +616,7 @@ def default_legs(args, local):
     torch.cuda.empty_cache()
     c5 = c5_measure(args, 1, 0, local, steps=2, warmup=1, gib=100.0)
     c5.pop("_wl")
+    c5.pop("_last")
     out["c5"] = {k: c5[k] for k in ("value", "unit", "ms_per_step", "steps", "bytes_per_gpu", "stream_windows_per_gpu",
                                     "window_bytes", "batches_per_step", "matches_per_step", "prefilter_ms_per_step",
                                     "research_kernel_ms_per_step", "roofline_frac_kernels", "roofline_frac_step",
@@ -621,6 +679,7 @@ def c5_measure(args, world, rank, local, steps, warmup, gib):
     setup_s = time.perf_counter() - t_setup
 
     dev_recs = [torch.empty(1 << 20, dtype=torch.uint8, device=torch.device("cuda", local))]
+    last = [None]  # the records the latest step delivered (rank 0): --dump-outputs
 
     def step():
         # every window's owned records (stream.rs:262-297) appended in HBM in stream order, then at
@@ -633,8 +692,10 @@ def c5_measure(args, world, rank, local, steps, warmup, gib):
             k_ms += st.kernel_ms
         if world > 1:
             gathered = gather_device(dev_recs[0], n, 0)
+            last[0] = gathered
             return (gathered.numel() // 32 if gathered is not None else 0), pf_ms, k_ms
         recs = dev_recs[0][: n * 32].cpu().numpy().view(MATCH_DTYPE)
+        last[0] = recs
         return len(recs), pf_ms, k_ms
 
     for _ in range(warmup):
@@ -673,7 +734,7 @@ def c5_measure(args, world, rank, local, steps, warmup, gib):
            "roofline_frac_kernels": (bytes_step / (dev_ms / 1e3) / 1e9 / HBM_PEAK_GBS) if dev_ms > 0 else None,
            "roofline_frac_step": bytes_step / (elapsed / steps) / 1e9 / HBM_PEAK_GBS,
            "setup_s": setup_s, "workload": "c5: " + WORKLOAD["c5"], "patterns": len(wl.patterns),
-           "threshold": wl.threshold, "_wl": wl}
+           "threshold": wl.threshold, "_wl": wl, "_last": last[0]}
     del staged, engine
     return out
 
@@ -682,9 +743,13 @@ def run_c5(args, world, rank, local):
     """C5 line (--config c5): c5_measure at the requested stream size, CPU baseline on rank 0 at N = 1."""
     r = c5_measure(args, world, rank, local, args.steps, args.warmup, args.gib)
     wl = r.pop("_wl")
+    recs = r.pop("_last")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, recs)
+    del recs
     traffic, traffic_note = load_traffic(args, args.gib * 1024)  # c5 traffic is keyed by the stream size
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         min_mib = args.cpu_min_mib if args.cpu_min_mib is not None else 2.0  # at least 2 MiB single-thread
         cpu = cpu_baseline(wl, args.cpu_seconds, args.cpu_threads, int(min_mib * (1 << 20)))
     if rank == 0:
@@ -731,7 +796,7 @@ class _RepeatReader:
         return bytes(self.block[o:o + take])
 
 
-def stream_measure(local, gib, steps, warmup=1):
+def stream_measure(local, gib, steps, warmup=1, keep=False):
     """The product's streaming API itself (FuzzyAhoCorasick::search_stream, stream.rs:319-335, over
     fac_stream_*): an in-memory reader of `gib` GiB (repeats of C5's 1 GiB block, SURVEY §8(d)
     generator) read in READ_CHUNK pieces, windows of the crate's 256 KiB cut as its WindowReader
@@ -745,19 +810,24 @@ def stream_measure(local, gib, steps, warmup=1):
     total = int(gib * (1 << 30))
     setup_s = time.perf_counter() - t0
     hits = [0]
+    rows = []  # keep (--dump-outputs): the matches the callback received in the latest step
 
     def on_match(m):
         hits[0] += 1
+        if keep:
+            rows.append((m.start, m.end, m.pattern_index, m.similarity, m.insertions, m.deletions, m.substitutions,
+                         m.swaps, m.edits))
 
     for _ in range(warmup):
         engine.search_stream(_RepeatReader(wl.haystack, min(total, 1 << 30)), wl.threshold, on_match)
     hits[0] = 0
     t = time.perf_counter()
     for _ in range(steps):
+        rows.clear()
         n = engine.search_stream(_RepeatReader(wl.haystack, total), wl.threshold, on_match)
         assert n == total
     dt = (time.perf_counter() - t) / steps
-    return {"value": total / dt / 1e9, "unit": "Gchars/s", "ms_per_step": dt * 1e3, "steps": steps,
+    return {"value": total / dt / 1e9, "unit": "Gchars/s", "ms_per_step": dt * 1e3, "steps": steps, "_last": rows,
             "stream_bytes": total, "matches_per_step": hits[0] / steps, "setup_s": setup_s,
             "workload": "search_stream (fac_stream_*) over an in-memory reader of C5 data, 256 KiB windows, "
                         "no pre-filter (as the crate's search_stream), edits=1, 1K patterns (10-16), threshold 0.85",
@@ -767,7 +837,12 @@ def stream_measure(local, gib, steps, warmup=1):
 def run_stream(args, world, rank, local):
     """--config stream: stream_measure on this rank (N > 1: every rank its own stream, weak)."""
     import torch.distributed as dist
-    r = stream_measure(local, args.gib if args.gib != 100.0 else 8.0, args.steps, args.warmup)
+    r = stream_measure(local, args.gib if args.gib != 100.0 else 8.0, args.steps, args.warmup,
+                       keep=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        from fuzzy_aho_corasick._native import MATCH_DTYPE
+        dump_outputs(args.dump_outputs, np.array([row + (b"",) for row in r["_last"]], dtype=MATCH_DTYPE))
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": r["value"] * world, "unit": "Gchars/s", "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],

@@ -23,7 +23,7 @@ if has smoke; then
   cat "$OUT/smoke.log"
 fi
 if has c3; then
-  timeout -k 10 400 python bench.py > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
+  timeout -k 10 400 python bench.py --full > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
   cat "$OUT/bench_c3.json"
 fi
 if has c3e2e; then
@@ -31,15 +31,15 @@ if has c3e2e; then
   cat "$OUT/bench_c3_e2e.json"
 fi
 if has c2; then
-  timeout -k 10 300 python bench.py --config c2 --no-cpu-baseline > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+  timeout -k 10 300 python bench.py --full --config c2 --no-cpu-baseline > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
   cat "$OUT/bench_c2.json"
 fi
 if has c4; then
-  timeout -k 10 300 python bench.py --config c4 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+  timeout -k 10 300 python bench.py --full --config c4 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
   cat "$OUT/bench_c4.json"
 fi
 if has c5; then  # one GPU's full 12.5 GiB share of the 100 GiB stream, CPU baseline included
-  timeout -k 10 600 python bench.py --config c5 --steps 2 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
+  timeout -k 10 600 python bench.py --full --config c5 --steps 2 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
   cat "$OUT/bench_c5.json"
 fi
 export TMPDIR=/tmp
@@ -84,16 +84,16 @@ for cfg in c2 c4; do  # pmc2 / pmc4: PMC traffic of the C2 (1 GiB) / C4 (128 MiB
     head -c 600 "$OUT/traffic_$cfg.log"
   fi
   if has ${cfg}t; then  # with the CPU baseline and the traffic just measured
-    timeout -k 10 400 python bench.py --config $cfg > "$OUT/bench_${cfg}_traffic.json" 2> "$OUT/bench_${cfg}_traffic.err"
+    timeout -k 10 400 python bench.py --full --config $cfg > "$OUT/bench_${cfg}_traffic.json" 2> "$OUT/bench_${cfg}_traffic.err"
     cat "$OUT/bench_${cfg}_traffic.json"
   fi
 done
 if has c5t; then  # after traffic_c5.json exists
-  timeout -k 10 600 python bench.py --config c5 --steps 2 > "$OUT/bench_c5_traffic.json" 2> "$OUT/bench_c5_traffic.err"
+  timeout -k 10 600 python bench.py --full --config c5 --steps 2 > "$OUT/bench_c5_traffic.json" 2> "$OUT/bench_c5_traffic.err"
   cat "$OUT/bench_c5_traffic.json"
 fi
 if has c3t; then  # bench after traffic.json exists: the line carries roofline.traffic
-  timeout -k 10 400 python bench.py > "$OUT/bench_c3_traffic.json" 2> "$OUT/bench_c3_traffic.err"
+  timeout -k 10 400 python bench.py --full > "$OUT/bench_c3_traffic.json" 2> "$OUT/bench_c3_traffic.err"
   cat "$OUT/bench_c3_traffic.json"
 fi
 echo "evidence $TAG done"
