@@ -28,6 +28,9 @@ struct fac_haystack {
 struct fac_stream {
   fac::StreamCore* s = nullptr;
 };
+struct fac_batch {
+  fac::Batch b;
+};
 
 namespace fac {
 
@@ -971,6 +974,206 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
   if (!v.empty()) std::memcpy(matches, v.data(), v.size() * sizeof(fac_match));
   *n_out = v.size();
   return FAC_OK;
+}
+
+// ---- batches (fac.h "Batches"): staging, search and per-document apply on the device
+
+static int batch_limits(uint64_t n_docs, uint64_t total_len) {
+  if (n_docs > fac::kBatchMaxDocs || total_len >= (1ull << fac::kDocTagShift))
+    return fail(FAC_E_UNSUPPORTED, "a batch holds at most 2^24 documents and fewer than 2^40 bytes");
+  return FAC_OK;
+}
+
+static int batch_stage_fail(fac_batch* fb, bool fresh, int rc, const std::string& err, uint64_t* err_doc,
+                            uint64_t* err_graphemes) {
+  if ((rc == FAC_E_INVALID || rc == FAC_E_HAYSTACK_TOO_LARGE) && fb->b.err_doc != ~0ull && err_doc) *err_doc = fb->b.err_doc;
+  if (rc == FAC_E_HAYSTACK_TOO_LARGE && err_graphemes) *err_graphemes = fb->b.err_graphemes;
+  if (fresh) {
+    fac::free_batch(fb->b);
+    delete fb;
+  } else {  // a failed restage leaves an empty batch
+    fb->b.n_docs = 0;
+    fb->b.n_segs = 0;
+    fb->b.windows = 0;
+    fb->b.h.len = 0;
+    fb->b.h.n = 0;
+  }
+  return fail(rc, rc == FAC_E_HAYSTACK_TOO_LARGE ? std::string("a document has more than u32::MAX grapheme clusters") : err);
+}
+
+int fac_batch_stage(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets, uint64_t n_docs,
+                    fac_batch** out, uint64_t* err_doc, uint64_t* err_graphemes) {
+  if (!engine || !out || (n_docs && !offsets)) return fail(FAC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  // the last offset is the byte count; everything else about the offsets is checked on the device
+  const uint64_t len = n_docs ? offsets[n_docs] : 0;
+  if (len && !utf8) return fail(FAC_E_INVALID, "NULL argument");
+  if (int rc = batch_limits(n_docs, len)) return rc;
+  const fac::Engine& e = engine->e;
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  fac_batch* fb = new (std::nothrow) fac_batch();
+  if (!fb) return fail(FAC_E_OOM, "out of host memory");
+  fac::Batch& b = fb->b;
+  b.h.device = e.device;
+  b.h.len = len;
+  b.n_docs = n_docs;
+  std::string err;
+  int rc = FAC_OK;
+  hipStream_t st = e.stream;
+  if (hipMalloc((void**)&b.h.d_utf8, std::max<uint64_t>(len, 16)) != hipSuccess ||
+      hipMalloc((void**)&b.d_offsets, (n_docs + 1) * 8) != hipSuccess) {
+    rc = FAC_E_OOM;
+    err = "hipMalloc of the batch failed";
+  }
+  b.h.own_utf8 = true;
+  b.own_offsets = true;
+  b.offsets_cap = n_docs + 1;
+  if (!rc && ((len && hipMemcpyAsync(b.h.d_utf8, utf8, len, hipMemcpyHostToDevice, st) != hipSuccess) ||
+              (n_docs && hipMemcpyAsync(b.d_offsets, offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess))) {
+    rc = FAC_E_HIP;
+    err = "hipMemcpyAsync of the batch failed";
+  }
+  if (!rc) rc = fac::stage_batch_device(e, b, st, err);
+  if (rc) return batch_stage_fail(fb, true, rc, err, err_doc, err_graphemes);
+  *out = fb;
+  return FAC_OK;
+}
+
+int fac_batch_stage_device(const fac_engine* engine, const uint8_t* d_utf8, const uint64_t* d_offsets, uint64_t n_docs,
+                           uint64_t total_len, void* stream, fac_batch** batch, uint64_t* err_doc,
+                           uint64_t* err_graphemes) {
+  if (!engine || !batch || (n_docs && !d_offsets) || (total_len && !d_utf8)) return fail(FAC_E_INVALID, "NULL argument");
+  if (!n_docs && total_len) return fail(FAC_E_INVALID, "bytes without documents");
+  if (int rc = batch_limits(n_docs, total_len)) return rc;
+  const fac::Engine& e = engine->e;
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  fac_batch* fb = *batch;
+  const bool fresh = fb == nullptr;
+  if (fresh) {
+    fb = new (std::nothrow) fac_batch();
+    if (!fb) return fail(FAC_E_OOM, "out of host memory");
+  } else if (fb->b.h.own_utf8 && fb->b.h.d_utf8) {
+    return fail(FAC_E_INVALID, "batch was not staged from device memory");
+  }
+  fac::Batch& b = fb->b;
+  b.h.device = e.device;
+  b.h.len = total_len;
+  b.h.d_utf8 = const_cast<uint8_t*>(d_utf8);
+  b.h.own_utf8 = false;
+  b.d_offsets = const_cast<uint64_t*>(d_offsets);
+  b.own_offsets = false;
+  b.n_docs = n_docs;
+  std::string err;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e.stream;
+  const int rc = fac::stage_batch_device(e, b, st, err);
+  if (rc) {
+    b.h.d_utf8 = nullptr;
+    b.d_offsets = nullptr;
+    return batch_stage_fail(fb, fresh, rc, err, err_doc, err_graphemes);
+  }
+  *batch = fb;
+  return FAC_OK;
+}
+
+void fac_batch_free(fac_batch* batch) {
+  if (!batch) return;
+  fac::free_batch(batch->b);
+  delete batch;
+}
+
+uint64_t fac_batch_docs(const fac_batch* batch) { return batch ? batch->b.n_docs : 0; }
+
+uint64_t fac_batch_doc_graphemes(const fac_batch* batch, uint64_t d, int32_t* is_ascii) {
+  if (is_ascii) *is_ascii = 1;
+  if (!batch || d >= batch->b.n_docs) return 0;
+  const fac::Batch& b = batch->b;
+  uint32_t f = 0;
+  fac::BatchTri t{0, 0, 0};
+  if (hipSetDevice(b.h.device) != hipSuccess || hipMemcpy(&f, b.d_flags + d, 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&t, b.d_tri_in + d, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  if (is_ascii) *is_ascii = (f & 2u) ? 0 : 1;
+  return t.w;
+}
+
+uint64_t fac_batch_grapheme_starts(const fac_batch* batch, uint64_t d, uint64_t* out, uint64_t cap) {
+  if (!batch || d >= batch->b.n_docs) return 0;
+  const fac::Batch& b = batch->b;
+  uint32_t f = 0;
+  fac::BatchTri t{0, 0, 0}, ex{0, 0, 0};
+  uint64_t lo = 0;
+  if (hipSetDevice(b.h.device) != hipSuccess || hipMemcpy(&f, b.d_flags + d, 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&t, b.d_tri_in + d, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&ex, b.d_tri_ex + d, sizeof(ex), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&lo, b.d_offsets + d, 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  const uint64_t n = t.w, k = std::min(n, cap);
+  if (!out || !k) return n;
+  if (!(f & 2u)) {
+    for (uint64_t g = 0; g < k; ++g) out[g] = g;
+    return n;
+  }
+  if (hipMemcpy(out, b.h.d_off + ex.u, k * 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  for (uint64_t g = 0; g < k; ++g) out[g] = (out[g] & ((1ull << fac::kDocTagShift) - 1)) - lo;
+  return n;
+}
+
+int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
+                     uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats) {
+  if (!engine || !batch || !args || !n_out || (!out && !args->device_out)) return fail(FAC_E_INVALID, "NULL argument");
+  if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
+    return fail(FAC_E_INVALID, "bad order/overlap");
+  if (out) *out = nullptr;
+  *n_out = 0;
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
+  if (e.has_map && !b.h.ascii)
+    return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
+  const uint64_t nd = b.n_docs;
+  std::string err;
+  // raw tagged records into a device buffer (grown and searched again if it was too small), then
+  // the per-document apply; nothing but counts visits the host
+  uint64_t cap = std::max<uint64_t>(4096, b.windows / 64);
+  for (;;) {
+    DevMem raw(st), doff(st);
+    if (int rc = raw.alloc(2 * cap * sizeof(fac_match), err)) return fail(rc, err);
+    if (int rc = doff.alloc((nd + 1) * 8, err)) return fail(rc, err);
+    fac::MatchSink sink;
+    sink.dev = static_cast<fac_match*>(raw.p);
+    sink.dev_cap = cap;
+    if (int rc = fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err)) return fail(rc, err);
+    if (stats) stats->graphemes = b.windows;
+    if (sink.n > cap) {
+      cap = sink.n;
+      continue;
+    }
+    fac_match* res = nullptr;
+    uint64_t n_res = 0;
+    uint64_t* d_doc = args->device_doc_offsets ? args->device_doc_offsets : static_cast<uint64_t*>(doff.p);
+    if (int rc = fac::apply_batch_device(e, sink.dev, sink.dev + cap, sink.n, b.d_offsets, nd, args->order, args->overlap,
+                                         args->unique_ids, st, d_doc, &res, &n_res, err))
+      return fail(rc, err);
+    *n_out = n_res;
+    if (args->device_out && n_res > args->device_cap)
+      return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*n_out = records needed)");
+    fac::MatchSink fin;
+    fin.dev = static_cast<fac_match*>(args->device_out);
+    fin.dev_cap = args->device_cap;
+    if (int rc = fac::sink_append_device(fin, res, n_res, st, err)) {
+      fac::result_free(fin.pinned);
+      return fail(rc, err);
+    }
+    if ((doc_offsets && hipMemcpyAsync(doc_offsets, d_doc, (nd + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      fac::result_free(fin.pinned);
+      return fail(FAC_E_HIP, "copy of the batch's records failed");
+    }
+    if (fin.dev) return FAC_OK;
+    return hand_out(fin, out, n_out);
+  }
 }
 
 int fac_stream_open(const fac_engine* engine, float threshold, uint64_t window_bytes, fac_stream** out) {

@@ -454,6 +454,50 @@ struct Haystack {
   uint64_t failed_n = 0;  // graphemes counted by a failed restage (stage_haystack_device), for the error
 };
 
+// A batch of independent documents staged on the device (stage_kernels.hip stage_batch_device,
+// fac.h fac_batch_*). `h` holds the concatenated bytes and, for the non-ASCII documents only, their
+// graphemes in document order: h.d_off[g] = global byte | document << kDocTagShift, h.d_text32[g];
+// h.ascii = every document is ASCII, h.n = graphemes of the non-ASCII documents. The descriptors of
+// the non-empty documents (d_segs, d_prefix: SearchParams::segs / seg_prefix) are written by the
+// device; byte_base carries the document tag, so every record's start and end come back tagged
+// (local_byte subtracts the tagged byte_base from the tagged d_off, and adds it back).
+constexpr uint32_t kDocTagShift = 40;
+constexpr uint64_t kBatchMaxDocs = 1ull << 24;
+struct BatchTri {  // per document: graphemes of a non-ASCII document, windows, 1 if not empty
+  uint64_t u, w, s;
+};
+struct Batch {
+  Haystack h;
+  uint64_t n_docs = 0;
+  uint64_t* d_offsets = nullptr;  // n_docs + 1 document byte offsets
+  bool own_offsets = false;
+  uint64_t offsets_cap = 0;       // entries an owned d_offsets holds
+  // per-document scratch, kept when staged again: flags[n_docs] (bit 0 invalid UTF-8, bit 1 not
+  // ASCII), tri_in / tri_ex[n_docs + 1] (counts and their exclusive scan), scal[8]
+  void* d_meta = nullptr;
+  size_t meta_cap = 0;
+  uint32_t* d_flags = nullptr;
+  BatchTri* d_tri_in = nullptr;
+  BatchTri* d_tri_ex = nullptr;
+  unsigned long long* d_scal = nullptr;
+  SegDesc* d_segs = nullptr;
+  uint64_t* d_prefix = nullptr;
+  uint64_t seg_cap = 0;
+  uint64_t n_segs = 0;   // non-empty documents
+  uint64_t windows = 0;  // start windows of all documents
+  uint64_t err_doc = 0, err_graphemes = 0;  // of a failed staging
+};
+// stage_kernels.hip: stages the documents [d_offsets[d], d_offsets[d + 1]) of b.h.d_utf8 (b.h.len
+// bytes, b.n_docs, b.d_offsets set by the caller) on st; synchronous
+int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& err);
+void free_batch(Batch& b);
+// rank_kernels.hip: FuzzyMatches::apply per document on the n tagged records at d_a (d_b: scratch of
+// n). Kept records, tag cleared and rebased to their document, go to *res (d_a or d_b) grouped by
+// document; d_doc_off (device, n_docs + 1) receives the CSR index
+int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t n, const uint64_t* d_offsets,
+                       uint64_t n_docs, int order, int overlap, const uint64_t* unique_ids, hipStream_t s,
+                       uint64_t* d_doc_off, fac_match** res, uint64_t* n_res, std::string& err);
+
 // Where a search delivers its records: a host vector (internal callers), a pooled pinned host
 // buffer handed to the C ABI caller (fac_search_staged / fac_search_raw: no page faults on the
 // D2H, result_alloc below), or the caller's device buffer (fac_search_staged_device: records stay
@@ -485,6 +529,13 @@ int launch_search(const Engine& e, const Haystack& h, const std::vector<SegDesc>
 // first window, for a shard of one haystack (search.rs:1096-1103); 0 for a whole search
 int launch_search_sink(const Engine& e, const Haystack& h, const std::vector<SegDesc>& segs, float thr,
                        hipStream_t stream, uint64_t ab_prefix, MatchSink& sink, fac_stats* stats, std::string& err);
+// The batch entry's search: the segment and window-prefix arrays are already on the device
+// (Batch::d_segs / d_prefix: non-empty segments, w_end <= n) and only the totals are known to the
+// host, so a million-document batch costs no per-document host loop and no descriptor upload.
+// Auto-beam engines read the descriptors back and take launch_search_sink's per-segment loop.
+// The prefix cache is gated by the batch's own rule, not by windows per segment.
+int launch_search_batch(const Engine& e, const Batch& b, float thr, hipStream_t stream, MatchSink& sink,
+                        fac_stats* stats, std::string& err);
 // auto-beam pass 1 alone: sum of queue.len() over the windows of `segs` searched unbeamed
 int auto_beam_total(const Engine& e, const Haystack& h, const std::vector<SegDesc>& segs, float thr,
                     hipStream_t stream, uint64_t& total, std::string& err);

@@ -467,6 +467,184 @@ int window_owned_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_
   return FAC_OK;
 }
 
+// ---------------------------------------------------------------- per-document apply of a batch
+// A batch's raw records carry their document in bits kDocTagShift.. of start and end (Batch,
+// fac_internal.h), so one sort keyed (document, RankCmp) ranks every document's records at once and
+// leaves them grouped by document. The overlap walks (matches.rs:83-149) then run one thread per
+// document over its ranked records: accepted spans sorted by start in the document's own index
+// range, and -- NonOverlappingUnique -- the uniqueness keys accepted so far, a set that is per
+// document (per search call in the crate), which is what makes the unique walk parallel here. Two
+// documents never meet in a walk, so spans that touch across a document boundary cannot interact.
+namespace {
+
+constexpr uint64_t kDocLow = (1ull << kDocTagShift) - 1;
+
+struct BatchCmp {  // (document, RankCmp); order 0: (document, start, end, pattern_index)
+  const uint32_t* plen;
+  int order;
+  __device__ bool operator()(const fac_match& a, const fac_match& b) const {
+    const uint64_t da = a.start >> kDocTagShift, db = b.start >> kDocTagShift;
+    if (da != db) return da < db;
+    if (order == 0) {
+      if (a.start != b.start) return a.start < b.start;
+      if (a.end != b.end) return a.end < b.end;
+      return a.pattern_index < b.pattern_index;
+    }
+    return RankCmp{plen, order}(a, b);
+  }
+};
+
+// CSR index of records grouped by document: doc_off[d] = the first record whose document is >= d.
+// keys: the tagged start of record i at base + i * stride.
+__global__ void batch_doc_index_kernel(const char* base, size_t stride, uint64_t n, uint64_t n_docs, uint64_t* doc_off) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d > n_docs) return;
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    const uint64_t k = *reinterpret_cast<const uint64_t*>(base + mid * stride) >> kDocTagShift;
+    if (k < d) lo = mid + 1;
+    else hi = mid;
+  }
+  doc_off[d] = lo;
+}
+
+// One thread per document: the reference's acceptance walk over the document's records in rank
+// order (walk_host above, on the device). occ / used: scratch of n entries, each document using the
+// index range of its own records.
+__global__ void batch_walk_kernel(const fac_match* __restrict__ m, const uint64_t* __restrict__ doc_off, uint64_t n_docs,
+                                  const uint64_t* __restrict__ uid, int unique, ulonglong2* __restrict__ occ,
+                                  uint64_t* __restrict__ used, uint8_t* __restrict__ keep) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= n_docs) return;
+  const uint64_t b = doc_off[d], e = doc_off[d + 1];
+  uint64_t k = 0;  // accepted so far
+  for (uint64_t i = b; i < e; ++i) {
+    const uint64_t ms = m[i].start, me = m[i].end;
+    uint64_t u = 0;
+    if (unique) {
+      u = uid ? uid[m[i].pattern_index] : m[i].pattern_index;
+      bool seen = false;
+      for (uint64_t t = 0; t < k && !seen; ++t) seen = used[b + t] == u;
+      if (seen) continue;
+    }
+    uint64_t lo = 0, hi = k;  // bisect_left on accepted starts
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if (occ[b + mid].x < ms) lo = mid + 1;
+      else hi = mid;
+    }
+    const bool prev_ok = lo == 0 || occ[b + lo - 1].y <= ms;
+    const bool next_ok = lo == k || occ[b + lo].x >= me;
+    if (!(prev_ok && next_ok)) continue;
+    for (uint64_t t = k; t > lo; --t) occ[b + t] = occ[b + t - 1];
+    occ[b + lo] = make_ulonglong2(ms, me);
+    if (unique) used[b + k] = u;
+    ++k;
+    keep[i] = 1;
+  }
+}
+
+// records leave the library relative to their own document, the tag cleared
+__device__ inline fac_match batch_rebase(fac_match r, const uint64_t* offsets) {
+  const uint64_t base = offsets[r.start >> kDocTagShift];
+  r.start = (r.start & kDocLow) - base;
+  r.end = (r.end & kDocLow) - base;
+  return r;
+}
+__global__ void batch_rebase_kernel(fac_match* m, uint64_t n, const uint64_t* offsets) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) m[i] = batch_rebase(m[i], offsets);
+}
+__global__ void batch_gather_kernel(const fac_match* m, const Span* order, uint64_t n, const uint64_t* offsets,
+                                    fac_match* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = batch_rebase(m[order[i].rank], offsets);
+}
+
+}  // namespace
+
+int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t n, const uint64_t* d_offsets,
+                       uint64_t n_docs, int order, int overlap, const uint64_t* unique_ids, hipStream_t s,
+                       uint64_t* d_doc_off, fac_match** res, uint64_t* n_res, std::string& err) {
+  *res = d_a;
+  *n_res = 0;
+  if (n == 0) {
+    RK_TRY(hipMemsetAsync(d_doc_off, 0, (n_docs + 1) * 8, s));
+    return FAC_OK;
+  }
+  if (n >= (1ull << 32)) {
+    err = "a batch search returned more than 2^32 records";
+    return FAC_E_UNSUPPORTED;
+  }
+  t_buf_stream = s;
+  const uint32_t T = 256;
+  const uint32_t G = (uint32_t)((n + T - 1) / T), GD = (uint32_t)((n_docs + 1 + T - 1) / T);
+  RK_TRY(dev_sort(d_a, d_b, n, BatchCmp{e.d_pat_bytes, order}, s));
+  fac_match* ranked = d_b;
+  if (overlap == 0) {
+    hipLaunchKernelGGL(batch_doc_index_kernel, dim3(GD), dim3(T), 0, s, reinterpret_cast<const char*>(ranked),
+                       sizeof(fac_match), n, n_docs, d_doc_off);
+    hipLaunchKernelGGL(batch_rebase_kernel, dim3(G), dim3(T), 0, s, ranked, n, d_offsets);
+    RK_TRY(hipGetLastError());
+    *res = ranked;
+    *n_res = n;
+    return FAC_OK;
+  }
+  Buf d_idx, d_occ, d_used, d_uid, d_keep, d_pos, d_kept, d_kept2;
+  RK_TRY(d_idx.alloc((n_docs + 1) * 8));
+  hipLaunchKernelGGL(batch_doc_index_kernel, dim3(GD), dim3(T), 0, s, reinterpret_cast<const char*>(ranked),
+                     sizeof(fac_match), n, n_docs, d_idx.as<uint64_t>());
+  RK_TRY(d_occ.alloc(n * sizeof(ulonglong2)));
+  RK_TRY(d_keep.alloc(n));
+  RK_TRY(hipMemsetAsync(d_keep.p, 0, n, s));
+  const bool unique = overlap == 2;
+  if (unique) {
+    RK_TRY(d_used.alloc(n * 8));
+    if (unique_ids) {
+      RK_TRY(d_uid.alloc(std::max<size_t>(e.pats.size(), 1) * 8));
+      RK_TRY(hipMemcpyAsync(d_uid.p, unique_ids, e.pats.size() * 8, hipMemcpyHostToDevice, s));
+    }
+  }
+  hipLaunchKernelGGL(batch_walk_kernel, dim3((uint32_t)((n_docs + T - 1) / T)), dim3(T), 0, s, ranked,
+                     d_idx.as<uint64_t>(), n_docs, unique && unique_ids ? d_uid.as<uint64_t>() : (const uint64_t*)nullptr,
+                     unique ? 1 : 0, d_occ.as<ulonglong2>(), d_used.as<uint64_t>(), d_keep.as<uint8_t>());
+  RK_TRY(hipGetLastError());
+  RK_TRY(d_pos.alloc(n * 4));
+  {
+    size_t bytes = 0;
+    RK_TRY(rocprim::inclusive_scan(nullptr, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
+                                   rocprim::plus<uint32_t>(), s));
+    Buf tmp;
+    RK_TRY(tmp.alloc(bytes));
+    RK_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
+                                   rocprim::plus<uint32_t>(), s));
+  }
+  uint32_t kept = 0;
+  RK_TRY(hipMemcpyAsync(&kept, d_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
+  RK_TRY(hipStreamSynchronize(s));  // (also: the pageable unique_ids were read)
+  *n_res = kept;
+  if (kept == 0) {
+    RK_TRY(hipMemsetAsync(d_doc_off, 0, (n_docs + 1) * 8, s));
+    return FAC_OK;
+  }
+  // the kept matches in (document, start) order, ties in acceptance (rank) order: the tagged start
+  // sorts by document first
+  RK_TRY(d_kept.alloc((uint64_t)kept * sizeof(Span)));
+  RK_TRY(d_kept2.alloc((uint64_t)kept * sizeof(Span)));
+  hipLaunchKernelGGL(kept_spans_kernel, dim3(G), dim3(T), 0, s, ranked, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
+                     d_kept.as<Span>());
+  RK_TRY(dev_sort(d_kept.as<Span>(), d_kept2.as<Span>(), kept, KeptByStart{}, s));
+  hipLaunchKernelGGL(batch_doc_index_kernel, dim3(GD), dim3(T), 0, s, reinterpret_cast<const char*>(d_kept2.p), sizeof(Span),
+                     (uint64_t)kept, n_docs, d_doc_off);
+  hipLaunchKernelGGL(batch_gather_kernel, dim3((kept + T - 1) / T), dim3(T), 0, s, ranked, d_kept2.as<Span>(), (uint64_t)kept,
+                     d_offsets, d_a);
+  RK_TRY(hipGetLastError());
+  // the scratch above goes back to the pool for this stream only: its later users are ordered after these kernels
+  *res = d_a;
+  return FAC_OK;
+}
+
 // A batch of stream windows' raw records (start and end tagged with the window, kWinTagShift): per window,
 // sorted().non_overlapping() and the matches starting before its commit point, rebased to stream
 // offsets (stream.rs:262-297), appended to `out` in window order with the tag cleared.

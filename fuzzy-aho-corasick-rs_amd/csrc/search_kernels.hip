@@ -5136,9 +5136,20 @@ int ensure_gids(const Engine& e, const Haystack& h, std::string& err) {
 // One search over the windows of `segs_in` with a given beam (0 = none). exact_dedup: the dedup
 // must be exact (beam, or auto-beam counting); counts (optional): per virtual window (non-empty
 // segments concatenated) the number of states pushed, the reference's queue.len().
+// dsegs (the batch entry, launch_search_batch): the non-empty segments and their window prefix are
+// already on the device and segs_in is empty; rc_seg_windows = the windows per segment the prefix
+// cache asks for (1024 for every other caller).
+constexpr uint64_t kBatchRcSegWindows = 0;
+struct DevSegs {
+  const SegDesc* segs;
+  const uint64_t* prefix;
+  uint32_t n;
+  uint64_t windows;
+  uint64_t rc_seg_windows;
+};
 int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& segs_in, float thr,
                 hipStream_t stream, uint32_t beam, bool exact_dedup, std::vector<uint32_t>* counts,
-                MatchSink& out, fac_stats* stats, std::string& err) {
+                MatchSink& out, fac_stats* stats, std::string& err, const DevSegs* dsegs = nullptr) {
   const auto t_begin = std::chrono::steady_clock::now();
   auto host_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
   const bool timing = diag_env("FAC_TIMING") != nullptr;  // diagnostics: host wall-clock phases
@@ -5153,8 +5164,10 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     segs.push_back(c);
     prefix.push_back(prefix.back() + (c.w_end - c.w_begin));
   }
-  uint64_t windows = prefix.back();  // (a key part: its own windows, set once they are listed)
+  uint64_t windows = dsegs ? dsegs->windows : prefix.back();  // (a key part: its own windows, set once they are listed)
   if (windows == 0) return FAC_OK;
+  const uint64_t n_segs = dsegs ? dsegs->n : segs.size();
+  const uint64_t rc_seg_windows = dsegs ? dsegs->rc_seg_windows : 1024ull;
 
   SearchParams P{};
   P.nodes = e.d_nodes;
@@ -5177,7 +5190,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   P.utf8 = h.d_utf8;
   P.text32 = h.d_text32;
   P.off = h.d_off;
-  P.n_segs = (uint32_t)segs.size();
+  P.n_segs = (uint32_t)n_segs;
   P.total_windows = windows;
   P.case_insensitive = e.case_insensitive;
   P.thr = thr;
@@ -5301,11 +5314,13 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     static_assert(ScratchSet::kSlots >= Engine::kScratch, "stream scratch slots");
     for (size_t i = 0; i < bufs.size(); ++i) bufs[i]->bind(&scratch_p[i], &scratch_n[i]);
   }
-  HIP_TRY(d_segs.alloc(segs.size() * sizeof(SegDesc), stream));
-  HIP_TRY(d_prefix.alloc(prefix.size() * sizeof(uint64_t), stream));
-  if (timing) std::fprintf(stderr, "FAC_TIMING launch_pass setup before the segment upload %.3f ms\n", host_ms());
-  HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipMemcpyAsync(d_prefix.p, prefix.data(), prefix.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  if (!dsegs) {
+    HIP_TRY(d_segs.alloc(segs.size() * sizeof(SegDesc), stream));
+    HIP_TRY(d_prefix.alloc(prefix.size() * sizeof(uint64_t), stream));
+    if (timing) std::fprintf(stderr, "FAC_TIMING launch_pass setup before the segment upload %.3f ms\n", host_ms());
+    HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_prefix.p, prefix.data(), prefix.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  }
   uint64_t out_cap = std::max<uint64_t>(4096, windows / 64);
   // beamed passes spill every window whose pending count passes 2 bw from the dedup-free first pass
   // (C3: ~5 % of its windows): a list too short re-runs the whole pass
@@ -5352,8 +5367,8 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   Events ev;
   HIP_TRY(hipEventCreate(&ev.a));
   HIP_TRY(hipEventCreate(&ev.b));
-  P.segs = static_cast<const SegDesc*>(d_segs.p);
-  P.seg_prefix = static_cast<const uint64_t*>(d_prefix.p);
+  P.segs = dsegs ? dsegs->segs : static_cast<const SegDesc*>(d_segs.p);
+  P.seg_prefix = dsegs ? dsegs->prefix : static_cast<const uint64_t*>(d_prefix.p);
   P.win_list = nullptr;
   P.kp_wlist = nullptr;
   // a key part (Haystack::kparts): its windows listed in ascending order; from here on `windows`
@@ -5446,7 +5461,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   // for the cache's counts and builds: C5 212.7 vs 241.5 Gchars/s with it off, round 5 profiles/r05s)
   if (!root_out && !e.has_map && fan_root + 1 <= 4096 && kVariants[vi].qcap <= 4096 &&
       windows >= (rc_min ? std::strtoull(rc_min, nullptr, 10) : 4096ull) &&
-      (rc_min || windows >= 1024ull * segs.size()) && !diag_env("FAC_NO_RC")) {
+      (rc_min || windows >= rc_seg_windows * n_segs) && !diag_env("FAC_NO_RC")) {
     auto env_u = [](const char* name, uint64_t dflt) {
       const char* v = diag_env(name);
       return v ? std::strtoull(v, nullptr, 10) : dflt;
@@ -6281,6 +6296,25 @@ int launch_search_sink(const Engine& e, const Haystack& h, const std::vector<Seg
   if ((rc = sink_append_host(out, kept.data(), kept.size(), stream, err))) return rc;
   if (tails.empty()) return FAC_OK;
   return launch_pass(e, h, tails, thr, stream, ab_beam, true, nullptr, out, stats, err);
+}
+
+int launch_search_batch(const Engine& e, const Batch& b, float thr, hipStream_t stream, MatchSink& sink,
+                        fac_stats* stats, std::string& err) {
+  if (b.n_segs == 0) return FAC_OK;
+  HIP_TRY(hipSetDevice(e.device));
+  if (!stream) stream = e.stream;
+  if (e.has_auto_beam && e.beam_width == 0) {  // the per-segment switch window needs each segment's counts in order
+    std::vector<SegDesc> segs(b.n_segs);
+    HIP_TRY(hipMemcpyAsync(segs.data(), b.d_segs, b.n_segs * sizeof(SegDesc), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return launch_search_sink(e, b.h, segs, thr, stream, 0, sink, stats, err);
+  }
+  // the batch's prefix-cache rule: windows per segment asked for, 0 = no such condition
+  uint64_t seg_windows = kBatchRcSegWindows;
+  if (const char* v = diag_env("FAC_BATCH_RC_SEG")) seg_windows = std::strtoull(v, nullptr, 10);
+  const DevSegs ds{b.d_segs, b.d_prefix, (uint32_t)b.n_segs, b.windows, seg_windows};
+  const uint32_t beam = (uint32_t)std::min<uint64_t>(e.beam_width, 0xFFFFFFFFull);
+  return launch_pass(e, b.h, {}, thr, stream, beam, beam != 0, nullptr, sink, stats, err, &ds);
 }
 
 int launch_search(const Engine& e, const Haystack& h, const std::vector<SegDesc>& segs, float thr,

@@ -17,6 +17,8 @@
 #include <cstring>
 #include <mutex>
 
+#include <rocprim/device/device_scan.hpp>
+
 #include "fac_internal.h"
 
 namespace fac {
@@ -670,6 +672,303 @@ int graphemes_before(const Haystack& h, uint64_t b, hipStream_t st, uint64_t& ou
   ST_TRY(hipMemcpyAsync(&v, d + 3, 8, hipMemcpyDeviceToHost, st));
   ST_TRY(hipStreamSynchronize(st));
   out = v;
+  return FAC_OK;
+}
+
+// ---------------------------------------------------------------- batch staging (fac_batch_*)
+// Every document of a batch is staged as if it were staged alone: the UTF-8 check and is_ascii
+// (search.rs:196) per document, UAX #29 segmentation of the non-ASCII documents from start-of-text
+// at each document's first byte, and one SegDesc per non-empty document, all on the device.
+// scal: [0] bit 0 bad offsets, bit 1 some document is not ASCII; [1] first invalid document,
+// [2] first document over the grapheme limit (both ~0: none).
+namespace {
+
+__global__ void batch_offsets_kernel(const uint64_t* __restrict__ off, uint64_t n_docs, uint64_t total,
+                                     unsigned long long* __restrict__ scal) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d > n_docs) return;
+  bool bad = false;
+  if (d == 0) bad = off[0] != 0;
+  if (d == n_docs) bad = bad || off[d] != total;
+  else bad = bad || off[d] > off[d + 1] || off[d + 1] > total;
+  if (bad) atomicOr(scal, 1ull);
+}
+
+// One wave per document: str::from_utf8 and str::is_ascii of its bytes alone. Each lane checks the
+// bytes it reads: a lead byte's whole sequence (inside the document, continuation bytes, shortest
+// form, no surrogate, <= U+10FFFF), a continuation byte that a lead byte at most three bytes before
+// it, inside the document, covers it.
+__global__ __launch_bounds__(256) void batch_doc_scan_kernel(const uint8_t* __restrict__ s, const uint64_t* __restrict__ off,
+                                                             uint64_t n_docs, uint32_t* __restrict__ flags,
+                                                             unsigned long long* __restrict__ scal) {
+  const uint64_t d = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64;
+  const uint32_t lane = threadIdx.x & 63u;
+  if (d >= n_docs) return;  // whole waves
+  const uint64_t a = off[d], b = off[d + 1];
+  auto lead_len = [](uint32_t c) -> uint32_t {
+    return (c & 0xE0u) == 0xC0u ? 2u : (c & 0xF0u) == 0xE0u ? 3u : (c & 0xF8u) == 0xF0u ? 4u : 0u;
+  };
+  bool hi = false, bad = false;
+  for (uint64_t p = a + lane; p < b; p += 64) {
+    const uint32_t c = s[p];
+    if (c < 0x80u) continue;
+    hi = true;
+    if ((c & 0xC0u) == 0x80u) {
+      uint32_t k = 1;
+      while (k <= 3 && p >= a + k && (s[p - k] & 0xC0u) == 0x80u) ++k;
+      if (k > 3 || p < a + k || lead_len(s[p - k]) <= k) bad = true;
+      continue;
+    }
+    const uint32_t len = lead_len(c);
+    if (len == 0 || p + len > b) {
+      bad = true;
+      continue;
+    }
+    uint32_t cp = len == 2 ? (c & 0x1Fu) : len == 3 ? (c & 0x0Fu) : (c & 0x07u);
+    for (uint32_t k = 1; k < len; ++k) {
+      const uint32_t x = s[p + k];
+      if ((x & 0xC0u) != 0x80u) bad = true;
+      cp = (cp << 6) | (x & 0x3Fu);
+    }
+    const uint32_t mn = len == 2 ? 0x80u : len == 3 ? 0x800u : 0x10000u;
+    if (cp < mn || cp > 0x10FFFFu || (cp >= 0xD800u && cp <= 0xDFFFu)) bad = true;
+  }
+  const bool any_hi = __ballot(hi) != 0, any_bad = __ballot(bad) != 0;
+  if (lane == 0) {
+    flags[d] = (any_bad ? 1u : 0u) | (any_hi ? 2u : 0u);
+    if (any_hi) atomicOr(scal, 2ull);
+    if (any_bad) atomicMin(scal + 1, (unsigned long long)d);
+  }
+}
+
+// One thread per non-ASCII document: unicode.cpp segment_graphemes over its bytes, the segmenter
+// starting from start-of-text at the document's first code point (so no left context crosses a
+// document boundary, whatever the run: regional indicators pair from the document's start, GB9/GB11/
+// GB9c see nothing before it). WRITE = false counts the graphemes (tri_in[d].u); WRITE = true writes
+// their tagged byte starts and folded first code points from the document's scanned base.
+template <bool WRITE>
+__global__ __launch_bounds__(64) void batch_seg_kernel(const uint8_t* __restrict__ s, const uint64_t* __restrict__ off,
+                                                       uint64_t n_docs, const uint32_t* __restrict__ flags,
+                                                       const uint8_t* __restrict__ ptab, const uint16_t* __restrict__ ltab,
+                                                       int ci, BatchTri* __restrict__ tri_in,
+                                                       const BatchTri* __restrict__ tri_ex, uint64_t* __restrict__ goff,
+                                                       uint32_t* __restrict__ text32) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= n_docs) return;
+  const uint32_t f = flags[d];
+  if (!(f & 2u) || (f & 1u)) {
+    if (!WRITE) tri_in[d].u = 0;
+    return;
+  }
+  const uint64_t a = off[d], b = off[d + 1];
+  const uint64_t tag = d << kDocTagShift;
+  uint64_t i = a, cnt = 0;
+  uint64_t base = 0;
+  if (WRITE) base = tri_ex[d].u;
+  SegState st{};
+  while (i < b) {
+    const uint64_t pos = i;
+    const uint32_t cp = decode(s, b, i);
+    const Props R = props_fast(ptab, cp);
+    bool br;
+    if (pos == a) {
+      st = seg_init(R);
+      br = true;
+    } else {
+      br = seg_step(st, R);
+    }
+    if (br) {
+      if (WRITE) {
+        goff[base + cnt] = pos | tag;
+        text32[base + cnt] = ci ? fold_fast(ltab, cp) : cp;
+      }
+      ++cnt;
+    }
+  }
+  if (!WRITE) tri_in[d].u = cnt;
+}
+
+// windows and the "not empty" flag per document (an ASCII document's graphemes are its bytes); the
+// first document over the grapheme limit
+__global__ void batch_tri_kernel(const uint64_t* __restrict__ off, uint64_t n_docs, const uint32_t* __restrict__ flags,
+                                 BatchTri* __restrict__ tri_in, uint64_t limit, unsigned long long* __restrict__ scal) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d > n_docs) return;
+  if (d == n_docs) {
+    tri_in[d] = BatchTri{0, 0, 0};
+    return;
+  }
+  const uint64_t n = (flags[d] & 2u) ? tri_in[d].u : off[d + 1] - off[d];
+  if (!(flags[d] & 2u)) tri_in[d].u = 0;
+  tri_in[d].w = n;
+  tri_in[d].s = n ? 1u : 0u;
+  if (n > limit) atomicMin(scal + 2, (unsigned long long)d);
+}
+
+struct TriPlus {
+  __host__ __device__ BatchTri operator()(const BatchTri& a, const BatchTri& b) const {
+    return BatchTri{a.u + b.u, a.w + b.w, a.s + b.s};
+  }
+};
+
+// One thread per document: the SegDesc of a non-empty document at its slot among the non-empty
+// ones, its window prefix, and (thread 0) the closing prefix entry.
+__global__ void batch_desc_kernel(const uint64_t* __restrict__ off, uint64_t n_docs, const uint32_t* __restrict__ flags,
+                                  const BatchTri* __restrict__ tri_in, const BatchTri* __restrict__ tri_ex,
+                                  SegDesc* __restrict__ segs, uint64_t* __restrict__ prefix) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= n_docs) return;
+  if (d == 0) prefix[tri_ex[n_docs].s] = tri_ex[n_docs].w;
+  const uint64_t n = tri_in[d].w;
+  if (n == 0) return;
+  const bool ascii = !(flags[d] & 2u);
+  SegDesc S;
+  S.text_base = ascii ? off[d] : tri_ex[d].u;
+  S.n = n;
+  S.avail = n;
+  S.hay_len = off[d + 1] - off[d];
+  S.byte_base = off[d] | (d << kDocTagShift);
+  S.w_begin = 0;
+  S.w_end = n;
+  S.ascii = ascii ? 1u : 0u;
+  S.pad = 0;
+  const uint64_t k = tri_ex[d].s;
+  segs[k] = S;
+  prefix[k] = tri_ex[d].w;
+}
+
+}  // namespace
+
+void free_batch(Batch& b) {
+  (void)hipSetDevice(b.h.device);
+  if (b.own_offsets && b.d_offsets) (void)hipFree(b.d_offsets);
+  b.d_offsets = nullptr;
+  if (b.d_meta) (void)hipFree(b.d_meta);
+  b.d_meta = nullptr;
+  if (b.d_segs) (void)hipFree(b.d_segs);
+  if (b.d_prefix) (void)hipFree(b.d_prefix);
+  b.d_segs = nullptr;
+  b.d_prefix = nullptr;
+  free_haystack(b.h);
+}
+
+int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& err) {
+  Haystack& h = b.h;
+  const uint64_t nd = b.n_docs, len = h.len;
+  b.n_segs = 0;
+  b.windows = 0;
+  b.err_doc = b.err_graphemes = 0;
+  h.ascii = true;
+  h.n = 0;
+  {
+    std::lock_guard<std::mutex> lk(h.host_mu);
+    h.host_ready = false;
+    h.utf8.clear();
+    h.starts.clear();
+  }
+  if (nd == 0) return FAC_OK;
+  // flags | tri_in | tri_ex | scal
+  const size_t tri_b = (nd + 1) * sizeof(BatchTri), flag_b = (nd * 4 + 15) & ~size_t(15);
+  const size_t need = flag_b + 2 * tri_b + 64;
+  if (b.meta_cap < need) {
+    if (b.d_meta) ST_TRY(hipFree(b.d_meta));
+    b.d_meta = nullptr;
+    b.meta_cap = 0;
+    ST_TRY(hipMalloc(&b.d_meta, need));
+    b.meta_cap = need;
+  }
+  uint8_t* m = static_cast<uint8_t*>(b.d_meta);
+  b.d_flags = reinterpret_cast<uint32_t*>(m);
+  b.d_tri_in = reinterpret_cast<BatchTri*>(m + flag_b);
+  b.d_tri_ex = reinterpret_cast<BatchTri*>(m + flag_b + tri_b);
+  b.d_scal = reinterpret_cast<unsigned long long*>(m + flag_b + 2 * tri_b);
+  const unsigned long long scal0[4] = {0ull, ~0ull, ~0ull, 0ull};
+  ST_TRY(hipMemcpyAsync(b.d_scal, scal0, sizeof(scal0), hipMemcpyHostToDevice, st));
+  const uint32_t T = 256;
+  const uint32_t G1 = (uint32_t)((nd + 1 + T - 1) / T);
+  // the offsets are checked before anything is read through them
+  hipLaunchKernelGGL(batch_offsets_kernel, dim3(G1), dim3(T), 0, st, b.d_offsets, nd, len, b.d_scal);
+  ST_TRY(hipGetLastError());
+  unsigned long long sc[4] = {0, 0, 0, 0};
+  ST_TRY(hipMemcpyAsync(sc, b.d_scal, sizeof(sc), hipMemcpyDeviceToHost, st));
+  ST_TRY(hipStreamSynchronize(st));
+  if (sc[0] & 1ull) {
+    err = "batch offsets must start at 0, not decrease, and end at the byte count";
+    b.err_doc = ~0ull;
+    return FAC_E_INVALID;
+  }
+  BmpTabs tabs;
+  if (int trc = bmp_tables(h.device, st, tabs, err)) return trc;
+  hipLaunchKernelGGL(batch_doc_scan_kernel, dim3((uint32_t)((nd + 3) / 4)), dim3(T), 0, st, h.d_utf8, b.d_offsets, nd,
+                     b.d_flags, b.d_scal);
+  // (every thread returns at once in an all-ASCII batch: no segmentation work)
+  hipLaunchKernelGGL(batch_seg_kernel<false>, dim3((uint32_t)((nd + 63) / 64)), dim3(64), 0, st, h.d_utf8, b.d_offsets, nd,
+                     b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, b.d_tri_ex, (uint64_t*)nullptr,
+                     (uint32_t*)nullptr);
+  hipLaunchKernelGGL(batch_tri_kernel, dim3(G1), dim3(T), 0, st, b.d_offsets, nd, b.d_flags, b.d_tri_in, grapheme_limit(),
+                     b.d_scal);
+  ST_TRY(hipGetLastError());
+  {
+    size_t bytes = 0;
+    ST_TRY(rocprim::exclusive_scan(nullptr, bytes, b.d_tri_in, b.d_tri_ex, BatchTri{0, 0, 0}, nd + 1, TriPlus{}, st));
+    hipError_t he = hipSuccess;
+    void* tmp = call_scratch_take(std::max<size_t>(bytes, 16), st, &he);
+    ST_TRY(he);
+    he = rocprim::exclusive_scan(tmp, bytes, b.d_tri_in, b.d_tri_ex, BatchTri{0, 0, 0}, nd + 1, TriPlus{}, st);
+    call_scratch_give(tmp, st);
+    ST_TRY(he);
+  }
+  BatchTri tot{0, 0, 0};
+  ST_TRY(hipMemcpyAsync(sc, b.d_scal, sizeof(sc), hipMemcpyDeviceToHost, st));
+  ST_TRY(hipMemcpyAsync(&tot, b.d_tri_ex + nd, sizeof(tot), hipMemcpyDeviceToHost, st));
+  ST_TRY(hipStreamSynchronize(st));
+  // search_raw applied to the documents in order: the first document that fails decides the error
+  // (an invalid document has no grapheme count, so only the valid ones can be too large)
+  if (sc[1] != ~0ull || sc[2] != ~0ull) {
+    if (sc[1] < sc[2]) {
+      b.err_doc = sc[1];
+      err = "a document of the batch is not valid UTF-8";
+      return FAC_E_INVALID;
+    }
+    b.err_doc = sc[2];
+    BatchTri t{0, 0, 0};
+    ST_TRY(hipMemcpyAsync(&t, b.d_tri_in + sc[2], sizeof(t), hipMemcpyDeviceToHost, st));
+    ST_TRY(hipStreamSynchronize(st));
+    b.err_graphemes = t.w;
+    return FAC_E_HAYSTACK_TOO_LARGE;
+  }
+  h.ascii = !(sc[0] & 2ull);
+  h.n = tot.u;
+  if (!h.ascii) {
+    if (h.off_cap < h.n + 1) {
+      if (h.d_off) ST_TRY(hipFree(h.d_off));
+      if (h.d_text32) ST_TRY(hipFree(h.d_text32));
+      h.d_off = nullptr;
+      h.d_text32 = nullptr;
+      h.off_cap = 0;
+      ST_TRY(hipMalloc((void**)&h.d_off, (h.n + 1) * 8));
+      ST_TRY(hipMalloc((void**)&h.d_text32, std::max<uint64_t>(h.n * 4, 16)));
+      h.off_cap = h.n + 1;
+    }
+    hipLaunchKernelGGL(batch_seg_kernel<true>, dim3((uint32_t)((nd + 63) / 64)), dim3(64), 0, st, h.d_utf8, b.d_offsets, nd,
+                       b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, b.d_tri_ex, h.d_off, h.d_text32);
+  }
+  if (b.seg_cap < tot.s + 1) {
+    if (b.d_segs) ST_TRY(hipFree(b.d_segs));
+    if (b.d_prefix) ST_TRY(hipFree(b.d_prefix));
+    b.d_segs = nullptr;
+    b.d_prefix = nullptr;
+    b.seg_cap = 0;
+    ST_TRY(hipMalloc((void**)&b.d_segs, (tot.s + 1) * sizeof(SegDesc)));
+    ST_TRY(hipMalloc((void**)&b.d_prefix, (tot.s + 1) * 8));
+    b.seg_cap = tot.s + 1;
+  }
+  hipLaunchKernelGGL(batch_desc_kernel, dim3((uint32_t)((nd + T - 1) / T)), dim3(T), 0, st, b.d_offsets, nd, b.d_flags,
+                     b.d_tri_in, b.d_tri_ex, b.d_segs, b.d_prefix);
+  ST_TRY(hipGetLastError());
+  ST_TRY(hipStreamSynchronize(st));
+  b.n_segs = tot.s;
+  b.windows = tot.w;
   return FAC_OK;
 }
 

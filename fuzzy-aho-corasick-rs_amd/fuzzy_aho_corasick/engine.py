@@ -6,14 +6,14 @@ import ctypes
 import os
 import sys
 import time
-from typing import Iterable, List, Optional, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 from . import _native
 
 _TIMING = bool(os.environ.get("FAC_TIMING"))  # diagnostics: host-side phase times
 from .matches import FuzzyMatch, FuzzyMatches
 from .structs import (DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge, Order, Overlap,
-                      Pattern, SearchOptions, Similarity, UnsupportedConfiguration, f32)
+                      Pattern, SearchError, SearchOptions, Similarity, UnsupportedConfiguration, f32)
 
 
 def _default_device() -> int:
@@ -356,6 +356,25 @@ class FuzzyAhoCorasick:
     # -- device-resident haystacks (bench / sharding)
     def stage(self, haystack: bytes) -> "StagedHaystack":
         return StagedHaystack(self, haystack)
+
+    # -- many independent haystacks in one device pass (fac_search_batch)
+    def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None) -> List[FuzzyMatches]:
+        """`[self.search(h, opts) for h in haystacks]` as one call: every haystack is staged, searched
+        and ranked as a text of its own (the crate has no such entry point; its answer to many
+        documents is one engine shared by threads). Errors name the first offending document
+        (`.doc` of the exception)."""
+        opts = opts or SearchOptions()
+        haystacks = list(haystacks)
+        enc = [h.encode("utf-8") for h in haystacks]
+        data, offsets = batch_offsets(enc)
+        recs, doc_off = StagedBatch(self, data, offsets).search_records(opts)
+        out = []
+        for d, (hay, raw) in enumerate(zip(haystacks, enc)):
+            rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
+                     int(r["insertions"]), int(r["deletions"]), int(r["substitutions"]), int(r["swaps"]),
+                     int(r["edits"])) for r in recs[int(doc_off[d]):int(doc_off[d + 1])]]
+            out.append(self._to_matches(hay, raw, rows))
+        return out
 
 
 class Prefiltered:
@@ -705,6 +724,136 @@ class StagedHaystack:
         if rc:
             _raise(rc)
         return _native.take_matches(out, n.value), st
+
+
+def batch_offsets(docs) -> Tuple[bytes, List[int]]:
+    """(concatenated bytes, offsets) of a list of `bytes` documents: document d is
+    data[offsets[d]:offsets[d + 1]] (the layout fac_batch_stage takes). Pure Python."""
+    offsets = [0]
+    for d in docs:
+        if not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError(f"batch documents must be bytes, got {type(d).__name__}")
+        offsets.append(offsets[-1] + len(d))
+    return b"".join(bytes(d) for d in docs), offsets
+
+
+def _raise_batch(rc: int, doc: int, graphemes: int):
+    try:
+        _raise(rc, graphemes)
+    except SearchError as ex:
+        ex.doc = doc  # the first offending document (None: not a per-document error)
+        raise
+
+
+class StagedBatch:
+    """A batch of independent documents staged into HBM once (fac_batch_stage) and searched many
+    times: document d is data[offsets[d]:offsets[d + 1]], staged as if it were staged alone (UTF-8
+    validity, is_ascii and grapheme segmentation per document)."""
+
+    def __init__(self, engine: FuzzyAhoCorasick, data: bytes, offsets):
+        import numpy as np
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        if off.ndim != 1 or len(off) < 1:
+            raise ValueError("offsets needs n_docs + 1 entries")
+        if int(off[-1]) != len(data) or (len(off) > 1 and int(off.max()) > len(data)):
+            # (the library cannot see the length of `data`: keep its reads inside the buffer)
+            raise DeviceError(_native.FAC_E_INVALID, "batch offsets must end at len(data) and stay inside it")
+        self.engine, self.data, self.n_docs = engine, data, len(off) - 1
+        h = ctypes.c_void_p()
+        ed = ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
+        eg = ctypes.c_uint64()
+        rc = _native.lib.fac_batch_stage(engine._h, data, off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                         self.n_docs, ctypes.byref(h), ctypes.byref(ed), ctypes.byref(eg))
+        if rc:
+            _raise_batch(rc, None if ed.value == 0xFFFFFFFFFFFFFFFF else ed.value, eg.value)
+        self._h = h
+        self._dev_out = self._dev_doc = None
+
+    @classmethod
+    def from_device(cls, engine: FuzzyAhoCorasick, d_utf8: int, d_offsets: int, n_docs: int, total_len: int,
+                    stream=None, reuse: "StagedBatch" = None) -> "StagedBatch":
+        """fac_batch_stage_device: the bytes (`d_utf8`, total_len of them) and the n_docs + 1 uint64
+        offsets (`d_offsets`) are device addresses, e.g. torch tensors' data_ptr() (borrowed: keep both
+        alive). `reuse`: a batch staged this way before, restaged in place and returned."""
+        h = ctypes.c_void_p(reuse._h.value if reuse is not None else None)
+        ed = ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
+        eg = ctypes.c_uint64()
+        rc = _native.lib.fac_batch_stage_device(engine._h, ctypes.c_void_p(d_utf8), ctypes.c_void_p(d_offsets), n_docs,
+                                                total_len, ctypes.c_void_p(stream or 0), ctypes.byref(h),
+                                                ctypes.byref(ed), ctypes.byref(eg))
+        if rc:
+            if reuse is not None:  # a failed restage leaves the batch empty
+                reuse.n_docs = 0
+            _raise_batch(rc, None if ed.value == 0xFFFFFFFFFFFFFFFF else ed.value, eg.value)
+        obj = reuse
+        if obj is None:
+            obj = cls.__new__(cls)
+            obj.engine, obj.data, obj._h = engine, None, h
+            obj._dev_out = obj._dev_doc = None
+        obj.n_docs = n_docs
+        return obj
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _native.lib is not None:
+            _native.lib.fac_batch_free(h)
+            self._h = None
+
+    def doc_graphemes(self, d: int) -> Tuple[int, bool]:
+        """(grapheme count, is_ascii) of document d."""
+        asc = ctypes.c_int32()
+        n = _native.lib.fac_batch_doc_graphemes(self._h, d, ctypes.byref(asc))
+        return int(n), bool(asc.value)
+
+    def grapheme_starts(self, d: int) -> List[int]:
+        """Document-relative byte start of every grapheme of document d."""
+        n, _ = self.doc_graphemes(d)
+        buf = (ctypes.c_uint64 * max(1, n))()
+        k = _native.lib.fac_batch_grapheme_starts(self._h, d, buf, n)
+        return list(buf[:min(n, k)])
+
+    def _args(self, opts: SearchOptions, stream=None) -> "_native.fac_batch_args":
+        a = _native.fac_batch_args()
+        a.threshold = f32(opts.threshold_)
+        a.order = opts.order_.value
+        a.overlap = opts.overlap_.value
+        a.unique_ids = self.engine._unique_ids()
+        a.stream = stream or None
+        return a
+
+    def search_records(self, opts: SearchOptions = None, out=None, stream=None, stats=None, doc_offsets_out=None):
+        """fac_search_batch: (records, doc_offsets). Records (MATCH_DTYPE) are grouped by document,
+        offsets relative to the record's own document, each document in FuzzyMatches::apply's order;
+        doc_offsets (n_docs + 1) indexes them. `out`: a uint8 CUDA tensor to leave the records in HBM
+        (32 bytes each): returns (the tensor's filled part, doc_offsets); FAC_E_OUTPUT_CAPACITY is
+        raised as DeviceError with `.needed` records when it is too small. `doc_offsets_out`: an int64
+        CUDA tensor of n_docs + 1 entries that also receives the index, in HBM."""
+        import numpy as np
+        opts = opts or SearchOptions()
+        a = self._args(opts, stream)
+        doc_off = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        ptr = ctypes.POINTER(_native.fac_match)()
+        if out is not None:
+            a.device_out = out.data_ptr()
+            a.device_cap = out.numel() // _native.REC_BYTES
+        if doc_offsets_out is not None:
+            if doc_offsets_out.numel() < self.n_docs + 1 or doc_offsets_out.element_size() != 8:
+                raise ValueError("doc_offsets_out needs n_docs + 1 64-bit entries")
+            a.device_doc_offsets = doc_offsets_out.data_ptr()
+        rc = _native.lib.fac_search_batch(self.engine._h, self._h, ctypes.byref(a),
+                                          None if out is not None else ctypes.byref(ptr), ctypes.byref(n),
+                                          doc_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                          ctypes.byref(stats) if stats is not None else None)
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed = int(n.value)
+                raise
+        if out is not None:
+            return out[: n.value * _native.REC_BYTES], doc_off
+        return _native.take_records(ptr, n.value), doc_off
 
 
 class FuzzyReplacer:

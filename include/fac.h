@@ -312,6 +312,72 @@ int fac_search_staged_prefiltered(const fac_engine* engine, const fac_haystack* 
 int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, int32_t order, int32_t overlap,
                       const uint64_t* unique_ids, uint64_t* n_out);
 
+/* ---- Batches: many independent haystacks ("documents") searched in one device pass.
+ *
+ * The crate's answer to many documents is one Sync engine shared by threads that call search once
+ * per document (structs.rs:528-567, query.rs:30); there is no search_many in the crate. A batch is
+ * that loop as one call: every document is staged as if it were staged alone (UTF-8 validity,
+ * is_ascii and UAX #29 segmentation are per document; a document start is start-of-text), searched
+ * as its own `haystack` argument of search_raw, and ranked with FuzzyMatches::apply on its own
+ * records. Staging, the segment descriptors, attribution, ranking and overlap resolution (the
+ * per-document "pattern used once" set of NonOverlappingUnique included) run on the device.
+ *
+ * Limits of the implementation (FAC_E_UNSUPPORTED, never a partial result): at most 2^24
+ * documents and fewer than 2^40 bytes in all (a record carries its document in bits 40..63 of
+ * start / end while it is inside the library; the tag is cleared before records leave it), and no
+ * engine with multi-character mappings when some document is not ASCII. Auto-beam engines read the
+ * segment descriptors back and run the per-segment auto-beam loop of fac_search_staged on the host.
+ * Pre-filtered batches, batched replace / segment helpers and multi-GPU batches are not provided. */
+typedef struct fac_batch fac_batch;
+
+/* Documents d = 0..n_docs-1 are bytes [offsets[d], offsets[d+1]) of utf8.
+ * offsets[0] == 0, non-decreasing; empty documents allowed. Errors follow search_raw applied to
+ * the documents in order: invalid UTF-8 gives FAC_E_INVALID with *err_doc = the first offending
+ * document (a sequence split by a document boundary makes both documents invalid); a document over
+ * the grapheme limit gives FAC_E_HAYSTACK_TOO_LARGE with *err_doc / *err_graphemes of the first
+ * such document; bad offsets give FAC_E_INVALID (*err_doc untouched). */
+int fac_batch_stage(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets, uint64_t n_docs,
+                    fac_batch** out, uint64_t* err_doc, uint64_t* err_graphemes);
+
+/* Bytes and offsets already in device memory (borrowed, like fac_haystack_stage_device: keep both
+ * alive and unchanged while the batch is used). total_len = offsets[n_docs]. *batch NULL, or an
+ * earlier batch of this function to restage in place (its device buffers are reused). Ordered on
+ * `stream` (NULL = the engine's), complete on return. On error *batch is left as passed; a batch
+ * whose restage failed is empty (zero documents). */
+int fac_batch_stage_device(const fac_engine* engine, const uint8_t* d_utf8, const uint64_t* d_offsets, uint64_t n_docs,
+                           uint64_t total_len, void* stream, fac_batch** batch, uint64_t* err_doc,
+                           uint64_t* err_graphemes);
+
+void fac_batch_free(fac_batch* batch);
+uint64_t fac_batch_docs(const fac_batch* batch);
+
+/* Tests and hosts: document d's grapheme count, is_ascii, and document-relative grapheme byte
+ * starts (writes up to `cap` entries, returns the count). */
+uint64_t fac_batch_doc_graphemes(const fac_batch* batch, uint64_t d, int32_t* is_ascii);
+uint64_t fac_batch_grapheme_starts(const fac_batch* batch, uint64_t d, uint64_t* out, uint64_t cap);
+
+typedef struct fac_batch_args {
+  float threshold;
+  int32_t order;               /* as fac_matches_apply */
+  int32_t overlap;             /* as fac_matches_apply */
+  const uint64_t* unique_ids;  /* as fac_matches_apply (host array, one key per pattern) */
+  void* stream;
+  void* device_out;            /* optional: records stay in HBM */
+  uint64_t device_cap;
+  uint64_t* device_doc_offsets; /* optional: n_docs+1 entries on the device */
+} fac_batch_args;
+
+/* Records grouped by document, ascending document index. start/end are relative to the record's
+ * own document. doc_offsets (caller's host array, n_docs+1 entries) is the CSR index into the
+ * records. Within a document: the order FuzzyMatches::apply(order, overlap) gives. For
+ * Unsorted+Keep the order within a document is unspecified; Unsorted with an overlap mode walks a
+ * document's records in (start, end, pattern_index) order (the crate walks its hash map's order).
+ * Records go to the host (*out, fac_matches_free) or, with device_out set, into that device buffer
+ * of device_cap records; FAC_E_OUTPUT_CAPACITY: the buffer is too small, *n_out holds the count
+ * needed and nothing was written. */
+int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
+                     uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats);
+
 /* Streaming search (stream.rs:77-297): feed the input in the reader's read() pieces; windows
  * of `window_bytes` (0 = the crate's 256 KiB) are cut, searched (sorted + non-overlapping) and
  * their owned matches returned with absolute byte offsets, exactly like search_stream. Two windows

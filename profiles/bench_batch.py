@@ -1,0 +1,185 @@
+#!/usr/bin/env python3
+"""Batch search against the per-document loop.
+
+The texts of workloads.config("c2") and config("c3") are cut into documents at the space nearest
+every L bytes and searched three ways in one process, on device-resident bytes, after a warm-up:
+
+  (a) one fac_search_batch call over every document (records left in HBM, Unsorted + Keep),
+      timed with device events on the call's stream; run once per prefix-cache rule
+      (FAC_BATCH_RC_SEG: windows per segment the cache asks for; 0 = no such condition),
+  (b) the per-document loop fac_search_raw(doc) over a fixed sample of documents, host wall clock
+      (every call ends synchronised); repeated to get its spread; legs (a) and (b) alternate,
+  (c) the same bytes as ONE haystack through fac_search_staged: the boundary-free ceiling, a
+      different result set, shown for scale only.
+
+Staging is reported in ms per GiB: the batch stager against fac_haystack_stage_device on the same
+bytes. One JSON line per configuration; "gate" is true when (a) beats (b) per document by more than
+(b)'s own spread and (a)'s records for the sample equal (b)'s.
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+os.environ["FAC_DIAGNOSTICS"] = "1"  # the cache-rule knob is a diagnostics knob
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "fuzzy-aho-corasick-rs_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from fuzzy_aho_corasick import SearchOptions, StagedBatch, StagedHaystack, _native, workloads  # noqa: E402
+from fuzzy_aho_corasick.structs import f32  # noqa: E402
+
+
+def cut_documents(data: bytes, L: int) -> np.ndarray:
+    """Offsets of the documents: a cut after the space nearest every L bytes."""
+    b = np.frombuffer(data, np.uint8)
+    sp = np.flatnonzero(b == 0x20)
+    tg = np.arange(L, len(data), L)
+    i = np.clip(np.searchsorted(sp, tg), 1, len(sp) - 1)
+    near = np.where(tg - sp[i - 1] <= sp[i] - tg, sp[i - 1], sp[i]) + 1
+    return np.unique(np.concatenate([[0], near, [len(data)]])).astype(np.uint64)
+
+
+def raw_records(engine, doc: bytes, thr: float):
+    out = ctypes.POINTER(_native.fac_match)()
+    n = ctypes.c_uint64()
+    eg = ctypes.c_uint64()
+    rc = _native.lib.fac_search_raw(engine._h, doc, len(doc), f32(thr), ctypes.byref(out), ctypes.byref(n), ctypes.byref(eg))
+    if rc:
+        raise RuntimeError(_native.last_error())
+    return _native.take_records(out, n.value)
+
+
+def timed(stream, fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(stream)
+    r = fn()
+    b.record(stream)
+    b.synchronize()
+    return a.elapsed_time(b), r
+
+
+_CACHE = {}
+
+
+def workload(name, nbytes):
+    if (name, nbytes) not in _CACHE:
+        w = workloads.config(name, nbytes)
+        _CACHE[(name, nbytes)] = (w, workloads.builder_for(w).build(w.patterns))
+    return _CACHE[(name, nbytes)]
+
+
+def run(name, nbytes, L, sample, rounds, rules, profile_only):
+    w, engine = workload(name, nbytes)
+    data = w.haystack
+    off = cut_documents(data, L)
+    nd = len(off) - 1
+    dev = torch.device("cuda", engine.device)
+    t_data = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
+    t_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    sh = stream.cuda_stream
+    opts = SearchOptions().threshold(w.threshold)
+    out = torch.empty(max(1 << 16, len(data) // 16) * 32, dtype=torch.uint8, device=dev)
+
+    def stage_batch(reuse=None):
+        return StagedBatch.from_device(engine, t_data.data_ptr(), t_off.data_ptr(), nd, len(data), stream=sh, reuse=reuse)
+
+    def batch_search(sb):
+        nonlocal out
+        while True:
+            try:
+                return sb.search_records(opts, out=out, stream=sh)
+            except Exception as ex:  # FAC_E_OUTPUT_CAPACITY: grow and search again
+                need = getattr(ex, "needed", 0)
+                if not need:
+                    raise
+                out = torch.empty(int(need * 1.1 + 1024) * 32, dtype=torch.uint8, device=dev)
+
+    if profile_only == "c":  # the one-haystack leg alone
+        hay = StagedHaystack.from_device(engine, t_data.data_ptr(), len(data), stream=sh)
+        for _ in range(4):
+            hay = StagedHaystack.from_device(engine, t_data.data_ptr(), len(data), stream=sh, reuse=hay)
+            hay.search_device(w.threshold, stream=sh)
+        return None
+    sb = stage_batch()
+    for rule in rules:  # warm-up: buffers, tables, the output size
+        os.environ["FAC_BATCH_RC_SEG"] = str(rule)
+        batch_search(sb)
+    if profile_only:
+        os.environ.pop("FAC_BATCH_RC_SEG")
+        for _ in range(3):
+            sb = stage_batch(sb)
+            batch_search(sb)
+        return None
+    idx = np.unique(np.linspace(0, nd - 1, min(sample, nd)).astype(np.int64))
+    docs = [data[int(off[d]):int(off[d + 1])] for d in idx]
+    for d in docs[:50]:
+        raw_records(engine, d, w.threshold)
+    a_ms = {r: [] for r in rules}
+    b_ms = []
+    for _ in range(rounds):
+        for rule in rules:
+            os.environ["FAC_BATCH_RC_SEG"] = str(rule)
+            ms, (recs, doc_off) = timed(stream, lambda: batch_search(sb))
+            a_ms[rule].append(ms)
+        t0 = time.perf_counter()
+        per_doc = [raw_records(engine, d, w.threshold) for d in docs]
+        b_ms.append(1e3 * (time.perf_counter() - t0))
+    os.environ.pop("FAC_BATCH_RC_SEG")
+    # (a)'s records of the sample against (b)'s
+    host = np.frombuffer(recs.cpu().numpy().tobytes(), dtype=_native.MATCH_DTYPE)
+    key = lambda r: sorted(zip(r["start"].tolist(), r["end"].tolist(), r["pattern_index"].tolist(),  # noqa: E731
+                               r["similarity"].view(np.uint32).tolist(), r["edits"].tolist()))
+    same = all(key(host[int(doc_off[d]):int(doc_off[d + 1])]) == key(p) for d, p in zip(idx, per_doc))
+    # staging, and the one-haystack ceiling
+    st_b = [timed(stream, lambda: stage_batch(sb))[0] for _ in range(rounds)]
+    hay = StagedHaystack.from_device(engine, t_data.data_ptr(), len(data), stream=sh)
+    st_h = [timed(stream, lambda: StagedHaystack.from_device(engine, t_data.data_ptr(), len(data), stream=sh, reuse=hay))[0]
+            for _ in range(rounds)]
+    hay.search_device(w.threshold, stream=sh)
+    c_ms = [timed(stream, lambda: hay.search_device(w.threshold, stream=sh))[0] for _ in range(rounds)]
+    gib = len(data) / float(1 << 30)
+    b_doc = [m / len(docs) for m in b_ms]
+    res = {"config": name, "bytes": len(data), "L": L, "docs": nd, "sample": len(docs), "records": int(len(host)),
+           "a_ms": {str(r): [round(x, 3) for x in v] for r, v in a_ms.items()},
+           "b_sample_ms": [round(x, 2) for x in b_ms], "c_ms": [round(x, 3) for x in c_ms],
+           "stage_batch_ms_per_gib": round(min(st_b) / gib, 2), "stage_haystack_ms_per_gib": round(min(st_h) / gib, 2),
+           "records_equal": bool(same)}
+    best_rule = min(rules, key=lambda r: float(np.median(a_ms[r])))
+    a_doc = float(np.median(a_ms[best_rule])) / nd
+    res.update({"best_rule": best_rule, "a_us_per_doc": round(1e3 * a_doc, 4),
+                "b_us_per_doc": [round(1e3 * x, 2) for x in b_doc], "b_spread_us": round(1e3 * (max(b_doc) - min(b_doc)), 2),
+                "a_over_b": round(a_doc / float(np.median(b_doc)), 6),
+                "a_over_c": round(float(np.median(a_ms[best_rule])) / float(np.median(c_ms)), 3),
+                "gate": bool(same and min(b_doc) - a_doc > max(b_doc) - min(b_doc))})
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--c2-bytes", type=int, default=64 << 20)
+    ap.add_argument("--c3-bytes", type=int, default=16 << 20)
+    ap.add_argument("--lengths", type=int, nargs="+", default=[64, 1024])
+    ap.add_argument("--configs", nargs="+", default=["c2", "c3"])
+    ap.add_argument("--sample", type=int, default=2000)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--rules", type=int, nargs="+", default=[0, 1024],
+                    help="prefix-cache rules to time for leg (a): windows per segment asked for")
+    ap.add_argument("--profile-only", nargs="?", const="a", choices=["a", "c"], default=None,
+                    help="a few calls of leg (a) (default) or (c) and nothing else (for rocprofv3)")
+    args = ap.parse_args()
+    for name in args.configs:
+        for L in args.lengths:
+            res = run(name, args.c2_bytes if name == "c2" else args.c3_bytes, L, args.sample, args.rounds, args.rules,
+                      args.profile_only)
+            if res is not None:
+                print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
