@@ -31,6 +31,9 @@ struct fac_stream {
 struct fac_batch {
   fac::Batch b;
 };
+struct fac_replacements {
+  fac::ReplaceTable t;
+};
 
 namespace fac {
 
@@ -1173,6 +1176,135 @@ int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac
     }
     if (fin.dev) return FAC_OK;
     return hand_out(fin, out, n_out);
+  }
+}
+
+// ---- batched replace (fac.h "Batched replace"): the table, then search + apply + splice
+
+int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
+                            const uint8_t* keep, uint64_t n_patterns, fac_replacements** out) {
+  if (!engine || !out || !offsets) return fail(FAC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  const fac::Engine& e = engine->e;
+  if (n_patterns != e.pats.size()) return fail(FAC_E_INVALID, "the table needs one replacement per pattern of the engine");
+  if (offsets[0] != 0) return fail(FAC_E_INVALID, "replacement offsets must start at 0");
+  for (uint64_t p = 0; p < n_patterns; ++p)
+    if (offsets[p + 1] < offsets[p]) return fail(FAC_E_INVALID, "replacement offsets must not decrease");
+  const uint64_t bytes = offsets[n_patterns];
+  if (bytes && !utf8) return fail(FAC_E_INVALID, "NULL argument");
+  if (bytes >= (1ull << 32)) return fail(FAC_E_UNSUPPORTED, "a replacement table holds fewer than 2^32 bytes");
+  std::vector<uint2> tab(std::max<uint64_t>(n_patterns, 1), make_uint2(0, 0));
+  for (uint64_t p = 0; p < n_patterns; ++p) {
+    const uint64_t b = offsets[p], len = offsets[p + 1] - b;
+    if (keep && keep[p]) {
+      tab[p] = make_uint2(0, fac::kReplaceKeep);
+      continue;
+    }
+    if (!fac::utf8_valid(utf8 + b, len)) return fail(FAC_E_INVALID, "a replacement is not valid UTF-8");
+    tab[p] = make_uint2((uint32_t)b, (uint32_t)len);
+  }
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  fac_replacements* fr = new (std::nothrow) fac_replacements();
+  if (!fr) return fail(FAC_E_OOM, "out of host memory");
+  fac::ReplaceTable& t = fr->t;
+  t.device = e.device;
+  t.n_patterns = n_patterns;
+  if (hipMalloc((void**)&t.d_tab, tab.size() * sizeof(uint2)) != hipSuccess ||
+      hipMalloc((void**)&t.d_bytes, std::max<uint64_t>(bytes, 16)) != hipSuccess) {
+    fac_replacements_free(fr);
+    return fail(FAC_E_OOM, "hipMalloc of the replacement table failed");
+  }
+  if (hipMemcpy(t.d_tab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess ||
+      (bytes && hipMemcpy(t.d_bytes, utf8, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+    fac_replacements_free(fr);
+    return fail(FAC_E_HIP, "upload of the replacement table failed");
+  }
+  *out = fr;
+  return FAC_OK;
+}
+
+void fac_replacements_free(fac_replacements* replacements) {
+  if (!replacements) return;
+  if (replacements->t.d_tab || replacements->t.d_bytes) (void)hipSetDevice(replacements->t.device);
+  if (replacements->t.d_tab) (void)hipFree(replacements->t.d_tab);
+  if (replacements->t.d_bytes) (void)hipFree(replacements->t.d_bytes);
+  delete replacements;
+}
+
+int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
+                      const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                      uint64_t* n_replaced, fac_stats* stats) {
+  if (!engine || !batch || !replacements || !args || !out_len || (!out && !args->device_out))
+    return fail(FAC_E_INVALID, "NULL argument");
+  if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
+    return fail(FAC_E_INVALID, "bad order/overlap");
+  if (out) *out = nullptr;
+  *out_len = 0;
+  if (n_replaced) *n_replaced = 0;
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  const fac::ReplaceTable& t = replacements->t;
+  if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
+  if (t.device != e.device || t.n_patterns != e.pats.size())
+    return fail(FAC_E_INVALID, "the replacement table was built for another engine");
+  if (e.has_map && !b.h.ascii)
+    return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
+  // `segmented` (query.rs:46-64): the splice needs start order and disjoint spans
+  const int order = args->order == 0 ? 1 : args->order, overlap = args->overlap == 0 ? 1 : args->overlap;
+  const uint64_t nd = b.n_docs;
+  std::string err;
+  // fac_search_batch's search and per-document apply, then the splice from the kept records in HBM
+  uint64_t cap = std::max<uint64_t>(4096, b.windows / 64);
+  for (;;) {
+    DevMem raw(st), doff(st), obuf(st);
+    if (int rc = raw.alloc(2 * cap * sizeof(fac_match), err)) return fail(rc, err);
+    if (int rc = doff.alloc((nd + 1) * 8, err)) return fail(rc, err);
+    fac::MatchSink sink;
+    sink.dev = static_cast<fac_match*>(raw.p);
+    sink.dev_cap = cap;
+    if (int rc = fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err)) return fail(rc, err);
+    if (stats) stats->graphemes = b.windows;
+    if (sink.n > cap) {
+      cap = sink.n;
+      continue;
+    }
+    fac_match* res = nullptr;
+    uint64_t n_res = 0;
+    uint64_t* d_doc = static_cast<uint64_t*>(doff.p);
+    if (int rc = fac::apply_batch_device(e, sink.dev, sink.dev + cap, sink.n, b.d_offsets, nd, order, overlap,
+                                         args->unique_ids, st, d_doc, &res, &n_res, err))
+      return fail(rc, err);
+    fac::ReplacePlan plan;
+    if (int rc = fac::replace_plan_device(b, t, res, n_res, d_doc, st, plan, err)) return fail(rc, err);
+    *out_len = plan.total;
+    if (n_replaced) *n_replaced = plan.n_replaced;
+    if (plan.total >= (1ull << fac::kDocTagShift))
+      return fail(FAC_E_UNSUPPORTED, "the replaced batch would hold 2^40 bytes or more");
+    if (args->device_out && plan.total > args->device_cap)
+      return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*out_len = bytes needed)");
+    uint8_t* d_out = static_cast<uint8_t*>(args->device_out);
+    if (!d_out) {
+      if (int rc = obuf.alloc(plan.total, err)) return fail(rc, err);
+      d_out = static_cast<uint8_t*>(obuf.p);
+    }
+    if (int rc = fac::replace_copy_device(b, t, res, d_doc, plan, d_out, err)) return fail(rc, err);
+    uint8_t* host = nullptr;
+    if (!args->device_out) {
+      host = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(plan.total, 1)));
+      if (!host) return fail(FAC_E_OOM, "out of host memory");
+    }
+    if ((host && plan.total && hipMemcpyAsync(host, d_out, plan.total, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (args->device_out_offsets &&
+         hipMemcpyAsync(args->device_out_offsets, plan.d_out_off, (nd + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+        (out_offsets && hipMemcpyAsync(out_offsets, plan.d_out_off, (nd + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      std::free(host);
+      return fail(FAC_E_HIP, "copy of the replaced batch failed");
+    }
+    if (host) *out = host;
+    return FAC_OK;
   }
 }
 

@@ -498,6 +498,41 @@ int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t
                        uint64_t n_docs, int order, int overlap, const uint64_t* unique_ids, hipStream_t s,
                        uint64_t* d_doc_off, fac_match** res, uint64_t* n_res, std::string& err);
 
+// replace_kernels.hip: the splice of a batch (fac.h fac_replace_batch; matches.rs:165-188 per
+// document). A replacement table holds per pattern {offset into d_bytes, byte length}, the length
+// kReplaceKeep for "keep the matched text" (the callback's None, matches.rs:180-183).
+constexpr uint32_t kReplaceKeep = 0xFFFFFFFFu;
+constexpr uint32_t kReplaceTile = 4096;  // output bytes one workgroup of replace_copy_kernel owns
+struct ReplaceTable {
+  int device = 0;
+  uint64_t n_patterns = 0;
+  uint2* d_tab = nullptr;
+  uint8_t* d_bytes = nullptr;
+};
+// The plan of one call: per kept record {output offset of its piece within its document's output
+// (bit 63: the guard skipped the record), source offset its preceding gap starts at}, and the
+// n_docs + 1 output offsets. Scratch comes from the stream's pool and goes back with the plan.
+void call_scratch_give(void* p, hipStream_t s);  // (declared with the pool below)
+struct ReplacePlan {
+  hipStream_t s = nullptr;
+  void* mem = nullptr;
+  ulonglong2* d_plan = nullptr;
+  uint64_t* d_out_off = nullptr;
+  uint64_t total = 0;       // output bytes of the whole batch
+  uint64_t n_replaced = 0;  // records the splice applied
+  ~ReplacePlan() {
+    if (mem) call_scratch_give(mem, s);
+  }
+};
+// d_recs / d_doc_off: apply_batch_device's result (kept records in (document, start, acceptance)
+// order, document-relative, and their CSR index). Plans the splice and scans the output lengths on
+// s; synchronises once to read total and n_replaced back.
+int replace_plan_device(const Batch& b, const ReplaceTable& t, const fac_match* d_recs, uint64_t n_recs,
+                        const uint64_t* d_doc_off, hipStream_t s, ReplacePlan& plan, std::string& err);
+// Writes the plan.total output bytes to d_out (asynchronous on plan.s).
+int replace_copy_device(const Batch& b, const ReplaceTable& t, const fac_match* d_recs, const uint64_t* d_doc_off,
+                        const ReplacePlan& plan, uint8_t* d_out, std::string& err);
+
 // Where a search delivers its records: a host vector (internal callers), a pooled pinned host
 // buffer handed to the C ABI caller (fac_search_staged / fac_search_raw: no page faults on the
 // D2H, result_alloc below), or the caller's device buffer (fac_search_staged_device: records stay

@@ -4,8 +4,8 @@ Mirrors the crate's public API (lib.rs:96-105): FuzzyAhoCorasickBuilder, FuzzyAh
 FuzzyLimits, FuzzyPenalties, Pattern, SearchOptions, Order, Overlap, FuzzyMatch, FuzzyMatches,
 Segment, Similarity, SearchError. The search itself runs in HIP kernels (libfac.so).
 """
-from .engine import (FuzzyAhoCorasick, FuzzyAhoCorasickBuilder, FuzzyReplacer, Prefiltered,
-                     StagedBatch, StagedHaystack, StreamMatch, batch_offsets)
+from .engine import (FuzzyAhoCorasick, FuzzyAhoCorasickBuilder, FuzzyReplacer, Prefiltered, ReplacementTable,
+                     StagedBatch, StagedHaystack, StreamMatch, batch_offsets, replacement_table)
 from .matches import FuzzyMatch, FuzzyMatches, Segment, UnmatchedSegment
 from .structs import (DEFAULT_THRESHOLD, DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge,
                       Order, Overlap, Pattern, SearchError, SearchOptions, Similarity,
@@ -13,7 +13,7 @@ from .structs import (DEFAULT_THRESHOLD, DeviceError, FuzzyLimits, FuzzyPenaltie
 
 __all__ = [
     "FuzzyAhoCorasick", "FuzzyAhoCorasickBuilder", "FuzzyReplacer", "Prefiltered", "StagedHaystack", "StreamMatch",
-    "StagedBatch", "batch_offsets",
+    "StagedBatch", "batch_offsets", "ReplacementTable", "replacement_table",
     "FuzzyMatch", "FuzzyMatches", "Segment", "UnmatchedSegment", "DEFAULT_THRESHOLD", "DeviceError",
     "FuzzyLimits", "FuzzyPenalties", "HaystackTooLarge", "Order", "Overlap", "Pattern", "SearchError",
     "SearchOptions", "Similarity", "UnsupportedConfiguration",

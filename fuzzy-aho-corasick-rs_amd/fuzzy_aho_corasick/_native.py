@@ -95,6 +95,15 @@ class fac_batch_args(ctypes.Structure):
                 ("device_doc_offsets", ctypes.c_void_p)]
 
 
+class fac_replace_args(ctypes.Structure):
+    _fields_ = [("threshold", ctypes.c_float), ("order", ctypes.c_int32), ("overlap", ctypes.c_int32),
+                ("unique_ids", ctypes.POINTER(ctypes.c_uint64)), ("stream", ctypes.c_void_p),
+                ("device_out", ctypes.c_void_p), ("device_cap", ctypes.c_uint64),
+                ("device_out_offsets", ctypes.c_void_p)]
+
+
+REPLACE_TILE = 4096  # output bytes one workgroup of the splice's copy kernel owns (kReplaceTile)
+
 assert ctypes.sizeof(fac_match) == 32
 
 if not os.path.exists(LIB_PATH):
@@ -190,6 +199,11 @@ SIGNATURES = {
     "fac_batch_grapheme_starts": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _u64p, ctypes.c_uint64]),
     "fac_search_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_batch_args), _P(_P(fac_match)), _u64p,
                                         _u64p, _P(fac_stats)]),
+    "fac_replacements_create": (ctypes.c_int, [_engine_p, ctypes.c_char_p, _u64p, ctypes.c_char_p, ctypes.c_uint64,
+                                               _P(ctypes.c_void_p)]),
+    "fac_replacements_free": (None, [ctypes.c_void_p]),
+    "fac_replace_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_replace_args),
+                                         _P(_P(ctypes.c_uint8)), _u64p, _u64p, _u64p, _P(fac_stats)]),
     "fac_edge_order": (None, [ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "fac_diag_beam_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),

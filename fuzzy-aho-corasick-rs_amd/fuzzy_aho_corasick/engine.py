@@ -376,6 +376,19 @@ class FuzzyAhoCorasick:
             out.append(self._to_matches(hay, raw, rows))
         return out
 
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements) -> List[str]:
+        """`[self.replace(t, opts, lambda m: replacements[m.pattern_index]) for t in texts]` as one
+        call (fac_replace_batch): searched, ranked and spliced on the device. `replacements` has one
+        entry per pattern, `None` = keep the matched text (the callback's None, matches.rs:180-183).
+        A per-match callback cannot run on the device; a per-pattern table is what FuzzyReplacer
+        uses (replacer.rs:24). Kept records of equal start are applied in the order search_batch
+        returns them (the crate leaves that order open, matches.rs:111)."""
+        enc = [t.encode("utf-8") for t in texts]
+        data, offsets = batch_offsets(enc)
+        table = replacements if isinstance(replacements, ReplacementTable) else ReplacementTable(self, replacements)
+        out, off = StagedBatch(self, data, offsets).replace_bytes(table, opts)
+        return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
+
 
 class Prefiltered:
     """prefilter.rs:57-156"""
@@ -855,6 +868,94 @@ class StagedBatch:
             return out[: n.value * _native.REC_BYTES], doc_off
         return _native.take_records(ptr, n.value), doc_off
 
+    def replace_bytes(self, table: "ReplacementTable", opts: SearchOptions = None, out=None, offsets_out=None,
+                      stream=None, stats=None):
+        """fac_replace_batch: (bytes, offsets). Output document d is bytes[offsets[d]:offsets[d + 1]],
+        the crate's engine.replace(doc_d, opts, callback) with callback = the table's entry of the
+        match's pattern (options normalised as `segmented`, query.rs:46-64). `out`: a uint8 CUDA
+        tensor to leave the bytes in HBM: returns (the tensor's filled part, offsets);
+        FAC_E_OUTPUT_CAPACITY is raised as DeviceError with `.needed` bytes when it is too small
+        (nothing is written then). `offsets_out`: an int64 CUDA tensor of n_docs + 1 entries that also
+        receives the offsets, in HBM. `self.replaced` holds the number of records applied."""
+        import numpy as np
+        opts = opts or SearchOptions()
+        a = _native.fac_replace_args()
+        a.threshold = f32(opts.threshold_)
+        a.order = opts.order_.value
+        a.overlap = opts.overlap_.value
+        a.unique_ids = self.engine._unique_ids()
+        a.stream = stream or None
+        offsets = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        nrep = ctypes.c_uint64()
+        ptr = ctypes.POINTER(ctypes.c_uint8)()
+        if out is not None:
+            a.device_out = out.data_ptr()
+            a.device_cap = out.numel() * out.element_size()
+        if offsets_out is not None:
+            if offsets_out.numel() < self.n_docs + 1 or offsets_out.element_size() != 8:
+                raise ValueError("offsets_out needs n_docs + 1 64-bit entries")
+            a.device_out_offsets = offsets_out.data_ptr()
+        rc = _native.lib.fac_replace_batch(self.engine._h, self._h, table._h, ctypes.byref(a),
+                                           None if out is not None else ctypes.byref(ptr), ctypes.byref(n),
+                                           offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(nrep),
+                                           ctypes.byref(stats) if stats is not None else None)
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed = int(n.value)
+                raise
+        self.replaced = int(nrep.value)
+        if out is not None:
+            return out[: n.value], offsets
+        try:
+            return ctypes.string_at(ptr, n.value), offsets
+        finally:
+            _native.lib.fac_buffer_free(ptr)
+
+
+def replacement_table(replacements) -> Tuple[bytes, List[int], bytes]:
+    """(utf8, offsets, keep) of one replacement per pattern, the layout fac_replacements_create
+    takes: replacement p is utf8[offsets[p]:offsets[p + 1]]; `None` (keep the matched text) has
+    keep[p] == 1 and no bytes. `str` entries are encoded as UTF-8, `bytes` taken as they are (the
+    library validates them). Pure Python."""
+    parts, offsets, keep = [], [0], bytearray()
+    for r in replacements:
+        if r is None:
+            raw = b""
+        elif isinstance(r, str):
+            raw = r.encode("utf-8")
+        elif isinstance(r, (bytes, bytearray, memoryview)):
+            raw = bytes(r)
+        else:
+            raise TypeError(f"a replacement must be str, bytes or None, got {type(r).__name__}")
+        keep.append(1 if r is None else 0)
+        parts.append(raw)
+        offsets.append(offsets[-1] + len(raw))
+    return b"".join(parts), offsets, bytes(keep)
+
+
+class ReplacementTable:
+    """One replacement per pattern of `engine` (None = keep), validated and uploaded once
+    (fac_replacements_create); freed with the object."""
+
+    def __init__(self, engine: FuzzyAhoCorasick, replacements):
+        data, offsets, keep = replacement_table(replacements)
+        self.engine, self.n_patterns = engine, len(keep)
+        off = (ctypes.c_uint64 * len(offsets))(*offsets)
+        h = ctypes.c_void_p()
+        rc = _native.lib.fac_replacements_create(engine._h, data, off, keep, len(keep), ctypes.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _native.lib is not None:
+            _native.lib.fac_replacements_free(h)
+            self._h = None
+
 
 class FuzzyReplacer:
     """replacer.rs:9-52"""
@@ -865,6 +966,13 @@ class FuzzyReplacer:
 
     def replace(self, text: str, opts: SearchOptions) -> str:
         return self.engine.replace(text, opts, lambda m: self.replacements[m.pattern_index])
+
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        """`[self.replace(t, opts) for t in texts]` as one device pass (fac_replace_batch)."""
+        key = tuple(self.replacements)
+        if getattr(self, "_table", None) is None or self._table[0] != key:
+            self._table = (key, ReplacementTable(self.engine, self.replacements))
+        return self.engine.replace_batch(texts, opts, self._table[1])
 
     def replace_stream(self, reader, writer, threshold: float) -> int:
         """replacer.rs:35-44"""

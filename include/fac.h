@@ -327,7 +327,8 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  * start / end while it is inside the library; the tag is cleared before records leave it), and no
  * engine with multi-character mappings when some document is not ASCII. Auto-beam engines read the
  * segment descriptors back and run the per-segment auto-beam loop of fac_search_staged on the host.
- * Pre-filtered batches, batched replace / segment helpers and multi-GPU batches are not provided. */
+ * Batched replace is provided (fac_replace_batch below). Batched strip_*, split and segment_*,
+ * pre-filtered batches and multi-GPU batches are not. */
 typedef struct fac_batch fac_batch;
 
 /* Documents d = 0..n_docs-1 are bytes [offsets[d], offsets[d+1]) of utf8.
@@ -377,6 +378,55 @@ typedef struct fac_batch_args {
  * needed and nothing was written. */
 int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
                      uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats);
+
+/* ---- Batched replace: FuzzyReplacer::replace (replacer.rs:22-25, query.rs:46-96,
+ * matches.rs:165-188) of every document of a staged batch, spliced on the device.
+ *
+ * A replacement table gives each pattern its canonical form, or marks it "keep" (the callback's
+ * None, matches.rs:180-183: the matched text stays). It is the per-pattern table FuzzyReplacer
+ * uses (replacer.rs:24); a per-match callback cannot run on the device. Replacement p is bytes
+ * [offsets[p], offsets[p+1]) of utf8 (offsets[0] == 0, non-decreasing, empty = deletion), each
+ * valid UTF-8 on its own; keep: NULL, or one byte per pattern, non-zero = keep (its bytes are
+ * ignored). Validated and uploaded once. FAC_E_INVALID: n_patterns differs from the engine's, bad
+ * offsets or invalid UTF-8; FAC_E_UNSUPPORTED: 2^32 bytes of replacements or more. */
+typedef struct fac_replacements fac_replacements;
+int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
+                            const uint8_t* keep, uint64_t n_patterns, fac_replacements** out);
+void fac_replacements_free(fac_replacements* replacements);
+
+typedef struct fac_replace_args {
+  float threshold;
+  int32_t order;               /* as fac_matches_apply; 0 Unsorted is taken as 1 Default */
+  int32_t overlap;             /* as fac_matches_apply; 0 Keep is taken as 1 NonOverlapping */
+  const uint64_t* unique_ids;  /* as fac_batch_args */
+  void* stream;
+  void* device_out;            /* optional: the replaced bytes stay in HBM */
+  uint64_t device_cap;         /* bytes device_out holds */
+  uint64_t* device_out_offsets; /* optional: n_docs+1 entries on the device */
+} fac_replace_args;
+
+/* For every document d the result is engine.replace(doc_d, opts, callback) of the crate with
+ * callback(m) = the table's entry for m.pattern_index. The options are normalised as `segmented`
+ * does (query.rs:46-64; NonOverlappingUnique keeps its per-document used-pattern set), the batch is
+ * searched and ranked as fac_search_batch does, and each document's kept records are walked in the
+ * order fac_search_batch returns them -- by start, records of equal start in acceptance order --
+ * with the loop of matches.rs:170-187: last = 0; a record with start >= last emits
+ * doc[last..start], then its replacement (doc[start..end] for "keep"), and sets last = end; a
+ * record with start < last is skipped; doc[last..] ends the document. Two kept records can share a
+ * start (a span and the empty span at its start, or two empty spans, matches.rs:93-99); the crate
+ * leaves their order open (sort_unstable_by_key, matches.rs:111), here it is the acceptance order
+ * above. Offsets are byte offsets within the document, ASCII or not; the output is valid UTF-8.
+ *
+ * Output document d is bytes [out_offsets[d], out_offsets[d+1]) of the result; out_offsets is the
+ * caller's host array of n_docs+1 entries (may be NULL). The bytes go to the host (*out,
+ * fac_buffer_free) or, with device_out set, into that device buffer; *out_len is the byte count
+ * either way and *n_replaced (may be NULL) the number of records the splice applied.
+ * FAC_E_OUTPUT_CAPACITY: device_cap is too small, *out_len holds the bytes needed and nothing was
+ * written. Errors and limits as fac_search_batch, and FAC_E_INVALID for a table of another pattern
+ * count or device, FAC_E_UNSUPPORTED (never a partial result) for an output of 2^40 bytes or more. */
+int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
+                      const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                      uint64_t* n_replaced, fac_stats* stats);
 
 /* Streaming search (stream.rs:77-297): feed the input in the reader's read() pieces; windows
  * of `window_bytes` (0 = the crate's 256 KiB) are cut, searched (sorted + non-overlapping) and

@@ -12,6 +12,15 @@ every L bytes and searched three ways in one process, on device-resident bytes, 
   (c) the same bytes as ONE haystack through fac_search_staged: the boundary-free ceiling, a
       different result set, shown for scale only.
 
+With --replace the legs are instead (DESIGN.md §6a "Batched replace"; the table maps every
+pattern to its upper-cased form):
+
+  (r)  one fac_replace_batch call, bytes and offsets left in HBM, device events,
+  (a') fac_search_batch with the same normalised options (Default + NonOverlapping) on the same
+       batch: (r) - (a') is what the splice costs,
+  (b') the per-document loop replacer.replace(doc, opts) over the fixed sample, host wall clock,
+  and a hipMemcpyDtoDAsync of the output's size, the copy kernel's yardstick.
+
 Staging is reported in ms per GiB: the batch stager against fac_haystack_stage_device on the same
 bytes. One JSON line per configuration; "gate" is true when (a) beats (b) per document by more than
 (b)'s own spread and (a)'s records for the sample equal (b)'s.
@@ -30,7 +39,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(HERE), "fuzzy-aho-corasick-rs_am
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from fuzzy_aho_corasick import SearchOptions, StagedBatch, StagedHaystack, _native, workloads  # noqa: E402
+from fuzzy_aho_corasick import (FuzzyReplacer, Order, Overlap, ReplacementTable, SearchOptions, StagedBatch,  # noqa: E402
+                                StagedHaystack, _native, workloads)
 from fuzzy_aho_corasick.structs import f32  # noqa: E402
 
 
@@ -160,6 +170,90 @@ def run(name, nbytes, L, sample, rounds, rules, profile_only):
     return res
 
 
+def run_replace(name, nbytes, L, sample, rounds, profile_only):
+    w, engine = workload(name, nbytes)
+    data = w.haystack
+    off = cut_documents(data, L)
+    nd = len(off) - 1
+    dev = torch.device("cuda", engine.device)
+    t_data = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
+    t_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    sh = stream.cuda_stream
+    opts = SearchOptions().threshold(w.threshold)  # normalised by the replace: Default + NonOverlapping
+    opts.order_, opts.overlap_ = Order.Default, Overlap.NonOverlapping
+    reps = [(p if isinstance(p, str) else p.pattern).upper() for p in w.patterns]
+    table = ReplacementTable(engine, reps)
+    replacer = FuzzyReplacer(engine, reps)
+    bufs = {"rec": torch.empty(max(1 << 16, len(data) // 16) * 32, dtype=torch.uint8, device=dev),
+            "out": torch.empty(len(data) + (1 << 20), dtype=torch.uint8, device=dev)}
+    t_out_off = torch.empty(nd + 1, dtype=torch.int64, device=dev)
+    sb = StagedBatch.from_device(engine, t_data.data_ptr(), t_off.data_ptr(), nd, len(data), stream=sh)
+
+    def grown(key, unit, call):
+        while True:
+            try:
+                return call(bufs[key])
+            except Exception as ex:  # FAC_E_OUTPUT_CAPACITY: grow and run again
+                need = getattr(ex, "needed", 0)
+                if not need:
+                    raise
+                bufs[key] = torch.empty(int(need * 1.1 + 1024) * unit, dtype=torch.uint8, device=dev)
+
+    def replace():
+        return grown("out", 1, lambda o: sb.replace_bytes(table, opts, out=o, offsets_out=t_out_off, stream=sh))
+
+    def search():
+        return grown("rec", 32, lambda o: sb.search_records(opts, out=o, stream=sh))
+
+    for _ in range(2):  # warm-up: buffers, tables, the output sizes
+        replace()
+        search()
+    if profile_only:
+        for _ in range(3):
+            replace()
+        return None
+    idx = np.unique(np.linspace(0, nd - 1, min(sample, nd)).astype(np.int64))
+    docs = [data[int(off[d]):int(off[d + 1])].decode("utf-8") for d in idx]
+    for d in docs[:50]:
+        replacer.replace(d, opts)
+    r_ms, a_ms, b_ms = [], [], []
+    for _ in range(rounds):
+        ms, (out, out_off) = timed(stream, replace)
+        r_ms.append(ms)
+        a_ms.append(timed(stream, search)[0])
+        t0 = time.perf_counter()
+        per_doc = [replacer.replace(d, opts) for d in docs]
+        b_ms.append(1e3 * (time.perf_counter() - t0))
+    host = out.cpu().numpy().tobytes()
+    same = all(host[int(out_off[d]):int(out_off[d + 1])] == p.encode("utf-8") for d, p in zip(idx, per_doc))
+    # the yardstick: a device-to-device copy of the output's size
+    copy_ms = None
+    try:
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        dst = torch.empty(len(host), dtype=torch.uint8, device=dev)
+        hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+        rcs = []
+        cp = lambda: rcs.append(hip.hipMemcpyDtoDAsync(dst.data_ptr(), out.data_ptr(), len(host), sh))  # noqa: E731
+        cp()
+        copy_ms = [round(timed(stream, cp)[0], 4) for _ in range(rounds)]
+        if any(rcs) or not torch.equal(dst, out[:len(host)]):  # the copy did not run on this stream: no yardstick
+            copy_ms = None
+    except (OSError, AttributeError):
+        pass
+    b_doc = [m / len(docs) for m in b_ms]
+    r_doc = float(np.median(r_ms)) / nd
+    return {"leg": "replace", "config": name, "bytes": len(data), "L": L, "docs": nd, "sample": len(docs),
+            "out_bytes": len(host), "replaced": int(sb.replaced),
+            "r_ms": [round(x, 3) for x in r_ms], "a_ms": [round(x, 3) for x in a_ms],
+            "splice_ms": round(float(np.median(r_ms)) - float(np.median(a_ms)), 3),
+            "b_sample_ms": [round(x, 2) for x in b_ms], "dtod_copy_ms": copy_ms,
+            "r_us_per_doc": round(1e3 * r_doc, 4), "b_us_per_doc": [round(1e3 * x, 2) for x in b_doc],
+            "b_spread_us": round(1e3 * (max(b_doc) - min(b_doc)), 2), "r_over_b": round(r_doc / float(np.median(b_doc)), 6),
+            "bytes_equal": bool(same), "gate": bool(same and min(b_doc) - r_doc > max(b_doc) - min(b_doc))}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--c2-bytes", type=int, default=64 << 20)
@@ -172,9 +266,17 @@ def main():
                     help="prefix-cache rules to time for leg (a): windows per segment asked for")
     ap.add_argument("--profile-only", nargs="?", const="a", choices=["a", "c"], default=None,
                     help="a few calls of leg (a) (default) or (c) and nothing else (for rocprofv3)")
+    ap.add_argument("--replace", action="store_true",
+                    help="time fac_replace_batch against fac_search_batch and the per-document replace loop")
     args = ap.parse_args()
     for name in args.configs:
         for L in args.lengths:
+            if args.replace:
+                res = run_replace(name, args.c2_bytes if name == "c2" else args.c3_bytes, L, args.sample, args.rounds,
+                                  args.profile_only)
+                if res is not None:
+                    print(json.dumps(res), flush=True)
+                continue
             res = run(name, args.c2_bytes if name == "c2" else args.c3_bytes, L, args.sample, args.rounds, args.rules,
                       args.profile_only)
             if res is not None:
