@@ -981,6 +981,24 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
 
 // ---- batches (fac.h "Batches"): staging, search and per-document apply on the device
 
+// Whether a batch call takes the pre-filtered path, and if so every document's merged windows.
+// The reference falls back to the plain search when the engine has no filter or some pattern's
+// k_for exceeds 24 (prefilter.rs:151-155, 311-317): engine and threshold alone decide, so a fallback
+// call is the plain batch call for any batch. Where the filter runs, the batch must be all ASCII
+// (a non-ASCII document's symbol ids need the host's folded-string lookup, ensure_symbols).
+static int batch_prefilter(const fac::Engine& e, const fac::Batch& b, float threshold, bool prefilter, hipStream_t st,
+                           fac::BatchWindows& pw, bool& filtered, fac_stats* stats, std::string& err) {
+  filtered = false;
+  std::vector<uint32_t> ks;
+  if (!prefilter || !e.bitap_ok || !prefilter_ks(e, threshold, ks)) return FAC_OK;
+  if (!b.h.ascii) {
+    err = "pre-filtered batches need an all-ASCII batch (search the other documents one by one)";
+    return FAC_E_UNSUPPORTED;
+  }
+  filtered = true;
+  return fac::batch_prefilter_windows(e, b, ks, st, pw, stats, err);
+}
+
 static int batch_limits(uint64_t n_docs, uint64_t total_len) {
   if (n_docs > fac::kBatchMaxDocs || total_len >= (1ull << fac::kDocTagShift))
     return fail(FAC_E_UNSUPPORTED, "a batch holds at most 2^24 documents and fewer than 2^40 bytes");
@@ -1121,8 +1139,10 @@ uint64_t fac_batch_grapheme_starts(const fac_batch* batch, uint64_t d, uint64_t*
   return n;
 }
 
-int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
-                     uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats) {
+// The body of fac_search_batch and fac_search_batch_prefiltered (prefilter: take the pre-filtered
+// path where the reference's Prefiltered::search would, prefilter.rs:151-155, 311-317)
+static int search_batch_impl(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
+                             uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats, bool prefilter) {
   if (!engine || !batch || !args || !n_out || (!out && !args->device_out)) return fail(FAC_E_INVALID, "NULL argument");
   if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
     return fail(FAC_E_INVALID, "bad order/overlap");
@@ -1137,9 +1157,12 @@ int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac
   hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
   const uint64_t nd = b.n_docs;
   std::string err;
+  fac::BatchWindows pw;  // pre-filtered: every document's merged windows, found once
+  bool filtered = false;
+  if (int rc = batch_prefilter(e, b, args->threshold, prefilter, st, pw, filtered, stats, err)) return fail(rc, err);
   // raw tagged records into a device buffer (grown and searched again if it was too small), then
   // the per-document apply; nothing but counts visits the host
-  uint64_t cap = std::max<uint64_t>(4096, b.windows / 64);
+  uint64_t cap = std::max<uint64_t>(4096, (filtered ? pw.windows : b.windows) / 64);
   for (;;) {
     DevMem raw(st), doff(st);
     if (int rc = raw.alloc(2 * cap * sizeof(fac_match), err)) return fail(rc, err);
@@ -1147,7 +1170,9 @@ int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac
     fac::MatchSink sink;
     sink.dev = static_cast<fac_match*>(raw.p);
     sink.dev_cap = cap;
-    if (int rc = fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err)) return fail(rc, err);
+    if (int rc = filtered ? fac::launch_search_batch_windows(e, b, pw, args->threshold, st, sink, stats, err)
+                          : fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err))
+      return fail(rc, err);
     if (stats) stats->graphemes = b.windows;
     if (sink.n > cap) {
       cap = sink.n;
@@ -1177,6 +1202,45 @@ int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac
     if (fin.dev) return FAC_OK;
     return hand_out(fin, out, n_out);
   }
+}
+
+int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
+                     uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats) {
+  return search_batch_impl(engine, batch, args, out, n_out, doc_offsets, stats, false);
+}
+
+int fac_search_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args,
+                                 fac_match** out, uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats) {
+  return search_batch_impl(engine, batch, args, out, n_out, doc_offsets, stats, true);
+}
+
+int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* batch, float threshold, void* stream,
+                                    uint64_t* out, uint64_t cap) {
+  if (!engine || !batch || (cap && !out)) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  if (b.h.device != e.device) return -(int64_t)fail(FAC_E_INVALID, "batch was staged for another device");
+  if (hipSetDevice(e.device) != hipSuccess) return -(int64_t)fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e.stream;
+  std::string err;
+  fac::BatchWindows pw;
+  bool filtered = false;
+  if (int rc = batch_prefilter(e, b, threshold, true, st, pw, filtered, nullptr, err)) return -(int64_t)fail(rc, err);
+  if (!filtered) return -1;
+  // (diagnostics: the descriptors and the offsets come back to the host)
+  std::vector<fac::SegDesc> segs(pw.n);
+  std::vector<uint64_t> off(b.n_docs + 1, 0);
+  if ((pw.n && hipMemcpyAsync(segs.data(), pw.d_segs, pw.n * sizeof(fac::SegDesc), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (b.n_docs && hipMemcpyAsync(off.data(), b.d_offsets, (b.n_docs + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return -(int64_t)fail(FAC_E_HIP, "copy of the batch's merged windows failed");
+  for (uint64_t i = 0; i < pw.n && i < cap; ++i) {
+    const uint64_t d = segs[i].byte_base >> fac::kDocTagShift, s0 = segs[i].text_base - off[d];
+    out[3 * i] = d;
+    out[3 * i + 1] = s0;
+    out[3 * i + 2] = s0 + segs[i].n;
+  }
+  return (int64_t)pw.n;
 }
 
 // ---- batched replace (fac.h "Batched replace"): the table, then search + apply + splice
@@ -1231,9 +1295,10 @@ void fac_replacements_free(fac_replacements* replacements) {
   delete replacements;
 }
 
-int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
-                      const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
-                      uint64_t* n_replaced, fac_stats* stats) {
+// The body of fac_replace_batch and fac_replace_batch_prefiltered (prefilter: as search_batch_impl)
+static int replace_batch_impl(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
+                              const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                              uint64_t* n_replaced, fac_stats* stats, bool prefilter) {
   if (!engine || !batch || !replacements || !args || !out_len || (!out && !args->device_out))
     return fail(FAC_E_INVALID, "NULL argument");
   if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
@@ -1255,8 +1320,11 @@ int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fa
   const int order = args->order == 0 ? 1 : args->order, overlap = args->overlap == 0 ? 1 : args->overlap;
   const uint64_t nd = b.n_docs;
   std::string err;
+  fac::BatchWindows pw;
+  bool filtered = false;
+  if (int rc = batch_prefilter(e, b, args->threshold, prefilter, st, pw, filtered, stats, err)) return fail(rc, err);
   // fac_search_batch's search and per-document apply, then the splice from the kept records in HBM
-  uint64_t cap = std::max<uint64_t>(4096, b.windows / 64);
+  uint64_t cap = std::max<uint64_t>(4096, (filtered ? pw.windows : b.windows) / 64);
   for (;;) {
     DevMem raw(st), doff(st), obuf(st);
     if (int rc = raw.alloc(2 * cap * sizeof(fac_match), err)) return fail(rc, err);
@@ -1264,7 +1332,9 @@ int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fa
     fac::MatchSink sink;
     sink.dev = static_cast<fac_match*>(raw.p);
     sink.dev_cap = cap;
-    if (int rc = fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err)) return fail(rc, err);
+    if (int rc = filtered ? fac::launch_search_batch_windows(e, b, pw, args->threshold, st, sink, stats, err)
+                          : fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err))
+      return fail(rc, err);
     if (stats) stats->graphemes = b.windows;
     if (sink.n > cap) {
       cap = sink.n;
@@ -1306,6 +1376,18 @@ int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fa
     if (host) *out = host;
     return FAC_OK;
   }
+}
+
+int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
+                      const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                      uint64_t* n_replaced, fac_stats* stats) {
+  return replace_batch_impl(engine, batch, replacements, args, out, out_len, out_offsets, n_replaced, stats, false);
+}
+
+int fac_replace_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
+                                  const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                                  uint64_t* n_replaced, fac_stats* stats) {
+  return replace_batch_impl(engine, batch, replacements, args, out, out_len, out_offsets, n_replaced, stats, true);
 }
 
 int fac_stream_open(const fac_engine* engine, float threshold, uint64_t window_bytes, fac_stream** out) {

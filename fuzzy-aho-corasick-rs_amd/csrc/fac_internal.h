@@ -486,7 +486,16 @@ struct Batch {
   uint64_t n_segs = 0;   // non-empty documents
   uint64_t windows = 0;  // start windows of all documents
   uint64_t err_doc = 0, err_graphemes = 0;  // of a failed staging
+  // the pre-filter's document-start bitmap (search_kernels.hip batch_prefilter_windows): one
+  // bit per byte of h.d_utf8, set at the first byte of every non-empty document; built by the first
+  // pre-filtered search after a staging and kept until the batch is staged again
+  mutable std::mutex dstart_mu;
+  mutable uint32_t* d_dstart = nullptr;
+  mutable uint64_t dstart_cap = 0;  // words d_dstart holds
+  mutable bool dstart_ready = false;
 };
+// stage_kernels.hip: d_out[i] = d_in[0] + ... + d_in[i - 1] for i < n, on st (asynchronous)
+int exclusive_sum_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n, hipStream_t st, std::string& err);
 // stage_kernels.hip: stages the documents [d_offsets[d], d_offsets[d + 1]) of b.h.d_utf8 (b.h.len
 // bytes, b.n_docs, b.d_offsets set by the caller) on st; synchronous
 int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& err);
@@ -571,6 +580,28 @@ int launch_search_sink(const Engine& e, const Haystack& h, const std::vector<Seg
 // The prefix cache is gated by the batch's own rule, not by windows per segment.
 int launch_search_batch(const Engine& e, const Batch& b, float thr, hipStream_t stream, MatchSink& sink,
                         fac_stats* stats, std::string& err);
+// Prefiltered::raw of every document of an all-ASCII batch (prefilter.rs:304-374 per document; ks:
+// prefilter_ks' edit budgets): one bitap pass over the concatenated bytes with the automaton reset
+// and the coverage cut at every document start (batch_prefilter_windows), then each merged window
+// searched as a haystack of its own, one segment of one launch_pass (launch_search_batch_windows).
+// The descriptors and their window prefix are written by the device, ascending by start (so by
+// document); the host reads back the two totals. The records come out tagged with their document
+// like launch_search_batch's. Scratch comes from the stream's pool and goes back with the struct.
+struct BatchWindows {
+  hipStream_t s = nullptr;
+  SegDesc* d_segs = nullptr;    // n descriptors: ascii, text_base = global byte, byte_base tagged
+  uint64_t* d_prefix = nullptr;  // n + 1 entries
+  uint64_t n = 0;        // merged windows of all documents
+  uint64_t windows = 0;  // their lengths summed: the start windows to search
+  ~BatchWindows() {
+    if (d_segs) call_scratch_give(d_segs, s);
+    if (d_prefix) call_scratch_give(d_prefix, s);
+  }
+};
+int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<uint32_t>& ks, hipStream_t stream,
+                            BatchWindows& out, fac_stats* stats, std::string& err);
+int launch_search_batch_windows(const Engine& e, const Batch& b, const BatchWindows& w, float thr, hipStream_t stream,
+                                MatchSink& sink, fac_stats* stats, std::string& err);
 // auto-beam pass 1 alone: sum of queue.len() over the windows of `segs` searched unbeamed
 int auto_beam_total(const Engine& e, const Haystack& h, const std::vector<SegDesc>& segs, float thr,
                     hipStream_t stream, uint64_t& total, std::string& err);

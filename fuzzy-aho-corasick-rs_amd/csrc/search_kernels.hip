@@ -4054,7 +4054,37 @@ struct BitapParams {
   uint32_t n_words;
   uint32_t seg_len;        // text positions owned by one wave
   uint32_t* cover;         // coverage bitmap, 1 bit per grapheme
+  const uint32_t* dstart;  // DOCS: 1 bit per text position, set where a document of a batch starts
 };
+
+// The document-start bitmap of a batch (one bit per byte of the concatenated text, set at the first
+// byte of every non-empty document; (n + 31) / 32 words). Documents are disjoint, so these two
+// lookups are all the pre-filter needs to keep automaton state and coverage inside a document.
+// The last document start in [lo, hi] (hi < n), or lo if there is none.
+__device__ __forceinline__ uint64_t doc_start_back(const uint32_t* __restrict__ ds, uint64_t lo, uint64_t hi) {
+  for (uint64_t w = hi >> 5;; --w) {
+    uint32_t v = ds[w];
+    if (w == (hi >> 5)) v &= 0xFFFFFFFFu >> (31u - (uint32_t)(hi & 31));
+    if (w == (lo >> 5)) v &= 0xFFFFFFFFu << (uint32_t)(lo & 31);
+    if (v) return w * 32 + (31u - (uint32_t)__builtin_clz(v));
+    if (w == (lo >> 5)) return lo;
+  }
+}
+// (a call: inlined into bitap_kernel's unrolled hit loop it doubled the scan's registers)
+__device__ __attribute__((noinline)) uint64_t doc_start_back_call(const uint32_t* __restrict__ ds, uint64_t lo, uint64_t hi) {
+  return doc_start_back(ds, lo, hi);
+}
+// The first document start in [lo, hi) (hi <= n), or hi if there is none.
+__device__ __forceinline__ uint64_t doc_start_fwd(const uint32_t* __restrict__ ds, uint64_t lo, uint64_t hi) {
+  if (lo >= hi) return hi;
+  const uint64_t wl = (hi - 1) >> 5;
+  for (uint64_t w = lo >> 5; w <= wl; ++w) {
+    uint32_t v = ds[w];
+    if (w == (lo >> 5)) v &= 0xFFFFFFFFu << (uint32_t)(lo & 31);
+    if (v) return min(hi, w * 32 + (uint32_t)__builtin_ctz(v));
+  }
+  return hi;
+}
 
 // Shift-AND over several patterns per automaton word: the patterns of one edit budget are packed
 // side by side (pattern f in bits lo_f..top_f). Every recurrence of bitap_windows
@@ -4068,6 +4098,30 @@ __device__ __forceinline__ W low_bits(uint32_t n) {
   return n >= sizeof(W) * 8 ? ~(W)0 : (((W)1 << n) - (W)1);
 }
 
+// bitap_kernel<.., DOCS>'s rolled loop: the coverage [end - span, end) of every hit of the symbol at i,
+// clipped to the start of the document holding it (as the scan's own hit loop)
+template <typename W>
+__device__ __attribute__((noinline)) void bitap_cover_docs(const uint32_t* __restrict__ dstart, uint32_t* __restrict__ cover, W hits, W top,
+                                                           uint32_t k, uint64_t i) {
+  const uint64_t end = i + 1;
+  do {
+    const uint32_t hi = (uint32_t)__builtin_ctzll((unsigned long long)hits);
+    hits &= hits - 1;
+    const W below = top & low_bits<W>(hi);
+    const uint32_t lo = below ? 64u - (uint32_t)__builtin_clzll((unsigned long long)below) : 0u;
+    const uint64_t span = (uint64_t)(hi + 1 - lo) + k;
+    const uint64_t ws = doc_start_back(dstart, end > span ? end - span : 0, i);
+    for (uint64_t x = ws; x < end;) {
+      const uint64_t w = x >> 5;
+      const uint32_t l = (uint32_t)(x & 31);
+      const uint32_t cnt = (uint32_t)min((uint64_t)(32 - l), end - x);
+      const uint32_t bits = (cnt == 32 ? 0xFFFFFFFFu : ((1u << cnt) - 1u)) << l;
+      atomicOr(cover + w, bits);
+      x += cnt;
+    }
+  } while (hits);
+}
+
 // Each lane runs one packed word over the wave's text segment. The state after `m + k` symbols no
 // longer depends on the initial state, so a segment starts `m + k` symbols early from the
 // reference's initial state and only reports ends inside its own range. Every hit of pattern f
@@ -4075,7 +4129,12 @@ __device__ __forceinline__ W low_bits(uint32_t n) {
 // merged windows of prefilter.rs:334-342.
 // W: the automaton word (uint32_t when every pattern has m <= 32: half the VALU work of uint64_t);
 // KMAX: the largest edit budget (levels above a word's own k are computed but never read).
-template <int KMAX, typename W>
+// DOCS: the text is a batch of documents (B.dstart). Every lane of a wave steps the same position, so
+// "this symbol starts a document" is wave-uniform: the state goes back to the initial one there
+// (a document's automaton starts at its first symbol, prefilter.rs:415-418), which also makes the
+// warm-up exact from the last document start inside it, and a hit's coverage is clipped to its
+// document's start instead of the text's.
+template <int KMAX, typename W, bool DOCS = false>
 __global__ __launch_bounds__(256) void bitap_kernel(BitapParams B) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -4111,17 +4170,63 @@ __global__ __launch_bounds__(256) void bitap_kernel(BitapParams B) {
   // Symbols come in 64 at a time (lane l loads symbol i0 + l, broadcast by readlane) and each lane
   // issues the masks of 8 symbols before stepping through them, so the loop waits on one memory
   // round trip per 8 symbols instead of two per symbol.
-  constexpr uint32_t U = 8;
+  // (DOCS with 64-bit words and 24 levels: 4, which keeps the second loop's registers out of scratch)
+  constexpr uint32_t U = (DOCS && sizeof(W) == 8 && KMAX > 16) ? 4 : 8;
   const W* mask_p = static_cast<const W*>(B.mask_t) + (live ? p : 0u);  // this lane's column
   for (uint64_t i0 = s0; i0 < b; i0 += 64) {
     const uint32_t cl = i0 + lane < b ? (uint32_t)B.ids[i0 + lane] : 0u;
     const uint32_t nsym = (uint32_t)min((uint64_t)64, b - i0);
+    uint64_t dmask = 0;  // DOCS: bit u = position i0 + u starts a document (wave-uniform)
+    if constexpr (DOCS) {
+      const uint64_t w0 = i0 >> 5, nwd = (B.n + 31) >> 5;
+      const uint32_t sh = (uint32_t)(i0 & 31);
+      const uint64_t lo = (uint64_t)B.dstart[w0] | ((w0 + 1 < nwd ? (uint64_t)B.dstart[w0 + 1] : 0ull) << 32);
+      const uint64_t hi = (sh && w0 + 2 < nwd) ? (uint64_t)B.dstart[w0 + 2] : 0ull;
+      dmask = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+      dmask = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)dmask) |
+              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(dmask >> 32)) << 32);
+    }
     for (uint32_t u0 = 0; u0 < nsym; u0 += U) {
       W bcs[U];
 #pragma unroll
       for (uint32_t q = 0; q < U; ++q) {
         const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cl, (int)(u0 + q));  // u0 + q < 64: wave-uniform
         bcs[q] = (live && u0 + q < nsym) ? mask_p[(size_t)c * B.n_words] : (W)0;
+      }
+      if constexpr (DOCS) {
+        // A document starts among these U symbols (wave-uniform): they are stepped one by one in a
+        // rolled loop (the masks rotate through bcs[0], so nothing is indexed by the loop counter),
+        // the state going back to the initial one -- level d holds the low min(d, m) bits of every
+        // field -- before the document's first symbol. Every other group takes the loop below as it is.
+        if ((dmask >> u0) & ((1ull << U) - 1ull)) {
+#pragma unroll 1
+          for (uint32_t q = 0; q < U && u0 + q < nsym; ++q) {
+            if ((dmask >> (u0 + q)) & 1ull) {  // (bits above the last field are never read, as in the steps)
+              r[0] = (W)0;
+#pragma unroll
+              for (int d = 1; d <= KMAX; ++d) r[d] = d == 1 ? first : (W)(r[d - 1] | ((W)(r[d - 1] << 1) & ~first));
+            }
+            const W bc = bcs[0];
+#pragma unroll
+            for (uint32_t x = 0; x + 1 < U; ++x) bcs[x] = bcs[x + 1];
+            W prev_old = r[0];
+            W prev_new = ((r[0] << 1) | first) & bc;
+            r[0] = prev_new;
+            W hit_level = (k == 0) ? prev_new : (W)0;
+#pragma unroll
+            for (int d = 1; d <= KMAX; ++d) {
+              const W old = r[d];
+              const W nv = ((old << 1) & bc) | ((prev_old | prev_new) << 1) | prev_old | first;
+              r[d] = nv;
+              prev_old = old;
+              prev_new = nv;
+              if ((uint32_t)d == k) hit_level = nv;
+            }
+            const W hits = hit_level & top;
+            if (live && hits && i0 + u0 + q >= a) bitap_cover_docs<W>(B.dstart, B.cover, hits, top, k, i0 + u0 + q);
+          }
+          continue;
+        }
       }
       // the hits of the 8 symbols are kept and only looked at when one of them is set (rare): the
       // per-symbol path carries no segment-range compare and no divergent branch
@@ -4163,7 +4268,8 @@ __global__ __launch_bounds__(256) void bitap_kernel(BitapParams B) {
             const W below = top & low_bits<W>(hi);  // tops of the fields under this one
             const uint32_t lo = below ? 64u - (uint32_t)__builtin_clzll((unsigned long long)below) : 0u;
             const uint64_t span = (uint64_t)(hi + 1 - lo) + k;
-            const uint64_t ws = end > span ? end - span : 0;
+            uint64_t ws = end > span ? end - span : 0;
+            if constexpr (DOCS) ws = doc_start_back_call(B.dstart, ws, i);  // the document holding the end
             for (uint64_t x = ws; x < end;) {  // set bits [ws, end)
               const uint64_t w = x >> 5;
               const uint32_t l = (uint32_t)(x & 31);
@@ -4232,6 +4338,8 @@ struct QgramParams {
   // wsh != 0: window w is [w << wsh, min(n, (w + 1) << wsh) + wov)) -- the crate's fixed-size cut,
   // bounds computed instead of loaded
   uint32_t wsh, wov;
+  // a batch of documents (qgram_verify_docs_kernel): the document-start bitmap, (n + 31) / 32 words
+  const uint32_t* dstart;
 };
 constexpr uint32_t QG_WSH = 16;  // window-table buckets of 64 Ki positions
 __host__ __device__ inline uint32_t qgram_key(uint32_t a, uint32_t b, uint32_t c, uint32_t d, bool q4) {
@@ -4665,6 +4773,106 @@ __global__ __launch_bounds__(LM ? 512 : 256) void qgram_verify_kernel(QgramParam
       }
     }
   }
+}
+
+// The verify of a batch of documents (Q.dstart, the document-start bitmap): a candidate is verified
+// once, for the document holding its gram position t. Only the part of that document the candidate
+// can reach matters -- the recurrence starts at most m + 2k + 1 <= 112 symbols before t and ends at
+// most m + k <= 87 after it -- so its bounds are the document starts found within 128 positions
+// before t and 96 after it (none found: the range's own end, which verify_one then never reaches).
+// A gram that straddles a boundary is a harmless extra candidate of the document it starts in.
+template <int KMAX, typename W, bool LM>
+__global__ __launch_bounds__(LM ? 512 : 256) void qgram_verify_docs_kernel(QgramParams Q) {
+  __shared__ uint8_t s_aid[128];  // bytes mode: byte -> symbol id
+  extern __shared__ uint16_t s_m16[];  // LM: Q.m16_words 32-bit words of 16-bit masks
+  if (Q.bytes)
+    for (uint32_t i = threadIdx.x; i < 128; i += blockDim.x) s_aid[i] = Q.aid[i];
+  if constexpr (LM)
+    for (uint32_t i = threadIdx.x; i < Q.m16_words; i += blockDim.x) reinterpret_cast<uint32_t*>(s_m16)[i] = Q.m16[i];
+  __syncthreads();
+  for (uint32_t r = blockIdx.x; r <= Q.nreg; r += gridDim.x) {  // regions as qgram_verify_kernel
+    const unsigned long long* base = r < Q.nreg ? Q.cand + (uint64_t)r * Q.region : Q.ovf;
+    const uint64_t cnt = r < Q.nreg ? (uint64_t)Q.rcnt[r] : min((uint64_t)*Q.n_ovf, Q.ovf_cap);
+    for (uint64_t x = threadIdx.x; x < cnt; x += blockDim.x) {
+      const unsigned long long cd = base[x];
+      const uint64_t t = cd >> 24;
+      if (t >= Q.n) continue;
+      const uint64_t lo = doc_start_back(Q.dstart, t > 128 ? t - 128 : 0, t);
+      const uint64_t hi = doc_start_fwd(Q.dstart, t + 1, min(Q.n, t + 96));
+      verify_one<KMAX, W, LM>(Q, cd, Q.ent[cd & 0xFFFFFFu], s_aid, s_m16, lo, hi, Q.cover);
+    }
+  }
+}
+
+// Runs of a batch's coverage bitmap, cut at document starts (two documents' coverage can touch:
+// "...hello" | "hello..."): a run starts at a set bit whose predecessor is clear or which starts a
+// document, and ends at the first clear bit or the next document start. Counted per bitmap word,
+// scanned, then written in place (runs_docs_write_kernel), so the runs come out sorted by start with
+// no list to overflow and no sort.
+__device__ __forceinline__ uint32_t run_starts(const uint32_t* __restrict__ cover, const uint32_t* __restrict__ ds,
+                                               uint64_t w, uint64_t n) {
+  const uint32_t cur = cover[w];
+  const uint32_t prev_hi = w > 0 ? (cover[w - 1] >> 31) : 0u;
+  uint32_t starts = cur & (~((cur << 1) | prev_hi) | ds[w]);
+  if (n - w * 32 < 32) starts &= (1u << (uint32_t)(n - w * 32)) - 1u;  // (the bitmap's last word)
+  return starts;
+}
+__global__ void runs_docs_count_kernel(const uint32_t* __restrict__ cover, const uint32_t* __restrict__ ds,
+                                       uint64_t n_words, uint64_t n, uint64_t* __restrict__ cnt) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w > n_words) return;
+  cnt[w] = w < n_words ? (uint64_t)__popc(run_starts(cover, ds, w, n)) : 0ull;  // (entry n_words: the scan's total)
+}
+// One SegDesc per run (a merged window searched as a haystack of its own, prefilter.rs:346-350,
+// tagged with its document like batch_desc_kernel's) and its length for the window prefix.
+__global__ void runs_docs_write_kernel(const uint32_t* __restrict__ cover, const uint32_t* __restrict__ ds,
+                                       uint64_t n_words, uint64_t n, const uint64_t* __restrict__ pos,
+                                       const uint64_t* __restrict__ off, uint64_t n_docs, SegDesc* __restrict__ segs,
+                                       uint64_t* __restrict__ lens) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n_words) return;
+  uint32_t starts = run_starts(cover, ds, w, n);
+  uint64_t idx = pos[w];
+  while (starts) {
+    const uint32_t b = __ffs(starts) - 1;
+    starts &= starts - 1;
+    const uint64_t s = w * 32 + b;
+    uint64_t e = n;  // the first clear bit or document start after s
+    for (uint64_t ww = w; ww < n_words; ++ww) {
+      uint32_t stop = ~cover[ww] | ds[ww];
+      if (ww == w) stop &= b == 31 ? 0u : (0xFFFFFFFFu << (b + 1));
+      if (stop) {
+        e = min(n, ww * 32 + (uint64_t)__builtin_ctz(stop));
+        break;
+      }
+    }
+    uint64_t lo = 0, hi = n_docs;  // the last document with off[d] <= s: the non-empty one holding s
+    while (hi - lo > 1) {
+      const uint64_t mid = (lo + hi) / 2;
+      if (off[mid] <= s) lo = mid;
+      else hi = mid;
+    }
+    SegDesc S;
+    S.text_base = s;
+    S.n = e - s;
+    S.avail = S.n;
+    S.hay_len = S.n;
+    S.byte_base = s | (lo << kDocTagShift);
+    S.w_begin = 0;
+    S.w_end = S.n;
+    S.ascii = 1u;
+    S.pad = 0;
+    segs[idx] = S;
+    lens[idx] = S.n;
+    ++idx;
+  }
+}
+// The document-start bitmap: one thread per document, one bit per non-empty document
+__global__ void doc_starts_kernel(const uint64_t* __restrict__ off, uint64_t n_docs, uint32_t* __restrict__ ds) {
+  const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= n_docs) return;
+  const uint64_t a = off[d];
+  if (off[d + 1] > a) atomicOr(ds + (a >> 5), 1u << (uint32_t)(a & 31));
 }
 
 // Maximal runs of set bits -> [start, end) windows (unordered; the host sorts them).
@@ -6540,29 +6748,166 @@ int pf_tables(const Engine& e, const std::vector<uint32_t>& ks, bool want_bytes,
 
 // qgram_verify_kernel for the tables' edit budget and mask layout: LDS masks in persistent blocks (two
 // per CU), else global masks, 32- or 64-bit automaton words
-template <bool WIN>
+// MODE 0: one text; 1: a batch of stream windows; 2: a batch of documents (qgram_verify_docs_kernel)
+template <int KMAX, typename W, bool LM, int MODE>
+constexpr auto qverify_fn() {
+  if constexpr (MODE == 2) return &qgram_verify_docs_kernel<KMAX, W, LM>;
+  else return &qgram_verify_kernel<KMAX, W, LM, MODE == 1>;
+}
+template <int MODE>
 void launch_qverify(const PfTables& T, const QgramParams& Q, dim3 vg, hipStream_t stream) {
   const uint32_t kq = T.kq;
-  if (T.m16) {
+  // (MODE 2 with more than 8 levels reads its masks from global memory: 24 levels under the LDS
+  // variant's 512-thread bound spill to scratch, and no kernel of the batch path may)
+  if (T.m16 && (MODE != 2 || kq <= 8)) {
     const size_t lds = (size_t)T.m16_words * 4;
-    if (kq <= 1) hipLaunchKernelGGL((qgram_verify_kernel<1, uint32_t, true, WIN>), vg, dim3(512), lds, stream, Q);
-    else if (kq <= 2) hipLaunchKernelGGL((qgram_verify_kernel<2, uint32_t, true, WIN>), vg, dim3(512), lds, stream, Q);
-    else if (kq <= 4) hipLaunchKernelGGL((qgram_verify_kernel<4, uint32_t, true, WIN>), vg, dim3(512), lds, stream, Q);
-    else if (kq <= 8) hipLaunchKernelGGL((qgram_verify_kernel<8, uint32_t, true, WIN>), vg, dim3(512), lds, stream, Q);
-    else hipLaunchKernelGGL((qgram_verify_kernel<24, uint32_t, true, WIN>), vg, dim3(512), lds, stream, Q);
+    if (kq <= 1) hipLaunchKernelGGL((qverify_fn<1, uint32_t, true, MODE>()), vg, dim3(512), lds, stream, Q);
+    else if (kq <= 2) hipLaunchKernelGGL((qverify_fn<2, uint32_t, true, MODE>()), vg, dim3(512), lds, stream, Q);
+    else if (kq <= 4) hipLaunchKernelGGL((qverify_fn<4, uint32_t, true, MODE>()), vg, dim3(512), lds, stream, Q);
+    else if (kq <= 8) hipLaunchKernelGGL((qverify_fn<8, uint32_t, true, MODE>()), vg, dim3(512), lds, stream, Q);
+    else if constexpr (MODE != 2) hipLaunchKernelGGL((qverify_fn<24, uint32_t, true, MODE>()), vg, dim3(512), lds, stream, Q);
   } else if (T.mq <= 32) {
-    if (kq <= 1) hipLaunchKernelGGL((qgram_verify_kernel<1, uint32_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else if (kq <= 2) hipLaunchKernelGGL((qgram_verify_kernel<2, uint32_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else if (kq <= 4) hipLaunchKernelGGL((qgram_verify_kernel<4, uint32_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else if (kq <= 8) hipLaunchKernelGGL((qgram_verify_kernel<8, uint32_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else hipLaunchKernelGGL((qgram_verify_kernel<24, uint32_t, false, WIN>), vg, dim3(256), 0, stream, Q);
+    if (kq <= 1) hipLaunchKernelGGL((qverify_fn<1, uint32_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else if (kq <= 2) hipLaunchKernelGGL((qverify_fn<2, uint32_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else if (kq <= 4) hipLaunchKernelGGL((qverify_fn<4, uint32_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else if (kq <= 8) hipLaunchKernelGGL((qverify_fn<8, uint32_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else hipLaunchKernelGGL((qverify_fn<24, uint32_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
   } else {
-    if (kq <= 1) hipLaunchKernelGGL((qgram_verify_kernel<1, uint64_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else if (kq <= 2) hipLaunchKernelGGL((qgram_verify_kernel<2, uint64_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else if (kq <= 4) hipLaunchKernelGGL((qgram_verify_kernel<4, uint64_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else if (kq <= 8) hipLaunchKernelGGL((qgram_verify_kernel<8, uint64_t, false, WIN>), vg, dim3(256), 0, stream, Q);
-    else hipLaunchKernelGGL((qgram_verify_kernel<24, uint64_t, false, WIN>), vg, dim3(256), 0, stream, Q);
+    if (kq <= 1) hipLaunchKernelGGL((qverify_fn<1, uint64_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else if (kq <= 2) hipLaunchKernelGGL((qverify_fn<2, uint64_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else if (kq <= 4) hipLaunchKernelGGL((qverify_fn<4, uint64_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else if (kq <= 8) hipLaunchKernelGGL((qverify_fn<8, uint64_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
+    else hipLaunchKernelGGL((qverify_fn<24, uint64_t, false, MODE>()), vg, dim3(256), 0, stream, Q);
   }
+}
+
+// bitap_kernel for the tables' word size and largest edit budget
+template <bool DOCS>
+void launch_bitap(const PfTables& T, const BitapParams& B, dim3 bgrid, hipStream_t stream) {
+  const uint32_t kmax = T.kmax;
+  if (T.w32) {
+    if (kmax == 0) hipLaunchKernelGGL((bitap_kernel<0, uint32_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax == 1) hipLaunchKernelGGL((bitap_kernel<1, uint32_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax == 2) hipLaunchKernelGGL((bitap_kernel<2, uint32_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax <= 4) hipLaunchKernelGGL((bitap_kernel<4, uint32_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax <= 8) hipLaunchKernelGGL((bitap_kernel<8, uint32_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax <= 16) hipLaunchKernelGGL((bitap_kernel<16, uint32_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else hipLaunchKernelGGL((bitap_kernel<24, uint32_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+  } else {
+    if (kmax <= 1) hipLaunchKernelGGL((bitap_kernel<1, uint64_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax <= 2) hipLaunchKernelGGL((bitap_kernel<2, uint64_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax <= 4) hipLaunchKernelGGL((bitap_kernel<4, uint64_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax <= 8) hipLaunchKernelGGL((bitap_kernel<8, uint64_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else if (kmax <= 16) hipLaunchKernelGGL((bitap_kernel<16, uint64_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+    else hipLaunchKernelGGL((bitap_kernel<24, uint64_t, DOCS>), bgrid, dim3(256), 0, stream, B);
+  }
+}
+
+// The q-gram path's parameters for a text of n symbols: the tables, the text buffer (the ids at d_ids,
+// or with T.bytes the staged bytes from vb read in place) and the coverage bitmap
+QgramParams qgram_params(const Engine& e, const Haystack& h, const PfTables& T, const uint8_t* vb, const void* d_ids,
+                         uint64_t n, void* d_cover) {
+  QgramParams Q{};
+  Q.ids = static_cast<const uint8_t*>(d_ids);
+  Q.n = n;
+  Q.nsafe = n + 80;
+  if (T.bytes) {
+    Q.ids = reinterpret_cast<const uint8_t*>((uintptr_t)vb & ~(uintptr_t)15);
+    Q.off = (uint32_t)(vb - Q.ids);
+    Q.nsafe = (uint64_t)(h.d_utf8 + h.len - Q.ids);
+    Q.bytes = 1;
+    Q.ci = e.case_insensitive ? 1u : 0u;
+    Q.aid = e.d_ascii_id;
+  }
+  Q.tab = static_cast<const uint2*>(T.tab);
+  Q.tab_mask = T.ts - 1;
+  Q.ent = static_cast<const uint2*>(T.ent);
+  Q.use3 = T.use3;
+  Q.use4 = T.use4;
+  Q.use5 = T.use5;
+  Q.pmask = static_cast<const uint64_t*>(T.qmask);
+  Q.pm = static_cast<const uint32_t*>(T.qpm);
+  Q.rows = e.alphabet + 1;
+  Q.cover = static_cast<uint32_t*>(d_cover);
+  Q.bits = static_cast<const uint32_t*>(T.qbits);
+  Q.m16 = static_cast<const uint32_t*>(T.m16);
+  Q.m16_words = T.m16_words;
+  return Q;
+}
+
+// qgram_scan_kernel over the text: fills Q's candidate lists (held by b), scanning again with room for
+// all of them if the overflow list overflowed. vg: the verify's grid; nc: the overflow entries.
+struct QgramBufs {
+  PoolBuf cand, n, ovf, rcnt;
+};
+int qgram_candidates(const Engine& e, const PfTables& T, QgramParams& Q, uint64_t n, hipStream_t stream, QgramBufs& b,
+                     dim3& vg, unsigned long long& nc, std::string& err) {
+  HIP_TRY(b.n.alloc(8, stream));
+  Q.n_ovf = static_cast<unsigned long long*>(b.n.p);
+  int cus = 256;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e.device));
+  // two full resident rounds of scan blocks (2 per CU at 56 KB of LDS): the scan strides over the
+  // text, so every block does the same work, and a grid of 8 per CU ran 2.7 rounds (the last one 2/3
+  // full); one round left the verify's 2 persistent blocks per CU 1.5 regions each (1.21 vs 1.15 ms)
+  // instantiations by the gram kinds in use (3-grams alone, 4-grams, 5-gram screens, or mixed)
+  const uint32_t qk = (Q.use3 ? 1u : 0u) | (Q.use4 ? 2u : 0u) | (Q.use5 ? 4u : 0u);
+  const void* scan_fns[8] = {reinterpret_cast<const void*>(&qgram_scan_kernel<true, false, false>),
+                             reinterpret_cast<const void*>(&qgram_scan_kernel<true, false, false>),
+                             reinterpret_cast<const void*>(&qgram_scan_kernel<false, true, false>),
+                             reinterpret_cast<const void*>(&qgram_scan_kernel<true, true, false>),
+                             reinterpret_cast<const void*>(&qgram_scan_kernel<false, false, true>),
+                             reinterpret_cast<const void*>(&qgram_scan_kernel<true, false, true>),
+                             reinterpret_cast<const void*>(&qgram_scan_kernel<false, true, true>),
+                             reinterpret_cast<const void*>(&qgram_scan_kernel<true, true, true>)};
+  const void* scan_fn = scan_fns[qk];
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, scan_fn, 64 * QG_WAVES, 0) != hipSuccess || per_cu < 1)
+    per_cu = 1;
+  const uint32_t sgrid =
+      (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 8191) / 8192, (uint64_t)cus * (uint64_t)per_cu * 2));
+  // regions of 1/16 of a block's positions (C5 fills ~half); the overflow list is checked after
+  Q.nreg = sgrid;
+  Q.region = std::max<uint64_t>(256, (n / sgrid + 15) / 16);
+  HIP_TRY(b.cand.alloc(Q.region * sgrid * 8, stream));
+  HIP_TRY(b.rcnt.alloc((size_t)sgrid * 4, stream));
+  Q.cand = static_cast<unsigned long long*>(b.cand.p);
+  Q.rcnt = static_cast<uint32_t*>(b.rcnt.p);
+  uint64_t ocap = 1 << 20;
+  nc = 0;  // overflow entries
+  for (;;) {  // candidates: one scan, again with room for all of them if the overflow list overflowed
+    HIP_TRY(b.ovf.alloc(ocap * 8, stream));
+    Q.ovf = static_cast<unsigned long long*>(b.ovf.p);
+    Q.ovf_cap = ocap;
+    HIP_TRY(hipMemsetAsync(b.n.p, 0, 8, stream));
+    switch (qk) {
+      case 2: hipLaunchKernelGGL((qgram_scan_kernel<false, true, false>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
+      case 3: hipLaunchKernelGGL((qgram_scan_kernel<true, true, false>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
+      case 4: hipLaunchKernelGGL((qgram_scan_kernel<false, false, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
+      case 5: hipLaunchKernelGGL((qgram_scan_kernel<true, false, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
+      case 6: hipLaunchKernelGGL((qgram_scan_kernel<false, true, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
+      case 7: hipLaunchKernelGGL((qgram_scan_kernel<true, true, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
+      default: hipLaunchKernelGGL((qgram_scan_kernel<true, false, false>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&nc, b.n.p, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (nc <= ocap) break;
+    // which candidates overflow depends on wave timing (a block's first failed reservation varies
+    // by up to one drain, 64 x 255 entries): regrow with headroom so the re-scan fits
+    ocap = nc + nc / 4 + (uint64_t)sgrid * 64 * 255;
+  }
+  if (diag_env("FAC_TIMING")) {
+    std::vector<uint32_t> rc(sgrid);
+    HIP_TRY(hipMemcpyAsync(rc.data(), b.rcnt.p, (size_t)sgrid * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    uint64_t tot = nc, mx = 0;
+    for (uint32_t c : rc) tot += c, mx = std::max<uint64_t>(mx, c);
+    std::fprintf(stderr, "FAC_QGRAM text %llu symbols, %llu candidates (%llu overflow, region %llu, fullest %llu), use3 %u use4 %u use5 %u\n",
+                 (unsigned long long)n, (unsigned long long)tot, nc, (unsigned long long)Q.region,
+                 (unsigned long long)mx, Q.use3, Q.use4, Q.use5);
+  }
+  vg = dim3((uint32_t)std::min<uint64_t>(sgrid + 1, (uint64_t)cus * (T.m16 ? 2 : 8)));
+  return FAC_OK;
 }
 
 int prefilter_windows(const Engine& e, const Haystack& h, const SegDesc& view, const std::vector<uint32_t>& ks,
@@ -6651,56 +6996,12 @@ int prefilter_windows_ex(const Engine& e, const Haystack& h, const SegDesc& view
   B.cover = static_cast<uint32_t*>(d_cover.p);
   const uint64_t segs = (n + B.seg_len - 1) / B.seg_len;
   const uint64_t waves = segs * ((nw + 63) / 64);
-  const uint32_t kmax = T->kmax;
   const dim3 bgrid((uint32_t)std::max<uint64_t>(1, (waves + 3) / 4));
-  if (nw == 0) {
-    // every pattern takes the q-gram path
-  } else if (T->w32) {
-    if (kmax == 0) hipLaunchKernelGGL((bitap_kernel<0, uint32_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax == 1) hipLaunchKernelGGL((bitap_kernel<1, uint32_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax == 2) hipLaunchKernelGGL((bitap_kernel<2, uint32_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax <= 4) hipLaunchKernelGGL((bitap_kernel<4, uint32_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax <= 8) hipLaunchKernelGGL((bitap_kernel<8, uint32_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax <= 16) hipLaunchKernelGGL((bitap_kernel<16, uint32_t>), bgrid, dim3(256), 0, stream, B);
-    else hipLaunchKernelGGL((bitap_kernel<24, uint32_t>), bgrid, dim3(256), 0, stream, B);
-  } else {
-    if (kmax <= 1) hipLaunchKernelGGL((bitap_kernel<1, uint64_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax <= 2) hipLaunchKernelGGL((bitap_kernel<2, uint64_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax <= 4) hipLaunchKernelGGL((bitap_kernel<4, uint64_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax <= 8) hipLaunchKernelGGL((bitap_kernel<8, uint64_t>), bgrid, dim3(256), 0, stream, B);
-    else if (kmax <= 16) hipLaunchKernelGGL((bitap_kernel<16, uint64_t>), bgrid, dim3(256), 0, stream, B);
-    else hipLaunchKernelGGL((bitap_kernel<24, uint64_t>), bgrid, dim3(256), 0, stream, B);
-  }
+  if (nw != 0) launch_bitap<false>(*T, B, bgrid, stream);  // (0: every pattern takes the q-gram path)
   HIP_TRY(hipGetLastError());
-  PoolBuf d_qcand, d_qn, d_qovf, d_qrcnt;
+  QgramBufs qb;
   if (T->q) {
-    HIP_TRY(d_qn.alloc(8, stream));
-    QgramParams Q{};
-    Q.ids = static_cast<const uint8_t*>(d_ids.p);
-    Q.n = n;
-    Q.nsafe = n + 80;
-    if (T->bytes) {
-      Q.ids = reinterpret_cast<const uint8_t*>((uintptr_t)vb & ~(uintptr_t)15);
-      Q.off = (uint32_t)(vb - Q.ids);
-      Q.nsafe = (uint64_t)(h.d_utf8 + h.len - Q.ids);
-      Q.bytes = 1;
-      Q.ci = e.case_insensitive ? 1u : 0u;
-      Q.aid = e.d_ascii_id;
-    }
-    Q.tab = static_cast<const uint2*>(T->tab);
-    Q.tab_mask = T->ts - 1;
-    Q.ent = static_cast<const uint2*>(T->ent);
-    Q.use3 = T->use3;
-    Q.use4 = T->use4;
-    Q.use5 = T->use5;
-    Q.n_ovf = static_cast<unsigned long long*>(d_qn.p);
-    Q.pmask = static_cast<const uint64_t*>(T->qmask);
-    Q.pm = static_cast<const uint32_t*>(T->qpm);
-    Q.rows = e.alphabet + 1;
-    Q.cover = static_cast<uint32_t*>(d_cover.p);
-    Q.bits = static_cast<const uint32_t*>(T->qbits);
-    Q.m16 = static_cast<const uint32_t*>(T->m16);
-    Q.m16_words = T->m16_words;
+    QgramParams Q = qgram_params(e, h, *T, vb, d_ids.p, n, d_cover.p);
     if (win) {
       Q.nwin = (uint32_t)wlo.size();
       Q.wlo = static_cast<const uint64_t*>(d_wlo.p);
@@ -6720,74 +7021,12 @@ int prefilter_windows_ex(const Engine& e, const Haystack& h, const SegDesc& view
         }
       }
     }
-    int cus = 256;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e.device));
-    // two full resident rounds of scan blocks (2 per CU at 56 KB of LDS): the scan strides over the
-    // text, so every block does the same work, and a grid of 8 per CU ran 2.7 rounds (the last one 2/3
-    // full); one round left the verify's 2 persistent blocks per CU 1.5 regions each (1.21 vs 1.15 ms)
-    // instantiations by the gram kinds in use (3-grams alone, 4-grams, 5-gram screens, or mixed)
-    const uint32_t qk = (Q.use3 ? 1u : 0u) | (Q.use4 ? 2u : 0u) | (Q.use5 ? 4u : 0u);
-    const void* scan_fns[8] = {reinterpret_cast<const void*>(&qgram_scan_kernel<true, false, false>),
-                               reinterpret_cast<const void*>(&qgram_scan_kernel<true, false, false>),
-                               reinterpret_cast<const void*>(&qgram_scan_kernel<false, true, false>),
-                               reinterpret_cast<const void*>(&qgram_scan_kernel<true, true, false>),
-                               reinterpret_cast<const void*>(&qgram_scan_kernel<false, false, true>),
-                               reinterpret_cast<const void*>(&qgram_scan_kernel<true, false, true>),
-                               reinterpret_cast<const void*>(&qgram_scan_kernel<false, true, true>),
-                               reinterpret_cast<const void*>(&qgram_scan_kernel<true, true, true>)};
-    const void* scan_fn = scan_fns[qk];
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, scan_fn, 64 * QG_WAVES, 0) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    const uint32_t sgrid =
-        (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 8191) / 8192, (uint64_t)cus * (uint64_t)per_cu * 2));
-    // regions of 1/16 of a block's positions (C5 fills ~half); the overflow list is checked after
-    Q.nreg = sgrid;
-    Q.region = std::max<uint64_t>(256, (n / sgrid + 15) / 16);
-    HIP_TRY(d_qcand.alloc(Q.region * sgrid * 8, stream));
-    HIP_TRY(d_qrcnt.alloc((size_t)sgrid * 4, stream));
-    Q.cand = static_cast<unsigned long long*>(d_qcand.p);
-    Q.rcnt = static_cast<uint32_t*>(d_qrcnt.p);
-    uint64_t ocap = 1 << 20;
-    unsigned long long nc = 0;  // overflow entries
-    for (;;) {  // candidates: one scan, again with room for all of them if the overflow list overflowed
-      HIP_TRY(d_qovf.alloc(ocap * 8, stream));
-      Q.ovf = static_cast<unsigned long long*>(d_qovf.p);
-      Q.ovf_cap = ocap;
-      HIP_TRY(hipMemsetAsync(d_qn.p, 0, 8, stream));
-      switch (qk) {
-        case 2: hipLaunchKernelGGL((qgram_scan_kernel<false, true, false>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
-        case 3: hipLaunchKernelGGL((qgram_scan_kernel<true, true, false>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
-        case 4: hipLaunchKernelGGL((qgram_scan_kernel<false, false, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
-        case 5: hipLaunchKernelGGL((qgram_scan_kernel<true, false, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
-        case 6: hipLaunchKernelGGL((qgram_scan_kernel<false, true, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
-        case 7: hipLaunchKernelGGL((qgram_scan_kernel<true, true, true>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
-        default: hipLaunchKernelGGL((qgram_scan_kernel<true, false, false>), dim3(sgrid), dim3(64 * QG_WAVES), 0, stream, Q); break;
-      }
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(&nc, d_qn.p, 8, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (nc <= ocap) break;
-      // which candidates overflow depends on wave timing (a block's first failed reservation varies
-      // by up to one drain, 64 x 255 entries): regrow with headroom so the re-scan fits
-      ocap = nc + nc / 4 + (uint64_t)sgrid * 64 * 255;
-    }
-    if (diag_env("FAC_TIMING")) {
-      std::vector<uint32_t> rc(sgrid);
-      HIP_TRY(hipMemcpyAsync(rc.data(), d_qrcnt.p, (size_t)sgrid * 4, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      uint64_t tot = nc, mx = 0;
-      for (uint32_t c : rc) tot += c, mx = std::max<uint64_t>(mx, c);
-      std::fprintf(stderr, "FAC_QGRAM text %llu symbols, %llu candidates (%llu overflow, region %llu, fullest %llu), use3 %u use4 %u use5 %u\n",
-                   (unsigned long long)n, (unsigned long long)tot, nc, (unsigned long long)Q.region,
-                   (unsigned long long)mx, Q.use3, Q.use4, Q.use5);
-    }
-    {
-      const dim3 vg((uint32_t)std::min<uint64_t>(sgrid + 1, (uint64_t)cus * (T->m16 ? 2 : 8)));
-      if (Q.nwin) launch_qverify<true>(*T, Q, vg, stream);
-      else launch_qverify<false>(*T, Q, vg, stream);
-      HIP_TRY(hipGetLastError());
-    }
+    dim3 vg;
+    unsigned long long nc = 0;
+    if (int rc = qgram_candidates(e, *T, Q, n, stream, qb, vg, nc, err)) return rc;
+    if (Q.nwin) launch_qverify<1>(*T, Q, vg, stream);
+    else launch_qverify<0>(*T, Q, vg, stream);
+    HIP_TRY(hipGetLastError());
     if (diag_env("FAC_RC_DEBUG"))
       std::fprintf(stderr, "FAC_QGRAM patterns=%zu/%zu grams=%zu keys=%zu candidates=%llu full-scan words=%u bytes=%d\n",
                    T->n_qpat, e.bp_m.size(), T->n_grams, T->n_keys, nc, nw, (int)T->bytes);
@@ -6864,6 +7103,156 @@ int prefilter_windows_ex(const Engine& e, const Haystack& h, const SegDesc& view
   return FAC_OK;
 }
 
+
+// ---- Pre-filtered batches (fac.h fac_search_batch_prefiltered) -----------------------------------
+// One pass over the batch's concatenated bytes gives every document its own merged bitap windows:
+// the packed full scan resets its automaton at every document start (bitap_kernel<.., DOCS>), the
+// q-gram verify takes the bounds of the candidate's document (qgram_verify_docs_kernel), both from
+// the document-start bitmap, and the runs of the one coverage bitmap are cut at document starts
+// (documents are disjoint, so no second bitmap and no window table). Runs are counted per bitmap
+// word, scanned and written in place as segment descriptors, so they are sorted by start -- by
+// document, then by start -- without a sort, and nothing per document or per run visits the host.
+int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<uint32_t>& ks, hipStream_t stream,
+                            BatchWindows& out, fac_stats* stats, std::string& err) {
+  HIP_TRY(hipSetDevice(e.device));
+  if (!stream) stream = e.stream;
+  const Haystack& h = b.h;
+  const uint64_t n = h.len;
+  out.s = stream;
+  out.n = out.windows = 0;
+  if (!h.ascii) {
+    err = "pre-filtered batches need an all-ASCII batch";
+    return FAC_E_UNSUPPORTED;
+  }
+  if (n == 0 || b.n_segs == 0) return FAC_OK;
+  const uint64_t n_words = (n + 31) / 32;
+  {  // the document-start bitmap, once per staging
+    std::lock_guard<std::mutex> lk(b.dstart_mu);
+    if (!b.dstart_ready) {
+      if (b.dstart_cap < n_words) {
+        if (b.d_dstart) HIP_TRY(hipFree(b.d_dstart));
+        b.d_dstart = nullptr;
+        b.dstart_cap = 0;
+        HIP_TRY(hipMalloc((void**)&b.d_dstart, n_words * 4));
+        b.dstart_cap = n_words;
+      }
+      HIP_TRY(hipMemsetAsync(b.d_dstart, 0, n_words * 4, stream));
+      hipLaunchKernelGGL(doc_starts_kernel, dim3((uint32_t)((b.n_docs + 255) / 256)), dim3(256), 0, stream, b.d_offsets,
+                         b.n_docs, b.d_dstart);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(stream));  // (another stream's search may use it next)
+      b.dstart_ready = true;
+    }
+  }
+  const uint8_t* vb = h.d_utf8;
+  const bool want_bytes = ((uintptr_t)h.d_utf8 & 15u) == 0 && !diag_env("FAC_QGRAM_IDS");
+  const PfTables* T = nullptr;
+  if (int rc = pf_tables(e, ks, want_bytes, T, err)) return rc;
+  const uint32_t nw = T->nw;
+  PoolBuf d_ids, d_cover, d_cnt, d_pos, d_lens;
+  if (!T->bytes) {  // transcode (prefilter.rs:253-258): the symbol ids of every document's bytes
+    HIP_TRY(d_ids.alloc(n + 80, stream));
+    const uint64_t threads = (n + 15) / 16;
+    hipLaunchKernelGGL(transcode_ascii_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, vb, n,
+                       e.d_ascii_id, static_cast<uint8_t*>(d_ids.p));
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(d_cover.alloc(n_words * 4, stream));
+  HIP_TRY(hipMemsetAsync(d_cover.p, 0, n_words * 4, stream));
+  Events ev;
+  HIP_TRY(hipEventCreate(&ev.a));
+  HIP_TRY(hipEventCreate(&ev.b));
+  HIP_TRY(hipEventRecord(ev.a, stream));
+  if (nw != 0) {
+    BitapParams B{};
+    B.ids = static_cast<const uint8_t*>(d_ids.p);
+    B.n = n;
+    B.mask_t = T->pmask;
+    B.top = T->ptop;
+    B.k = static_cast<const uint32_t*>(T->wk);
+    B.n_words = nw;
+    B.seg_len = 4096;
+    B.cover = static_cast<uint32_t*>(d_cover.p);
+    B.dstart = b.d_dstart;
+    const uint64_t waves = ((n + B.seg_len - 1) / B.seg_len) * ((nw + 63) / 64);
+    launch_bitap<true>(*T, B, dim3((uint32_t)std::max<uint64_t>(1, (waves + 3) / 4)), stream);
+    HIP_TRY(hipGetLastError());
+  }
+  QgramBufs qb;
+  if (T->q) {
+    QgramParams Q = qgram_params(e, h, *T, vb, d_ids.p, n, d_cover.p);
+    Q.dstart = b.d_dstart;
+    dim3 vg;
+    unsigned long long nc = 0;
+    if (int rc = qgram_candidates(e, *T, Q, n, stream, qb, vg, nc, err)) return rc;
+    launch_qverify<2>(*T, Q, vg, stream);
+    HIP_TRY(hipGetLastError());
+  }
+  // runs: per-word counts, their scan (entry n_words: the total), then the descriptors in place
+  const uint32_t* cov = static_cast<const uint32_t*>(d_cover.p);
+  HIP_TRY(d_cnt.alloc((n_words + 1) * 8, stream));
+  HIP_TRY(d_pos.alloc((n_words + 1) * 8, stream));
+  hipLaunchKernelGGL(runs_docs_count_kernel, dim3((uint32_t)((n_words + 1 + 255) / 256)), dim3(256), 0, stream, cov,
+                     b.d_dstart, n_words, n, static_cast<uint64_t*>(d_cnt.p));
+  HIP_TRY(hipGetLastError());
+  if (int rc = exclusive_sum_u64(static_cast<const uint64_t*>(d_cnt.p), static_cast<uint64_t*>(d_pos.p), n_words + 1, stream, err))
+    return rc;
+  uint64_t n_runs = 0;
+  HIP_TRY(hipMemcpyAsync(&n_runs, static_cast<uint64_t*>(d_pos.p) + n_words, 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (n_runs > 0xFFFFFFFFull) {
+    err = "a pre-filtered batch holds at most 2^32 - 1 merged windows";
+    return FAC_E_UNSUPPORTED;
+  }
+  uint64_t total = 0;
+  if (n_runs) {
+    hipError_t he = hipSuccess;
+    out.d_segs = static_cast<SegDesc*>(call_scratch_take(n_runs * sizeof(SegDesc), stream, &he));
+    HIP_TRY(he);
+    out.d_prefix = static_cast<uint64_t*>(call_scratch_take((n_runs + 1) * 8, stream, &he));
+    HIP_TRY(he);
+    HIP_TRY(d_lens.alloc((n_runs + 1) * 8, stream));
+    HIP_TRY(hipMemsetAsync(static_cast<uint64_t*>(d_lens.p) + n_runs, 0, 8, stream));
+    hipLaunchKernelGGL(runs_docs_write_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, stream, cov, b.d_dstart,
+                       n_words, n, static_cast<const uint64_t*>(d_pos.p), b.d_offsets, b.n_docs, out.d_segs,
+                       static_cast<uint64_t*>(d_lens.p));
+    HIP_TRY(hipGetLastError());
+    if (int rc = exclusive_sum_u64(static_cast<const uint64_t*>(d_lens.p), out.d_prefix, n_runs + 1, stream, err)) return rc;
+    HIP_TRY(hipMemcpyAsync(&total, out.d_prefix + n_runs, 8, hipMemcpyDeviceToHost, stream));
+  }
+  HIP_TRY(hipEventRecord(ev.b, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  out.n = n_runs;
+  out.windows = total;
+  if (diag_env("FAC_RC_DEBUG"))
+    std::fprintf(stderr, "FAC_BATCH_PF docs=%llu bytes=%llu full-scan words=%u qgram patterns=%zu/%zu bytes-mode=%d merged windows=%llu start windows=%llu\n",
+                 (unsigned long long)b.n_docs, (unsigned long long)n, nw, T->n_qpat, e.bp_m.size(), (int)T->bytes,
+                 (unsigned long long)n_runs, (unsigned long long)total);
+  if (stats) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    stats->prefilter_ms += ms;
+  }
+  return FAC_OK;
+}
+
+int launch_search_batch_windows(const Engine& e, const Batch& b, const BatchWindows& w, float thr, hipStream_t stream,
+                                MatchSink& sink, fac_stats* stats, std::string& err) {
+  if (w.n == 0) return FAC_OK;
+  HIP_TRY(hipSetDevice(e.device));
+  if (!stream) stream = e.stream;
+  if (e.has_auto_beam && e.beam_width == 0) {  // one merged window is one search_raw call: the running total restarts
+    std::vector<SegDesc> segs(w.n);
+    HIP_TRY(hipMemcpyAsync(segs.data(), w.d_segs, w.n * sizeof(SegDesc), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return launch_search_sink(e, b.h, segs, thr, stream, 0, sink, stats, err);
+  }
+  uint64_t seg_windows = kBatchRcSegWindows;  // the batch's prefix-cache rule, as launch_search_batch
+  if (const char* v = diag_env("FAC_BATCH_RC_SEG")) seg_windows = std::strtoull(v, nullptr, 10);
+  const DevSegs ds{w.d_segs, w.d_prefix, (uint32_t)w.n, w.windows, seg_windows};
+  const uint32_t beam = (uint32_t)std::min<uint64_t>(e.beam_width, 0xFFFFFFFFull);
+  return launch_pass(e, b.h, {}, thr, stream, beam, beam != 0, nullptr, sink, stats, err, &ds);
+}
 
 // ---- Diagnostics: the beam cut alone (tests) ----------------------------------------------------
 // One wave per key array: the array becomes a ring of states (node = original index, pen = key) at a

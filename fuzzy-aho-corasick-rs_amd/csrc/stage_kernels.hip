@@ -839,8 +839,24 @@ __global__ void batch_desc_kernel(const uint64_t* __restrict__ off, uint64_t n_d
 
 }  // namespace
 
+int exclusive_sum_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n, hipStream_t st, std::string& err) {
+  size_t bytes = 0;
+  ST_TRY(rocprim::exclusive_scan(nullptr, bytes, d_in, d_out, uint64_t(0), n, rocprim::plus<uint64_t>(), st));
+  hipError_t he = hipSuccess;
+  void* tmp = call_scratch_take(std::max<size_t>(bytes, 16), st, &he);
+  ST_TRY(he);
+  he = rocprim::exclusive_scan(tmp, bytes, d_in, d_out, uint64_t(0), n, rocprim::plus<uint64_t>(), st);
+  call_scratch_give(tmp, st);
+  ST_TRY(he);
+  return FAC_OK;
+}
+
 void free_batch(Batch& b) {
   (void)hipSetDevice(b.h.device);
+  if (b.d_dstart) (void)hipFree(b.d_dstart);
+  b.d_dstart = nullptr;
+  b.dstart_cap = 0;
+  b.dstart_ready = false;
   if (b.own_offsets && b.d_offsets) (void)hipFree(b.d_offsets);
   b.d_offsets = nullptr;
   if (b.d_meta) (void)hipFree(b.d_meta);
@@ -858,6 +874,7 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   b.n_segs = 0;
   b.windows = 0;
   b.err_doc = b.err_graphemes = 0;
+  b.dstart_ready = false;  // the pre-filter's document-start bitmap is rebuilt for the new offsets
   h.ascii = true;
   h.n = 0;
   {

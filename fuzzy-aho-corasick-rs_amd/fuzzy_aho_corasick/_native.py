@@ -199,11 +199,17 @@ SIGNATURES = {
     "fac_batch_grapheme_starts": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _u64p, ctypes.c_uint64]),
     "fac_search_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_batch_args), _P(_P(fac_match)), _u64p,
                                         _u64p, _P(fac_stats)]),
+    "fac_search_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_batch_args), _P(_P(fac_match)),
+                                                    _u64p, _u64p, _P(fac_stats)]),
+    "fac_batch_prefilter_windows": (ctypes.c_int64, [_engine_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, _u64p,
+                                                     ctypes.c_uint64]),
     "fac_replacements_create": (ctypes.c_int, [_engine_p, ctypes.c_char_p, _u64p, ctypes.c_char_p, ctypes.c_uint64,
                                                _P(ctypes.c_void_p)]),
     "fac_replacements_free": (None, [ctypes.c_void_p]),
     "fac_replace_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_replace_args),
                                          _P(_P(ctypes.c_uint8)), _u64p, _u64p, _u64p, _P(fac_stats)]),
+    "fac_replace_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_replace_args),
+                                                     _P(_P(ctypes.c_uint8)), _u64p, _u64p, _u64p, _P(fac_stats)]),
     "fac_edge_order": (None, [ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "fac_diag_beam_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),

@@ -403,6 +403,63 @@ class Prefiltered:
         opts = opts or SearchOptions()
         return self.engine._search_ranked(haystack, opts.threshold_, opts.order_, opts.overlap_, prefilter=True)
 
+    def _batch_parts(self, enc):
+        """Indices of the documents one pre-filtered batch takes: the ASCII ones (the device filter
+        is for all-ASCII batches; the others go through `search` one by one)."""
+        return [d for d, raw in enumerate(enc) if raw.isascii()]
+
+    def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None) -> List[FuzzyMatches]:
+        """`[self.search(h, opts) for h in haystacks]`: the ASCII haystacks as one pre-filtered batch
+        (fac_search_batch_prefiltered), the others one by one, results in input order."""
+        opts = opts or SearchOptions()
+        haystacks = list(haystacks)
+        enc = [h.encode("utf-8") for h in haystacks]
+        out = [None] * len(haystacks)
+        idx = self._batch_parts(enc)
+        if idx:
+            data, offsets = batch_offsets([enc[d] for d in idx])
+            recs, doc_off = StagedBatch(self.engine, data, offsets).search_records(opts, prefilter=True)
+            for k, d in enumerate(idx):
+                rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
+                         int(r["insertions"]), int(r["deletions"]), int(r["substitutions"]), int(r["swaps"]),
+                         int(r["edits"])) for r in recs[int(doc_off[k]):int(doc_off[k + 1])]]
+                out[d] = self.engine._to_matches(haystacks[d], enc[d], rows)
+        for d, h in enumerate(haystacks):
+            if out[d] is None:
+                out[d] = self.search(h, opts)
+        return out
+
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements) -> List[str]:
+        """`engine.replace_batch` over the pre-filtered search: the ASCII texts as one pre-filtered
+        batch (fac_replace_batch_prefiltered), the others through `search` and the host splice of
+        matches.rs:170-187, results in input order. `replacements`: one entry per pattern (None
+        keeps the matched text), or a ReplacementTable built from such a list."""
+        texts = list(texts)
+        enc = [t.encode("utf-8") for t in texts]
+        out = [None] * len(texts)
+        idx = self._batch_parts(enc)
+        if isinstance(replacements, ReplacementTable):
+            table, reps = replacements, replacements.replacements
+        else:
+            reps = list(replacements)
+            table = ReplacementTable(self.engine, reps) if idx else None
+        if idx:
+            data, offsets = batch_offsets([enc[d] for d in idx])
+            buf, off = StagedBatch(self.engine, data, offsets).replace_bytes(table, opts, prefilter=True)
+            for k, d in enumerate(idx):
+                out[d] = buf[int(off[k]):int(off[k + 1])].decode("utf-8")
+        order = Order.Default if opts.order_ == Order.Unsorted else opts.order_
+        overlap = Overlap.NonOverlapping if opts.overlap_ == Overlap.Keep else opts.overlap_
+        for d, t in enumerate(texts):
+            if out[d] is None:
+                ms = self.engine._search_ranked(t, opts.threshold_, order, overlap, prefilter=True)
+                out[d] = ms.replace(lambda m: _as_text(reps[m.pattern_index]))
+        return out
+
+
+def _as_text(r):
+    return bytes(r).decode("utf-8") if isinstance(r, (bytes, bytearray, memoryview)) else r
+
 
 def prefilter_windows(engine: "FuzzyAhoCorasick", haystack: str, threshold: float):
     """Diagnostics: merged bitap candidate windows (grapheme ranges), or None on fallback."""
@@ -834,8 +891,11 @@ class StagedBatch:
         a.stream = stream or None
         return a
 
-    def search_records(self, opts: SearchOptions = None, out=None, stream=None, stats=None, doc_offsets_out=None):
-        """fac_search_batch: (records, doc_offsets). Records (MATCH_DTYPE) are grouped by document,
+    def search_records(self, opts: SearchOptions = None, out=None, stream=None, stats=None, doc_offsets_out=None,
+                       prefilter: bool = False):
+        """fac_search_batch (`prefilter`: fac_search_batch_prefiltered, every document searched as
+        engine.with_prefilter().search would; all-ASCII batches only where the filter runs):
+        (records, doc_offsets). Records (MATCH_DTYPE) are grouped by document,
         offsets relative to the record's own document, each document in FuzzyMatches::apply's order;
         doc_offsets (n_docs + 1) indexes them. `out`: a uint8 CUDA tensor to leave the records in HBM
         (32 bytes each): returns (the tensor's filled part, doc_offsets); FAC_E_OUTPUT_CAPACITY is
@@ -854,10 +914,9 @@ class StagedBatch:
             if doc_offsets_out.numel() < self.n_docs + 1 or doc_offsets_out.element_size() != 8:
                 raise ValueError("doc_offsets_out needs n_docs + 1 64-bit entries")
             a.device_doc_offsets = doc_offsets_out.data_ptr()
-        rc = _native.lib.fac_search_batch(self.engine._h, self._h, ctypes.byref(a),
-                                          None if out is not None else ctypes.byref(ptr), ctypes.byref(n),
-                                          doc_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-                                          ctypes.byref(stats) if stats is not None else None)
+        fn = _native.lib.fac_search_batch_prefiltered if prefilter else _native.lib.fac_search_batch
+        rc = fn(self.engine._h, self._h, ctypes.byref(a), None if out is not None else ctypes.byref(ptr), ctypes.byref(n),
+                doc_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(stats) if stats is not None else None)
         if rc:
             try:
                 _raise(rc)
@@ -868,9 +927,26 @@ class StagedBatch:
             return out[: n.value * _native.REC_BYTES], doc_off
         return _native.take_records(ptr, n.value), doc_off
 
+    def prefilter_windows(self, threshold: float, stream=None):
+        """Diagnostics (fac_batch_prefilter_windows): the merged bitap windows of every document as
+        (document, start, end) triples, document-relative, ascending; None where the reference falls
+        back to the full search."""
+        cap = 1024
+        while True:
+            buf = (ctypes.c_uint64 * (3 * cap))()
+            n = _native.lib.fac_batch_prefilter_windows(self.engine._h, self._h, f32(threshold),
+                                                        ctypes.c_void_p(stream or 0), buf, cap)
+            if n == -1:
+                return None
+            if n < 0:
+                _raise(-n)
+            if n <= cap:
+                return [(int(buf[3 * i]), int(buf[3 * i + 1]), int(buf[3 * i + 2])) for i in range(n)]
+            cap = n
+
     def replace_bytes(self, table: "ReplacementTable", opts: SearchOptions = None, out=None, offsets_out=None,
-                      stream=None, stats=None):
-        """fac_replace_batch: (bytes, offsets). Output document d is bytes[offsets[d]:offsets[d + 1]],
+                      stream=None, stats=None, prefilter: bool = False):
+        """fac_replace_batch (`prefilter`: fac_replace_batch_prefiltered): (bytes, offsets). Output document d is bytes[offsets[d]:offsets[d + 1]],
         the crate's engine.replace(doc_d, opts, callback) with callback = the table's entry of the
         match's pattern (options normalised as `segmented`, query.rs:46-64). `out`: a uint8 CUDA
         tensor to leave the bytes in HBM: returns (the tensor's filled part, offsets);
@@ -896,10 +972,10 @@ class StagedBatch:
             if offsets_out.numel() < self.n_docs + 1 or offsets_out.element_size() != 8:
                 raise ValueError("offsets_out needs n_docs + 1 64-bit entries")
             a.device_out_offsets = offsets_out.data_ptr()
-        rc = _native.lib.fac_replace_batch(self.engine._h, self._h, table._h, ctypes.byref(a),
-                                           None if out is not None else ctypes.byref(ptr), ctypes.byref(n),
-                                           offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(nrep),
-                                           ctypes.byref(stats) if stats is not None else None)
+        fn = _native.lib.fac_replace_batch_prefiltered if prefilter else _native.lib.fac_replace_batch
+        rc = fn(self.engine._h, self._h, table._h, ctypes.byref(a), None if out is not None else ctypes.byref(ptr),
+                ctypes.byref(n), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(nrep),
+                ctypes.byref(stats) if stats is not None else None)
         if rc:
             try:
                 _raise(rc)
@@ -941,7 +1017,8 @@ class ReplacementTable:
     (fac_replacements_create); freed with the object."""
 
     def __init__(self, engine: FuzzyAhoCorasick, replacements):
-        data, offsets, keep = replacement_table(replacements)
+        self.replacements = list(replacements)
+        data, offsets, keep = replacement_table(self.replacements)
         self.engine, self.n_patterns = engine, len(keep)
         off = (ctypes.c_uint64 * len(offsets))(*offsets)
         h = ctypes.c_void_p()

@@ -327,8 +327,16 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  * start / end while it is inside the library; the tag is cleared before records leave it), and no
  * engine with multi-character mappings when some document is not ASCII. Auto-beam engines read the
  * segment descriptors back and run the per-segment auto-beam loop of fac_search_staged on the host.
- * Batched replace is provided (fac_replace_batch below). Batched strip_*, split and segment_*,
- * pre-filtered batches and multi-GPU batches are not. */
+ * Batched replace is provided (fac_replace_batch below), and both calls have a pre-filtered form
+ * for all-ASCII batches (fac_search_batch_prefiltered, fac_replace_batch_prefiltered below).
+ * Batched strip_*, split and segment_* and multi-GPU batches are not provided.
+ *
+ * Limits of the pre-filtered forms: where the filter runs, the batch must be all ASCII -- one
+ * non-ASCII document gives FAC_E_UNSUPPORTED with nothing written (a non-ASCII document's symbol
+ * ids need the per-grapheme folded-string lookup, which exists only on the host; the same limit
+ * fac_stream_windows_staged_device has) -- and it holds at most 2^32 - 1 merged windows. Staging
+ * errors stay fac_batch_stage's: a document over the grapheme limit fails there, which is stricter
+ * than the crate, whose Prefiltered::search only checks each merged window it searches. */
 typedef struct fac_batch fac_batch;
 
 /* Documents d = 0..n_docs-1 are bytes [offsets[d], offsets[d+1]) of utf8.
@@ -379,6 +387,31 @@ typedef struct fac_batch_args {
 int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
                      uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats);
 
+/* fac_search_batch with the crate's bit-parallel pre-filter per document: for every document d the
+ * result is engine.with_prefilter().search(doc_d, opts) (prefilter.rs:113-155, 304-374) -- the
+ * document transcoded alone, bitap_windows for every pattern from the initial state at its first
+ * symbol, the windows sorted and merged (adjacent ones merge), search_raw on each merged window as a
+ * haystack of its own, then FuzzyMatches::apply per document. No automaton state, coverage or merged
+ * window crosses a document boundary. One pass over the batch's bytes finds every document's
+ * windows; the descriptors of the merged windows are written by the device and searched in one
+ * launch. The result is not always fac_search_batch's: a merged window is its own search_raw call,
+ * so an auto-beam engine's running total restarts per merged window (one segment each, searched by
+ * the per-segment loop fac_search_batch uses for such engines).
+ * Where the reference falls back to the full search -- no filter (fac_prefilter_active == 0, which
+ * covers engines with mappings), or k_for above 24 for some pattern at this threshold -- the call is
+ * fac_search_batch exactly, for any batch. Otherwise arguments, contract, errors and limits are
+ * fac_search_batch's plus the all-ASCII limit above. stats: prefilter_ms = device time of the scan,
+ * verify and runs; windows = the start windows searched, the merged windows' lengths summed. */
+int fac_search_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args,
+                                 fac_match** out, uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats);
+
+/* Tests and diagnostics: the merged windows fac_search_batch_prefiltered searches, as
+ * (document, start, end) triples with document-relative offsets, ascending by document, then by
+ * start. Writes up to `cap` triples to `out` and returns their count, -1 where the reference falls
+ * back to the full search, or minus the error code (every FAC_E_* that can occur here is >= 100). */
+int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* batch, float threshold, void* stream,
+                                    uint64_t* out, uint64_t cap);
+
 /* ---- Batched replace: FuzzyReplacer::replace (replacer.rs:22-25, query.rs:46-96,
  * matches.rs:165-188) of every document of a staged batch, spliced on the device.
  *
@@ -427,6 +460,14 @@ typedef struct fac_replace_args {
 int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
                       const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
                       uint64_t* n_replaced, fac_stats* stats);
+
+/* fac_replace_batch over fac_search_batch_prefiltered's records: the same splice of
+ * matches.rs:170-187, per document, of engine.with_prefilter().search(doc_d, opts) with the options
+ * normalised as `segmented`. Arguments and contract as fac_replace_batch; fallback and limits as
+ * fac_search_batch_prefiltered. */
+int fac_replace_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
+                                  const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                                  uint64_t* n_replaced, fac_stats* stats);
 
 /* Streaming search (stream.rs:77-297): feed the input in the reader's read() pieces; windows
  * of `window_bytes` (0 = the crate's 256 KiB) are cut, searched (sorted + non-overlapping) and

@@ -21,6 +21,18 @@ pattern to its upper-cased form):
   (b') the per-document loop replacer.replace(doc, opts) over the fixed sample, host wall clock,
   and a hipMemcpyDtoDAsync of the output's size, the copy kernel's yardstick.
 
+With --prefilter the legs are (DESIGN.md §6a "Pre-filtered batches"; workloads c2, c5 and "c5n" =
+c5's engine on fresh filler words with no planted match):
+
+  (p)  one fac_search_batch_prefiltered call, records left in HBM, device events; once per
+       prefix-cache rule like (a),
+  (a)  fac_search_batch on the same batch (the path without the filter),
+  (c)  fac_search_staged_prefiltered of the same bytes as ONE haystack: the boundary-free ceiling
+       (a different result set; its records go to the host),
+  (b)  the per-document loop fac_search_prefiltered(doc) over the fixed sample, host wall clock.
+
+  The legs alternate; "records_equal" compares (p)'s records of the sample with (b)'s.
+
 Staging is reported in ms per GiB: the batch stager against fac_haystack_stage_device on the same
 bytes. One JSON line per configuration; "gate" is true when (a) beats (b) per document by more than
 (b)'s own spread and (a)'s records for the sample equal (b)'s.
@@ -254,6 +266,111 @@ def run_replace(name, nbytes, L, sample, rounds, profile_only):
             "bytes_equal": bool(same), "gate": bool(same and min(b_doc) - r_doc > max(b_doc) - min(b_doc))}
 
 
+def prefilter_workload(name, nbytes):
+    """c2 / c5 as workloads.config; c5n: c5's patterns and threshold over fresh filler words alone."""
+    if name != "c5n":
+        return workload(name, nbytes)
+    if (name, nbytes) not in _CACHE:
+        w5, engine = workload("c5", 1 << 20)
+        rng = workloads.XorShift(0xC5F1).numpy()
+        text = workloads._fresh_filler(rng, [workloads.ASCII_LOWER], nbytes, 2, 12)[:nbytes]
+        w = workloads.Workload("c5n", w5.patterns, text, w5.edits, w5.beam, w5.case_insensitive, w5.threshold, True)
+        _CACHE[(name, nbytes)] = (w, engine)
+    return _CACHE[(name, nbytes)]
+
+
+def run_prefilter(name, nbytes, L, sample, rounds, rules, profile_only):
+    w, engine = prefilter_workload(name, nbytes)
+    data = w.haystack
+    off = cut_documents(data, L)
+    nd = len(off) - 1
+    dev = torch.device("cuda", engine.device)
+    t_data = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
+    t_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    sh = stream.cuda_stream
+    opts = SearchOptions().threshold(w.threshold)
+    bufs = {"out": torch.empty(max(1 << 16, len(data) // 16) * 32, dtype=torch.uint8, device=dev)}
+    sb = StagedBatch.from_device(engine, t_data.data_ptr(), t_off.data_ptr(), nd, len(data), stream=sh)
+    stats = _native.fac_stats()
+
+    def batch_search(prefilter):
+        while True:
+            try:
+                return sb.search_records(opts, out=bufs["out"], stream=sh, prefilter=prefilter,
+                                         stats=stats if prefilter else None)
+            except Exception as ex:  # FAC_E_OUTPUT_CAPACITY: grow and search again
+                need = getattr(ex, "needed", 0)
+                if not need:
+                    raise
+                bufs["out"] = torch.empty(int(need * 1.1 + 1024) * 32, dtype=torch.uint8, device=dev)
+
+    def pf_records(doc):
+        out = ctypes.POINTER(_native.fac_match)()
+        n = ctypes.c_uint64()
+        eg = ctypes.c_uint64()
+        rc = _native.lib.fac_search_prefiltered(engine._h, doc, len(doc), f32(w.threshold), ctypes.byref(out),
+                                                ctypes.byref(n), ctypes.byref(eg))
+        if rc:
+            raise RuntimeError(_native.last_error())
+        return _native.take_records(out, n.value)
+
+    for rule in rules:  # warm-up: buffers, tables, the output size
+        os.environ["FAC_BATCH_RC_SEG"] = str(rule)
+        batch_search(True)
+    os.environ.pop("FAC_BATCH_RC_SEG")
+    batch_search(False)
+    if profile_only:
+        for _ in range(3):
+            batch_search(True)
+        return None
+    hay = StagedHaystack.from_device(engine, t_data.data_ptr(), len(data), stream=sh)
+    hay.search_prefiltered_records(w.threshold, stream=sh)
+    idx = np.unique(np.linspace(0, nd - 1, min(sample, nd)).astype(np.int64))
+    docs = [data[int(off[d]):int(off[d + 1])] for d in idx]
+    for d in docs[:50]:
+        pf_records(d)
+    p_ms = {r: [] for r in rules}
+    pf_ms, a_ms, b_ms, c_ms = [], [], [], []
+    for _ in range(rounds):
+        for rule in rules:
+            os.environ["FAC_BATCH_RC_SEG"] = str(rule)
+            stats.prefilter_ms = 0.0
+            stats.windows = 0
+            ms, (recs, doc_off) = timed(stream, lambda: batch_search(True))
+            p_ms[rule].append(ms)
+        pf_ms.append(stats.prefilter_ms)
+        windows = int(stats.windows)
+        os.environ.pop("FAC_BATCH_RC_SEG")
+        a_ms.append(timed(stream, lambda: batch_search(False))[0])
+        c_ms.append(timed(stream, lambda: hay.search_prefiltered_records(w.threshold, stream=sh))[0])
+        t0 = time.perf_counter()
+        per_doc = [pf_records(d) for d in docs]
+        b_ms.append(1e3 * (time.perf_counter() - t0))
+    os.environ["FAC_BATCH_RC_SEG"] = str(rules[-1])
+    recs, doc_off = batch_search(True)
+    os.environ.pop("FAC_BATCH_RC_SEG")
+    host = np.frombuffer(recs.cpu().numpy().tobytes(), dtype=_native.MATCH_DTYPE)
+    key = lambda r: sorted(zip(r["start"].tolist(), r["end"].tolist(), r["pattern_index"].tolist(),  # noqa: E731
+                               r["similarity"].view(np.uint32).tolist(), r["edits"].tolist()))
+    same = all(key(host[int(doc_off[d]):int(doc_off[d + 1])]) == key(p) for d, p in zip(idx, per_doc))
+    best_rule = min(rules, key=lambda r: float(np.median(p_ms[r])))
+    med = lambda v: float(np.median(v))  # noqa: E731
+    p_best = med(p_ms[best_rule])
+    b_doc = [m / len(docs) for m in b_ms]
+    return {"leg": "prefilter", "config": name, "bytes": len(data), "L": L, "docs": nd, "sample": len(docs),
+            "records": int(len(host)), "start_windows": windows,
+            "p_ms": {str(r): [round(x, 3) for x in v] for r, v in p_ms.items()}, "best_rule": best_rule,
+            "p_prefilter_ms": [round(x, 3) for x in pf_ms], "a_ms": [round(x, 3) for x in a_ms],
+            "c_ms": [round(x, 3) for x in c_ms], "b_sample_ms": [round(x, 2) for x in b_ms],
+            "p_us_per_doc": round(1e3 * p_best / nd, 4), "b_us_per_doc": [round(1e3 * x, 2) for x in b_doc],
+            "p_over_a": round(p_best / med(a_ms), 4), "p_over_c": round(p_best / med(c_ms), 4),
+            "p_spread_ms": round(max(p_ms[best_rule]) - min(p_ms[best_rule]), 3),
+            "a_spread_ms": round(max(a_ms) - min(a_ms), 3), "c_spread_ms": round(max(c_ms) - min(c_ms), 3),
+            "records_equal": bool(same),
+            "faster_than_a": bool(same and min(a_ms) - max(p_ms[best_rule]) > 0)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--c2-bytes", type=int, default=64 << 20)
@@ -268,7 +385,18 @@ def main():
                     help="a few calls of leg (a) (default) or (c) and nothing else (for rocprofv3)")
     ap.add_argument("--replace", action="store_true",
                     help="time fac_replace_batch against fac_search_batch and the per-document replace loop")
+    ap.add_argument("--prefilter", action="store_true",
+                    help="time fac_search_batch_prefiltered against the plain batch, the one-haystack pre-filtered "
+                         "search and the per-document Prefiltered loop (configs c2, c5, c5n; --pf-bytes each)")
+    ap.add_argument("--pf-bytes", type=int, default=64 << 20)
     args = ap.parse_args()
+    if args.prefilter:
+        for name in (args.configs if args.configs != ["c2", "c3"] else ["c2", "c5", "c5n"]):
+            for L in args.lengths:
+                res = run_prefilter(name, args.pf_bytes, L, args.sample, args.rounds, args.rules, args.profile_only)
+                if res is not None:
+                    print(json.dumps(res), flush=True)
+        return
     for name in args.configs:
         for L in args.lengths:
             if args.replace:
