@@ -597,6 +597,7 @@ struct DevMem {
   }
   int alloc(size_t bytes, std::string& err) {
     hipError_t he = hipSuccess;
+    if (p) fac::call_scratch_give(p, s);
     p = fac::call_scratch_take(std::max<size_t>(bytes, 16), s, &he);
     if (he != hipSuccess) {
       p = nullptr;
@@ -1139,6 +1140,68 @@ uint64_t fac_batch_grapheme_starts(const fac_batch* batch, uint64_t d, uint64_t*
   return n;
 }
 
+// The shared front of every batch call: the pre-filter where the reference's Prefiltered::search
+// would run it (prefilter.rs:151-155, 311-317), the search into a device buffer (grown and searched
+// again if it was too small) and the per-document apply. The kept records stay in HBM (`res`, inside
+// `raw`), grouped by document, with their CSR index in `d_doc`; nothing but counts visits the host.
+struct BatchKept {
+  DevMem raw, doff;
+  fac_match* res = nullptr;
+  uint64_t n_res = 0;
+  uint64_t* d_doc = nullptr;
+  explicit BatchKept(hipStream_t st) : raw(st), doff(st) {}
+};
+
+// d_doc_user: where the index goes instead of the call's own scratch (may be NULL)
+static int batch_kept(const fac::Engine& e, const fac::Batch& b, float threshold, int order, int overlap,
+                      const uint64_t* unique_ids, bool prefilter, hipStream_t st, uint64_t* d_doc_user, fac_stats* stats,
+                      BatchKept& k, std::string& err) {
+  const uint64_t nd = b.n_docs;
+  fac::BatchWindows pw;  // pre-filtered: every document's merged windows, found once
+  bool filtered = false;
+  if (int rc = batch_prefilter(e, b, threshold, prefilter, st, pw, filtered, stats, err)) return rc;
+  uint64_t cap = std::max<uint64_t>(4096, (filtered ? pw.windows : b.windows) / 64);
+  for (;;) {
+    if (int rc = k.raw.alloc(2 * cap * sizeof(fac_match), err)) return rc;
+    if (int rc = k.doff.alloc((nd + 1) * 8, err)) return rc;
+    fac::MatchSink sink;
+    sink.dev = static_cast<fac_match*>(k.raw.p);
+    sink.dev_cap = cap;
+    if (int rc = filtered ? fac::launch_search_batch_windows(e, b, pw, threshold, st, sink, stats, err)
+                          : fac::launch_search_batch(e, b, threshold, st, sink, stats, err))
+      return rc;
+    if (stats) stats->graphemes = b.windows;
+    if (sink.n > cap) {
+      cap = sink.n;
+      continue;
+    }
+    k.d_doc = d_doc_user ? d_doc_user : static_cast<uint64_t*>(k.doff.p);
+    return fac::apply_batch_device(e, sink.dev, sink.dev + cap, sink.n, b.d_offsets, nd, order, overlap, unique_ids, st,
+                                   k.d_doc, &k.res, &k.n_res, err);
+  }
+}
+
+// The records of a batch call (d_res, n of them, and their CSR index d_doc) to the caller: into
+// args->device_out, or a pinned host buffer handed out as *out; doc_offsets (host, may be NULL).
+static int deliver_records(const fac_batch_args* args, const fac_match* d_res, uint64_t n, const uint64_t* d_doc,
+                           uint64_t nd, hipStream_t st, fac_match** out, uint64_t* n_out, uint64_t* doc_offsets) {
+  std::string err;
+  fac::MatchSink fin;
+  fin.dev = static_cast<fac_match*>(args->device_out);
+  fin.dev_cap = args->device_cap;
+  if (int rc = fac::sink_append_device(fin, d_res, n, st, err)) {
+    fac::result_free(fin.pinned);
+    return fail(rc, err);
+  }
+  if ((doc_offsets && hipMemcpyAsync(doc_offsets, d_doc, (nd + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    fac::result_free(fin.pinned);
+    return fail(FAC_E_HIP, "copy of the batch's records failed");
+  }
+  if (fin.dev) return FAC_OK;
+  return hand_out(fin, out, n_out);
+}
+
 // The body of fac_search_batch and fac_search_batch_prefiltered (prefilter: take the pre-filtered
 // path where the reference's Prefiltered::search would, prefilter.rs:151-155, 311-317)
 static int search_batch_impl(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
@@ -1157,51 +1220,14 @@ static int search_batch_impl(const fac_engine* engine, const fac_batch* batch, c
   hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
   const uint64_t nd = b.n_docs;
   std::string err;
-  fac::BatchWindows pw;  // pre-filtered: every document's merged windows, found once
-  bool filtered = false;
-  if (int rc = batch_prefilter(e, b, args->threshold, prefilter, st, pw, filtered, stats, err)) return fail(rc, err);
-  // raw tagged records into a device buffer (grown and searched again if it was too small), then
-  // the per-document apply; nothing but counts visits the host
-  uint64_t cap = std::max<uint64_t>(4096, (filtered ? pw.windows : b.windows) / 64);
-  for (;;) {
-    DevMem raw(st), doff(st);
-    if (int rc = raw.alloc(2 * cap * sizeof(fac_match), err)) return fail(rc, err);
-    if (int rc = doff.alloc((nd + 1) * 8, err)) return fail(rc, err);
-    fac::MatchSink sink;
-    sink.dev = static_cast<fac_match*>(raw.p);
-    sink.dev_cap = cap;
-    if (int rc = filtered ? fac::launch_search_batch_windows(e, b, pw, args->threshold, st, sink, stats, err)
-                          : fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err))
-      return fail(rc, err);
-    if (stats) stats->graphemes = b.windows;
-    if (sink.n > cap) {
-      cap = sink.n;
-      continue;
-    }
-    fac_match* res = nullptr;
-    uint64_t n_res = 0;
-    uint64_t* d_doc = args->device_doc_offsets ? args->device_doc_offsets : static_cast<uint64_t*>(doff.p);
-    if (int rc = fac::apply_batch_device(e, sink.dev, sink.dev + cap, sink.n, b.d_offsets, nd, args->order, args->overlap,
-                                         args->unique_ids, st, d_doc, &res, &n_res, err))
-      return fail(rc, err);
-    *n_out = n_res;
-    if (args->device_out && n_res > args->device_cap)
-      return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*n_out = records needed)");
-    fac::MatchSink fin;
-    fin.dev = static_cast<fac_match*>(args->device_out);
-    fin.dev_cap = args->device_cap;
-    if (int rc = fac::sink_append_device(fin, res, n_res, st, err)) {
-      fac::result_free(fin.pinned);
-      return fail(rc, err);
-    }
-    if ((doc_offsets && hipMemcpyAsync(doc_offsets, d_doc, (nd + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      fac::result_free(fin.pinned);
-      return fail(FAC_E_HIP, "copy of the batch's records failed");
-    }
-    if (fin.dev) return FAC_OK;
-    return hand_out(fin, out, n_out);
-  }
+  BatchKept k(st);
+  if (int rc = batch_kept(e, b, args->threshold, args->order, args->overlap, args->unique_ids, prefilter, st,
+                          args->device_doc_offsets, stats, k, err))
+    return fail(rc, err);
+  *n_out = k.n_res;
+  if (args->device_out && k.n_res > args->device_cap)
+    return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*n_out = records needed)");
+  return deliver_records(args, k.res, k.n_res, k.d_doc, nd, st, out, n_out, doc_offsets);
 }
 
 int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
@@ -1295,6 +1321,28 @@ void fac_replacements_free(fac_replacements* replacements) {
   delete replacements;
 }
 
+// The output bytes of a batch call (d_out, total of them, and the n_docs + 1 offsets d_out_off) to
+// the caller: they are in args->device_out already, or go to a host buffer handed out as *out; the
+// offsets to args->device_out_offsets and out_offsets (host), where given.
+static int deliver_bytes(const fac_replace_args* args, const uint8_t* d_out, uint64_t total, const uint64_t* d_out_off,
+                         uint64_t nd, hipStream_t st, uint8_t** out, uint64_t* out_offsets) {
+  uint8_t* host = nullptr;
+  if (!args->device_out) {
+    host = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(total, 1)));
+    if (!host) return fail(FAC_E_OOM, "out of host memory");
+  }
+  if ((host && total && hipMemcpyAsync(host, d_out, total, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (args->device_out_offsets &&
+       hipMemcpyAsync(args->device_out_offsets, d_out_off, (nd + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+      (out_offsets && hipMemcpyAsync(out_offsets, d_out_off, (nd + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    std::free(host);
+    return fail(FAC_E_HIP, "copy of the batch's output failed");
+  }
+  if (host) *out = host;
+  return FAC_OK;
+}
+
 // The body of fac_replace_batch and fac_replace_batch_prefiltered (prefilter: as search_batch_impl)
 static int replace_batch_impl(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
                               const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
@@ -1320,62 +1368,26 @@ static int replace_batch_impl(const fac_engine* engine, const fac_batch* batch, 
   const int order = args->order == 0 ? 1 : args->order, overlap = args->overlap == 0 ? 1 : args->overlap;
   const uint64_t nd = b.n_docs;
   std::string err;
-  fac::BatchWindows pw;
-  bool filtered = false;
-  if (int rc = batch_prefilter(e, b, args->threshold, prefilter, st, pw, filtered, stats, err)) return fail(rc, err);
   // fac_search_batch's search and per-document apply, then the splice from the kept records in HBM
-  uint64_t cap = std::max<uint64_t>(4096, (filtered ? pw.windows : b.windows) / 64);
-  for (;;) {
-    DevMem raw(st), doff(st), obuf(st);
-    if (int rc = raw.alloc(2 * cap * sizeof(fac_match), err)) return fail(rc, err);
-    if (int rc = doff.alloc((nd + 1) * 8, err)) return fail(rc, err);
-    fac::MatchSink sink;
-    sink.dev = static_cast<fac_match*>(raw.p);
-    sink.dev_cap = cap;
-    if (int rc = filtered ? fac::launch_search_batch_windows(e, b, pw, args->threshold, st, sink, stats, err)
-                          : fac::launch_search_batch(e, b, args->threshold, st, sink, stats, err))
-      return fail(rc, err);
-    if (stats) stats->graphemes = b.windows;
-    if (sink.n > cap) {
-      cap = sink.n;
-      continue;
-    }
-    fac_match* res = nullptr;
-    uint64_t n_res = 0;
-    uint64_t* d_doc = static_cast<uint64_t*>(doff.p);
-    if (int rc = fac::apply_batch_device(e, sink.dev, sink.dev + cap, sink.n, b.d_offsets, nd, order, overlap,
-                                         args->unique_ids, st, d_doc, &res, &n_res, err))
-      return fail(rc, err);
-    fac::ReplacePlan plan;
-    if (int rc = fac::replace_plan_device(b, t, res, n_res, d_doc, st, plan, err)) return fail(rc, err);
-    *out_len = plan.total;
-    if (n_replaced) *n_replaced = plan.n_replaced;
-    if (plan.total >= (1ull << fac::kDocTagShift))
-      return fail(FAC_E_UNSUPPORTED, "the replaced batch would hold 2^40 bytes or more");
-    if (args->device_out && plan.total > args->device_cap)
-      return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*out_len = bytes needed)");
-    uint8_t* d_out = static_cast<uint8_t*>(args->device_out);
-    if (!d_out) {
-      if (int rc = obuf.alloc(plan.total, err)) return fail(rc, err);
-      d_out = static_cast<uint8_t*>(obuf.p);
-    }
-    if (int rc = fac::replace_copy_device(b, t, res, d_doc, plan, d_out, err)) return fail(rc, err);
-    uint8_t* host = nullptr;
-    if (!args->device_out) {
-      host = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(plan.total, 1)));
-      if (!host) return fail(FAC_E_OOM, "out of host memory");
-    }
-    if ((host && plan.total && hipMemcpyAsync(host, d_out, plan.total, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        (args->device_out_offsets &&
-         hipMemcpyAsync(args->device_out_offsets, plan.d_out_off, (nd + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
-        (out_offsets && hipMemcpyAsync(out_offsets, plan.d_out_off, (nd + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      std::free(host);
-      return fail(FAC_E_HIP, "copy of the replaced batch failed");
-    }
-    if (host) *out = host;
-    return FAC_OK;
+  BatchKept k(st);
+  if (int rc = batch_kept(e, b, args->threshold, order, overlap, args->unique_ids, prefilter, st, nullptr, stats, k, err))
+    return fail(rc, err);
+  DevMem obuf(st);
+  fac::ReplacePlan plan;
+  if (int rc = fac::replace_plan_device(b, t, k.res, k.n_res, k.d_doc, st, plan, err)) return fail(rc, err);
+  *out_len = plan.total;
+  if (n_replaced) *n_replaced = plan.n_replaced;
+  if (plan.total >= (1ull << fac::kDocTagShift))
+    return fail(FAC_E_UNSUPPORTED, "the replaced batch would hold 2^40 bytes or more");
+  if (args->device_out && plan.total > args->device_cap)
+    return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*out_len = bytes needed)");
+  uint8_t* d_out = static_cast<uint8_t*>(args->device_out);
+  if (!d_out) {
+    if (int rc = obuf.alloc(plan.total, err)) return fail(rc, err);
+    d_out = static_cast<uint8_t*>(obuf.p);
   }
+  if (int rc = fac::replace_copy_device(b, t, k.res, k.d_doc, plan, d_out, err)) return fail(rc, err);
+  return deliver_bytes(args, d_out, plan.total, plan.d_out_off, nd, st, out, out_offsets);
 }
 
 int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
@@ -1388,6 +1400,109 @@ int fac_replace_batch_prefiltered(const fac_engine* engine, const fac_batch* bat
                                   const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
                                   uint64_t* n_replaced, fac_stats* stats) {
   return replace_batch_impl(engine, batch, replacements, args, out, out_len, out_offsets, n_replaced, stats, true);
+}
+
+// ---- batched segmentation (fac.h "Batched segmentation"): search + apply, then the walk of
+// matches.rs:218-594 over the kept records in HBM
+
+// The body of fac_segment_batch and fac_segment_batch_prefiltered (prefilter: as search_batch_impl)
+static int segment_batch_impl(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args,
+                              fac_match** out, uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats, bool prefilter) {
+  if (!engine || !batch || !args || !n_out || (!out && !args->device_out)) return fail(FAC_E_INVALID, "NULL argument");
+  if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
+    return fail(FAC_E_INVALID, "bad order/overlap");
+  if (out) *out = nullptr;
+  *n_out = 0;
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
+  if (e.has_map && !b.h.ascii)
+    return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
+  // `segmented` (query.rs:46-64): the walk needs start order and disjoint spans
+  const int order = args->order == 0 ? 1 : args->order, overlap = args->overlap == 0 ? 1 : args->overlap;
+  const uint64_t nd = b.n_docs;
+  std::string err;
+  BatchKept k(st);
+  if (int rc = batch_kept(e, b, args->threshold, order, overlap, args->unique_ids, prefilter, st, nullptr, stats, k, err))
+    return fail(rc, err);
+  fac::SegmentPlan plan;
+  if (int rc = fac::segment_plan_device(b, fac::kSegmentRecords, k.res, k.d_doc, st, plan, err)) return fail(rc, err);
+  *n_out = plan.n_segs;
+  if (args->device_out && plan.n_segs > args->device_cap)
+    return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*n_out = segments needed)");
+  // (the caller's buffer may have any alignment: the segments are written to scratch and copied)
+  DevMem segs(st);
+  if (int rc = segs.alloc(plan.n_segs * sizeof(fac_match), err)) return fail(rc, err);
+  if (int rc = fac::segment_write_device(b, k.res, k.d_doc, plan, static_cast<fac_match*>(segs.p), err))
+    return fail(rc, err);
+  if (args->device_doc_offsets &&
+      hipMemcpyAsync(args->device_doc_offsets, plan.d_seg_off, (nd + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail(FAC_E_HIP, "copy of the batch's segment index failed");
+  return deliver_records(args, static_cast<fac_match*>(segs.p), plan.n_segs, plan.d_seg_off, nd, st, out, n_out,
+                         doc_offsets);
+}
+
+int fac_segment_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
+                      uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats) {
+  return segment_batch_impl(engine, batch, args, out, n_out, doc_offsets, stats, false);
+}
+
+int fac_segment_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args,
+                                  fac_match** out, uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats) {
+  return segment_batch_impl(engine, batch, args, out, n_out, doc_offsets, stats, true);
+}
+
+// The body of fac_render_batch and fac_render_batch_prefiltered (prefilter: as search_batch_impl)
+static int render_batch_impl(const fac_engine* engine, const fac_batch* batch, int32_t mode, const fac_replace_args* args,
+                             uint8_t** out, uint64_t* out_len, uint64_t* out_offsets, fac_stats* stats, bool prefilter) {
+  if (!engine || !batch || !args || !out_len || (!out && !args->device_out)) return fail(FAC_E_INVALID, "NULL argument");
+  if (mode != FAC_RENDER_STRIP_PREFIX && mode != FAC_RENDER_STRIP_SUFFIX && mode != FAC_RENDER_SEGMENT_TEXT)
+    return fail(FAC_E_INVALID, "bad render mode");
+  if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
+    return fail(FAC_E_INVALID, "bad order/overlap");
+  if (out) *out = nullptr;
+  *out_len = 0;
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
+  if (e.has_map && !b.h.ascii)
+    return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
+  const int order = args->order == 0 ? 1 : args->order, overlap = args->overlap == 0 ? 1 : args->overlap;
+  const uint64_t nd = b.n_docs;
+  std::string err;
+  BatchKept k(st);
+  if (int rc = batch_kept(e, b, args->threshold, order, overlap, args->unique_ids, prefilter, st, nullptr, stats, k, err))
+    return fail(rc, err);
+  DevMem obuf(st);
+  fac::SegmentPlan plan;
+  if (int rc = fac::segment_plan_device(b, mode, k.res, k.d_doc, st, plan, err)) return fail(rc, err);
+  *out_len = plan.total;
+  if (plan.total >= (1ull << fac::kDocTagShift))
+    return fail(FAC_E_UNSUPPORTED, "the rendered batch would hold 2^40 bytes or more");
+  if (args->device_out && plan.total > args->device_cap)
+    return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*out_len = bytes needed)");
+  uint8_t* d_out = static_cast<uint8_t*>(args->device_out);
+  if (!d_out) {
+    if (int rc = obuf.alloc(plan.total, err)) return fail(rc, err);
+    d_out = static_cast<uint8_t*>(obuf.p);
+  }
+  if (int rc = fac::render_copy_device(b, k.res, k.d_doc, plan, d_out, err)) return fail(rc, err);
+  return deliver_bytes(args, d_out, plan.total, plan.d_out_off, nd, st, out, out_offsets);
+}
+
+int fac_render_batch(const fac_engine* engine, const fac_batch* batch, int32_t mode, const fac_replace_args* args,
+                     uint8_t** out, uint64_t* out_len, uint64_t* out_offsets, fac_stats* stats) {
+  return render_batch_impl(engine, batch, mode, args, out, out_len, out_offsets, stats, false);
+}
+
+int fac_render_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, int32_t mode,
+                                 const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                                 fac_stats* stats) {
+  return render_batch_impl(engine, batch, mode, args, out, out_len, out_offsets, stats, true);
 }
 
 int fac_stream_open(const fac_engine* engine, float threshold, uint64_t window_bytes, fac_stream** out) {

@@ -542,6 +542,81 @@ int replace_plan_device(const Batch& b, const ReplaceTable& t, const fac_match* 
 int replace_copy_device(const Batch& b, const ReplaceTable& t, const fac_match* d_recs, const uint64_t* d_doc_off,
                         const ReplacePlan& plan, uint8_t* d_out, std::string& err);
 
+#if defined(__HIPCC__)
+// The 16 output bytes a lane of an output-stationary byte mover owns (replace_copy_kernel,
+// piece_copy_kernel), little-endian in two registers, filled run by run.
+struct Chunk16 {
+  uint64_t lo = 0, hi = 0;
+  uint32_t filled = 0;
+};
+// One byte, or `take` bytes of a run (they fit: filled + take <= 16).
+__device__ inline void chunk_put(Chunk16& c, uint64_t v) {
+  if (c.filled < 8) c.lo |= v << (8 * c.filled);
+  else c.hi |= v << (8 * (c.filled - 8));
+  ++c.filled;
+}
+__device__ inline void chunk_put(Chunk16& c, const uint8_t* __restrict__ src, uint32_t take) {
+  for (uint32_t t = 0; t < take; ++t) chunk_put(c, src[t]);
+}
+// The whole chunk from one run (filled == 0, 16 bytes readable at src): aligned words and byte
+// shifts (a misaligned source is the rule; the fifth word is read only when it holds one of the 16
+// bytes).
+__device__ inline void chunk_load16(Chunk16& c, const uint8_t* __restrict__ src) {
+  const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u);
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(src - a);
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = a ? w[4] : 0u;
+  const uint32_t o0 = __builtin_amdgcn_alignbyte(w1, w0, a), o1 = __builtin_amdgcn_alignbyte(w2, w1, a);
+  const uint32_t o2 = __builtin_amdgcn_alignbyte(w3, w2, a), o3 = __builtin_amdgcn_alignbyte(w4, w3, a);
+  c.lo = (uint64_t)o0 | ((uint64_t)o1 << 32);
+  c.hi = (uint64_t)o2 | ((uint64_t)o3 << 32);
+  c.filled = 16;
+}
+// One 16-byte store for a full chunk when `out` is 16-byte aligned (wide), byte stores otherwise.
+__device__ inline void chunk_store(const Chunk16& c, uint8_t* __restrict__ out, int wide) {
+  if (wide && c.filled == 16) {
+    *reinterpret_cast<uint4*>(out) =
+        make_uint4((uint32_t)c.lo, (uint32_t)(c.lo >> 32), (uint32_t)c.hi, (uint32_t)(c.hi >> 32));
+  } else {
+    for (uint32_t t = 0; t < c.filled; ++t) out[t] = (uint8_t)(t < 8 ? c.lo >> (8 * t) : c.hi >> (8 * (t - 8)));
+  }
+}
+#endif
+
+// segment_kernels.hip: the segmentation helpers of a batch (fac.h fac_segment_batch and
+// fac_render_batch; matches.rs:218-594 per document). The modes are fac.h's FAC_RENDER_*, and
+// kSegmentRecords for the segments themselves.
+constexpr int kRenderStripPrefix = 0, kRenderStripSuffix = 1, kRenderSegmentText = 2, kSegmentRecords = 3;
+constexpr uint32_t kSegmentTile = 4096;  // output bytes one workgroup of piece_copy_kernel owns
+// The plan of one call: the n_docs + 1 segment offsets (segment_text and the segments), the
+// n_docs + 1 output byte offsets (the render modes) and, for a strip, the global byte each
+// document's kept part starts at. Scratch comes from the stream's pool and goes back with the plan.
+struct SegmentPlan {
+  hipStream_t s = nullptr;
+  int mode = 0;
+  void* mem = nullptr;
+  void* mem_pieces = nullptr;  // segment_text: one piece per segment (render_copy_device)
+  uint64_t* d_seg_off = nullptr;
+  uint64_t* d_out_off = nullptr;
+  uint64_t* d_src = nullptr;
+  uint64_t n_segs = 0;  // segments of the whole batch
+  uint64_t total = 0;   // output bytes of the whole batch
+  ~SegmentPlan() {
+    if (mem_pieces) call_scratch_give(mem_pieces, s);
+    if (mem) call_scratch_give(mem, s);
+  }
+};
+// d_recs / d_doc_off: apply_batch_device's result, as for replace_plan_device. Walks every
+// document's records and scans the counts and lengths the mode needs on s; synchronises once to
+// read n_segs and total back.
+int segment_plan_device(const Batch& b, int mode, const fac_match* d_recs, const uint64_t* d_doc_off, hipStream_t s,
+                        SegmentPlan& plan, std::string& err);
+// Writes the plan.n_segs segments to d_out, 8-byte aligned (asynchronous on plan.s).
+int segment_write_device(const Batch& b, const fac_match* d_recs, const uint64_t* d_doc_off, const SegmentPlan& plan,
+                         fac_match* d_out, std::string& err);
+// Writes the plan.total output bytes of a render mode to d_out (asynchronous on plan.s).
+int render_copy_device(const Batch& b, const fac_match* d_recs, const uint64_t* d_doc_off, SegmentPlan& plan,
+                       uint8_t* d_out, std::string& err);
+
 // Where a search delivers its records: a host vector (internal callers), a pooled pinned host
 // buffer handed to the C ABI caller (fac_search_staged / fac_search_raw: no page faults on the
 // D2H, result_alloc below), or the caller's device buffer (fac_search_staged_device: records stay

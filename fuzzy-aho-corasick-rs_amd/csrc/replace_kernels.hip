@@ -121,8 +121,7 @@ __global__ __launch_bounds__(kThreads) void replace_copy_kernel(
     }
   }
 
-  uint64_t w_lo = 0, w_hi = 0;  // the lane's 16 bytes, little-endian
-  uint32_t filled = 0;
+  Chunk16 c;  // the lane's 16 bytes
   for (;;) {
     const uint8_t* src = utf8;
     uint64_t rl = 0;
@@ -159,27 +158,10 @@ __global__ __launch_bounds__(kThreads) void replace_copy_kernel(
       skip -= t;
     }
     if (rl) {
-      const uint32_t take = rl < (uint64_t)(n - filled) ? (uint32_t)rl : n - filled;
-      if (take == kChunk) {
-        // the whole chunk from one run: aligned words and byte shifts (a misaligned source is the
-        // rule; the fifth word is read only when it holds one of the 16 bytes)
-        const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u);
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(src - a);
-        const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = a ? w[4] : 0u;
-        const uint32_t o0 = __builtin_amdgcn_alignbyte(w1, w0, a), o1 = __builtin_amdgcn_alignbyte(w2, w1, a);
-        const uint32_t o2 = __builtin_amdgcn_alignbyte(w3, w2, a), o3 = __builtin_amdgcn_alignbyte(w4, w3, a);
-        w_lo = (uint64_t)o0 | ((uint64_t)o1 << 32);
-        w_hi = (uint64_t)o2 | ((uint64_t)o3 << 32);
-      } else {
-        for (uint32_t t = 0; t < take; ++t) {
-          const uint64_t v = src[t];
-          const uint32_t at = filled + t;
-          if (at < 8) w_lo |= v << (8 * at);
-          else w_hi |= v << (8 * (at - 8));
-        }
-      }
-      filled += take;
-      if (filled == n) break;
+      const uint32_t take = rl < (uint64_t)(n - c.filled) ? (uint32_t)rl : n - c.filled;
+      if (take == kChunk) chunk_load16(c, src);
+      else chunk_put(c, src, take);
+      if (c.filled == n) break;
     }
     // next run
     if (piece) {
@@ -197,12 +179,7 @@ __global__ __launch_bounds__(kThreads) void replace_copy_kernel(
     }
   }
 
-  if (wide && filled == kChunk) {
-    *reinterpret_cast<uint4*>(out + g) =
-        make_uint4((uint32_t)w_lo, (uint32_t)(w_lo >> 32), (uint32_t)w_hi, (uint32_t)(w_hi >> 32));
-  } else {
-    for (uint32_t t = 0; t < filled; ++t) out[g + t] = (uint8_t)(t < 8 ? w_lo >> (8 * t) : w_hi >> (8 * (t - 8)));
-  }
+  chunk_store(c, out + g, wide);
 }
 
 #define RP_TRY(x)                                              \

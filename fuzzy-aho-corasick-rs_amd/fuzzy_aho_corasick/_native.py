@@ -103,6 +103,11 @@ class fac_replace_args(ctypes.Structure):
 
 
 REPLACE_TILE = 4096  # output bytes one workgroup of the splice's copy kernel owns (kReplaceTile)
+SEGMENT_TILE = 4096  # output bytes one workgroup of the render modes' copy kernel owns (kSegmentTile)
+FAC_UNMATCHED = 0xFFFFFFFF  # pattern_index of an unmatched segment (fac_segment_batch)
+FAC_RENDER_STRIP_PREFIX = 0
+FAC_RENDER_STRIP_SUFFIX = 1
+FAC_RENDER_SEGMENT_TEXT = 2
 
 assert ctypes.sizeof(fac_match) == 32
 
@@ -210,6 +215,14 @@ SIGNATURES = {
                                          _P(_P(ctypes.c_uint8)), _u64p, _u64p, _u64p, _P(fac_stats)]),
     "fac_replace_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_replace_args),
                                                      _P(_P(ctypes.c_uint8)), _u64p, _u64p, _u64p, _P(fac_stats)]),
+    "fac_segment_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_batch_args), _P(_P(fac_match)), _u64p,
+                                         _u64p, _P(fac_stats)]),
+    "fac_segment_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_batch_args), _P(_P(fac_match)),
+                                                     _u64p, _u64p, _P(fac_stats)]),
+    "fac_render_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_int32, _P(fac_replace_args),
+                                        _P(_P(ctypes.c_uint8)), _u64p, _u64p, _P(fac_stats)]),
+    "fac_render_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_int32, _P(fac_replace_args),
+                                                    _P(_P(ctypes.c_uint8)), _u64p, _u64p, _P(fac_stats)]),
     "fac_edge_order": (None, [ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "fac_diag_beam_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),

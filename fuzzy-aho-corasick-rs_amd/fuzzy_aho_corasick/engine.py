@@ -11,7 +11,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 from . import _native
 
 _TIMING = bool(os.environ.get("FAC_TIMING"))  # diagnostics: host-side phase times
-from .matches import FuzzyMatch, FuzzyMatches
+from .matches import FuzzyMatch, FuzzyMatches, Segment, UnmatchedSegment
 from .structs import (DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge, Order, Overlap,
                       Pattern, SearchError, SearchOptions, Similarity, UnsupportedConfiguration, f32)
 
@@ -389,6 +389,29 @@ class FuzzyAhoCorasick:
         out, off = StagedBatch(self, data, offsets).replace_bytes(table, opts)
         return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
+    # -- the other segmentation helpers of a whole batch (fac_render_batch, fac_segment_batch): each is
+    # one device call; whitespace is Rust's char::is_whitespace (DESIGN.md 6a "Batched segmentation")
+    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        """`[self.strip_prefix(t, opts) for t in texts]` as one call."""
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_PREFIX, opts, False)
+
+    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        """`[self.strip_suffix(t, opts) for t in texts]` as one call."""
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, False)
+
+    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        """`[self.segment_text(t, opts) for t in texts]` as one call."""
+        return _render_batch(self, texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, False)
+
+    def segment_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[Segment]]:
+        """`[list(self.segment_iter(t, opts)) for t in texts]` as one call."""
+        return _segment_batch(self, texts, opts, False)
+
+    def split_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[str]]:
+        """`[list(self.split(t, opts)) for t in texts]` as one call."""
+        return [[s.unmatched().text for s in segs if s.unmatched() is not None]
+                for segs in _segment_batch(self, texts, opts, False)]
+
 
 class Prefiltered:
     """prefilter.rs:57-156"""
@@ -457,8 +480,84 @@ class Prefiltered:
         return out
 
 
+    def _segmented(self, haystack: str, opts: SearchOptions) -> FuzzyMatches:
+        order = Order.Default if opts.order_ == Order.Unsorted else opts.order_
+        overlap = Overlap.NonOverlapping if opts.overlap_ == Overlap.Keep else opts.overlap_
+        return self.engine._search_ranked(haystack, opts.threshold_, order, overlap, prefilter=True)
+
+    def _rendered(self, texts, mode: int, opts: SearchOptions, host) -> List[str]:
+        """The ASCII texts as one pre-filtered batch (fac_render_batch_prefiltered), the others
+        through `search` and the host method `host`, results in input order."""
+        texts = list(texts)
+        enc = [t.encode("utf-8") for t in texts]
+        out = [None] * len(texts)
+        idx = self._batch_parts(enc)
+        if idx:
+            for d, r in zip(idx, _render_batch(self.engine, [texts[d] for d in idx], mode, opts, True)):
+                out[d] = r
+        for d, t in enumerate(texts):
+            if out[d] is None:
+                out[d] = host(self._segmented(t, opts))
+        return out
+
+    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_STRIP_PREFIX, opts, lambda ms: ms.strip_prefix())
+
+    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, lambda ms: ms.strip_suffix())
+
+    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, lambda ms: ms.segment_text())
+
+    def segment_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[Segment]]:
+        """The ASCII texts as one pre-filtered batch (fac_segment_batch_prefiltered), the others
+        through `search` and the host's segment_iter, results in input order."""
+        texts = list(texts)
+        enc = [t.encode("utf-8") for t in texts]
+        out = [None] * len(texts)
+        idx = self._batch_parts(enc)
+        if idx:
+            for d, segs in zip(idx, _segment_batch(self.engine, [texts[d] for d in idx], opts, True)):
+                out[d] = segs
+        for d, t in enumerate(texts):
+            if out[d] is None:
+                out[d] = list(self._segmented(t, opts).segment_iter())
+        return out
+
+    def split_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[str]]:
+        return [[s.unmatched().text for s in segs if s.unmatched() is not None]
+                for segs in self.segment_batch(texts, opts)]
+
+
 def _as_text(r):
     return bytes(r).decode("utf-8") if isinstance(r, (bytes, bytearray, memoryview)) else r
+
+
+def _render_batch(engine: "FuzzyAhoCorasick", texts, mode: int, opts: SearchOptions, prefilter: bool) -> List[str]:
+    enc = [t.encode("utf-8") for t in texts]
+    data, offsets = batch_offsets(enc)
+    out, off = StagedBatch(engine, data, offsets).render_bytes(mode, opts, prefilter=prefilter)
+    return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
+
+
+def _segment_batch(engine: "FuzzyAhoCorasick", texts, opts: SearchOptions, prefilter: bool) -> List[List[Segment]]:
+    enc = [t.encode("utf-8") for t in texts]
+    data, offsets = batch_offsets(enc)
+    recs, doc_off = StagedBatch(engine, data, offsets).segment_records(opts, prefilter=prefilter)
+    out = []
+    for d, raw in enumerate(enc):
+        segs = []
+        for r in recs[int(doc_off[d]):int(doc_off[d + 1])]:
+            s, e, p = int(r["start"]), int(r["end"]), int(r["pattern_index"])
+            text = raw[s:e].decode("utf-8")
+            if p == _native.FAC_UNMATCHED:
+                segs.append(Segment(unmatched=UnmatchedSegment(s, e, text)))
+            else:
+                segs.append(Segment(matched=FuzzyMatch(int(r["insertions"]), int(r["deletions"]), int(r["substitutions"]),
+                                                       int(r["swaps"]), int(r["edits"]), p, engine.patterns_[p], s, e,
+                                                       float(r["similarity"]), text)))
+        out.append(segs)
+    return out
 
 
 def prefilter_windows(engine: "FuzzyAhoCorasick", haystack: str, threshold: float):
@@ -926,6 +1025,81 @@ class StagedBatch:
         if out is not None:
             return out[: n.value * _native.REC_BYTES], doc_off
         return _native.take_records(ptr, n.value), doc_off
+
+    def segment_records(self, opts: SearchOptions = None, out=None, stream=None, stats=None, doc_offsets_out=None,
+                        prefilter: bool = False):
+        """fac_segment_batch (`prefilter`: fac_segment_batch_prefiltered): (segments, doc_offsets), the
+        crate's engine.segment_iter(doc_d, opts) of every document (options normalised as
+        `segmented`, query.rs:46-64). Segments (MATCH_DTYPE) are grouped by document, offsets relative
+        to the segment's own document, and tile it; a matched segment is the kept record, an unmatched
+        one has pattern_index == _native.FAC_UNMATCHED. `out`, `doc_offsets_out` and the DeviceError
+        with `.needed` segments are search_records'."""
+        import numpy as np
+        opts = opts or SearchOptions()
+        a = self._args(opts, stream)
+        doc_off = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        ptr = ctypes.POINTER(_native.fac_match)()
+        if out is not None:
+            a.device_out = out.data_ptr()
+            a.device_cap = out.numel() // _native.REC_BYTES
+        if doc_offsets_out is not None:
+            if doc_offsets_out.numel() < self.n_docs + 1 or doc_offsets_out.element_size() != 8:
+                raise ValueError("doc_offsets_out needs n_docs + 1 64-bit entries")
+            a.device_doc_offsets = doc_offsets_out.data_ptr()
+        fn = _native.lib.fac_segment_batch_prefiltered if prefilter else _native.lib.fac_segment_batch
+        rc = fn(self.engine._h, self._h, ctypes.byref(a), None if out is not None else ctypes.byref(ptr), ctypes.byref(n),
+                doc_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(stats) if stats is not None else None)
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed = int(n.value)
+                raise
+        if out is not None:
+            return out[: n.value * _native.REC_BYTES], doc_off
+        return _native.take_records(ptr, n.value), doc_off
+
+    def render_bytes(self, mode: int, opts: SearchOptions = None, out=None, offsets_out=None, stream=None, stats=None,
+                     prefilter: bool = False):
+        """fac_render_batch (`prefilter`: fac_render_batch_prefiltered): (bytes, offsets). Output
+        document d is bytes[offsets[d]:offsets[d + 1]], the crate's engine.strip_prefix / strip_suffix /
+        segment_text(doc_d, opts) for mode _native.FAC_RENDER_STRIP_PREFIX / _STRIP_SUFFIX /
+        _SEGMENT_TEXT. `out`, `offsets_out` and the DeviceError with `.needed` bytes are replace_bytes'."""
+        import numpy as np
+        opts = opts or SearchOptions()
+        a = _native.fac_replace_args()
+        a.threshold = f32(opts.threshold_)
+        a.order = opts.order_.value
+        a.overlap = opts.overlap_.value
+        a.unique_ids = self.engine._unique_ids()
+        a.stream = stream or None
+        offsets = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        ptr = ctypes.POINTER(ctypes.c_uint8)()
+        if out is not None:
+            a.device_out = out.data_ptr()
+            a.device_cap = out.numel() * out.element_size()
+        if offsets_out is not None:
+            if offsets_out.numel() < self.n_docs + 1 or offsets_out.element_size() != 8:
+                raise ValueError("offsets_out needs n_docs + 1 64-bit entries")
+            a.device_out_offsets = offsets_out.data_ptr()
+        fn = _native.lib.fac_render_batch_prefiltered if prefilter else _native.lib.fac_render_batch
+        rc = fn(self.engine._h, self._h, int(mode), ctypes.byref(a), None if out is not None else ctypes.byref(ptr),
+                ctypes.byref(n), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                ctypes.byref(stats) if stats is not None else None)
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed = int(n.value)
+                raise
+        if out is not None:
+            return out[: n.value], offsets
+        try:
+            return ctypes.string_at(ptr, n.value), offsets
+        finally:
+            _native.lib.fac_buffer_free(ptr)
 
     def prefilter_windows(self, threshold: float, stream=None):
         """Diagnostics (fac_batch_prefilter_windows): the merged bitap windows of every document as

@@ -327,9 +327,11 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  * start / end while it is inside the library; the tag is cleared before records leave it), and no
  * engine with multi-character mappings when some document is not ASCII. Auto-beam engines read the
  * segment descriptors back and run the per-segment auto-beam loop of fac_search_staged on the host.
- * Batched replace is provided (fac_replace_batch below), and both calls have a pre-filtered form
- * for all-ASCII batches (fac_search_batch_prefiltered, fac_replace_batch_prefiltered below).
- * Batched strip_*, split and segment_* and multi-GPU batches are not provided.
+ * Batched replace is provided (fac_replace_batch below), and so are the other segmentation helpers:
+ * segment_iter and split (fac_segment_batch), strip_prefix, strip_suffix and segment_text
+ * (fac_render_batch). Every one of these calls has a pre-filtered form for all-ASCII batches
+ * (fac_search_batch_prefiltered, fac_replace_batch_prefiltered, fac_segment_batch_prefiltered,
+ * fac_render_batch_prefiltered below). Multi-GPU batches are not provided.
  *
  * Limits of the pre-filtered forms: where the filter runs, the batch must be all ASCII -- one
  * non-ASCII document gives FAC_E_UNSUPPORTED with nothing written (a non-ASCII document's symbol
@@ -468,6 +470,68 @@ int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fa
 int fac_replace_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
                                   const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
                                   uint64_t* n_replaced, fac_stats* stats);
+
+/* ---- Batched segmentation: segment_iter, split, strip_prefix, strip_suffix and segment_text
+ * (query.rs:98-170, matches.rs:218-594) of every document of a staged batch, walked on the device.
+ *
+ * The options are normalised as `segmented` does (query.rs:46-64: 0 Unsorted is taken as 1 Default,
+ * 0 Keep as 1 NonOverlapping; NonOverlappingUnique keeps its per-document used-pattern set), the
+ * batch is searched and ranked as fac_search_batch does, and each document's kept records are
+ * walked in the order fac_search_batch returns them -- by start, records of equal start in
+ * acceptance order, as in fac_replace_batch -- with the loop of segment_iter (matches.rs:526-553):
+ * last = 0; a record with start >= last emits Unmatched[last, start) if start > last, then
+ * Matched(record), and sets last = end; a record with start < last is dropped; Unmatched[last, len)
+ * ends the document if last < len. The segments tile [0, len). An unmatched segment is never empty;
+ * a matched one is empty where the record's span is.
+ *
+ * A segment is a fac_match: a matched segment is the kept record verbatim, an unmatched one has its
+ * start / end, pattern_index = FAC_UNMATCHED, similarity 0 and all counts 0. split (matches.rs:
+ * 344-354) is the unmatched segments, in order. */
+#define FAC_UNMATCHED 0xFFFFFFFFu
+
+/* Segments grouped by document, offsets relative to the segment's own document; doc_offsets is the
+ * CSR index into the segments. Arguments, contract, errors and limits are fac_search_batch's, with
+ * device_out / device_cap counting segments, device_doc_offsets receiving the segment index, and
+ * FAC_E_OUTPUT_CAPACITY (nothing written) reporting the segments needed in *n_out. */
+int fac_segment_batch(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args, fac_match** out,
+                      uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats);
+
+/* fac_segment_batch over fac_search_batch_prefiltered's records; fallback and limits as that call. */
+int fac_segment_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args,
+                                  fac_match** out, uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats);
+
+/* The helpers that return a String, per document over the segments above:
+ *   FAC_RENDER_STRIP_PREFIX  strip_prefix (matches.rs:218-245): doc[a..], a = the byte of the first
+ *                            non-whitespace character of the first unmatched segment that has one;
+ *                            empty if no unmatched segment has one.
+ *   FAC_RENDER_STRIP_SUFFIX  strip_suffix (matches.rs:276-307): doc[..b], b = the end of the last
+ *                            non-whitespace character of the last unmatched segment that has one;
+ *                            empty if none has.
+ *   FAC_RENDER_SEGMENT_TEXT  segment_text (matches.rs:566-594): the segments joined, with a U+0020
+ *                            before a matched segment that follows a matched one or a result that
+ *                            is not empty and does not end in U+0020 or U+0009, and before an
+ *                            unmatched segment that follows a matched one unless it starts with one
+ *                            of , . ? ! ; : U+2014 - U+2026.
+ * Whitespace is Rust's char::is_whitespace (the Unicode White_Space property: U+0009-U+000D, U+0020,
+ * U+0085, U+00A0, U+1680, U+2000-U+200A, U+2028, U+2029, U+202F, U+205F, U+3000); whitespace inside a
+ * matched segment does not count. */
+#define FAC_RENDER_STRIP_PREFIX 0
+#define FAC_RENDER_STRIP_SUFFIX 1
+#define FAC_RENDER_SEGMENT_TEXT 2
+
+/* The output contract is fac_replace_batch's: document d is bytes [out_offsets[d], out_offsets[d+1])
+ * of the result, on the host (*out, fac_buffer_free) or in args->device_out, with
+ * args->device_out_offsets honoured; *out_len is the byte count either way; FAC_E_OUTPUT_CAPACITY:
+ * device_cap is too small, *out_len holds the bytes needed and nothing was written. The output is
+ * valid UTF-8. FAC_E_INVALID for a bad mode, FAC_E_UNSUPPORTED (never a partial result) for an output
+ * of 2^40 bytes or more; errors and limits otherwise as fac_search_batch. */
+int fac_render_batch(const fac_engine* engine, const fac_batch* batch, int32_t mode, const fac_replace_args* args,
+                     uint8_t** out, uint64_t* out_len, uint64_t* out_offsets, fac_stats* stats);
+
+/* fac_render_batch over fac_search_batch_prefiltered's records; fallback and limits as that call. */
+int fac_render_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, int32_t mode,
+                                 const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
+                                 fac_stats* stats);
 
 /* Streaming search (stream.rs:77-297): feed the input in the reader's read() pieces; windows
  * of `window_bytes` (0 = the crate's 256 KiB) are cut, searched (sorted + non-overlapping) and

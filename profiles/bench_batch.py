@@ -33,6 +33,15 @@ c5's engine on fresh filler words with no planted match):
 
   The legs alternate; "records_equal" compares (p)'s records of the sample with (b)'s.
 
+With --segment the legs are (DESIGN.md §6a "Batched segmentation"):
+
+  (s)  one fac_render_batch call per mode (strip_prefix, strip_suffix, segment_text) and one
+       fac_segment_batch call, output and offsets left in HBM, device events,
+  (a') fac_search_batch with the same normalised options on the same batch: the cost floor,
+  (r)  fac_replace_batch with an all-keep table: the same bytes moved by the splice,
+  (b') the per-document loops engine.strip_prefix(doc, opts), strip_suffix, segment_text and
+       list(engine.segment_iter(doc, opts)) over the fixed sample, host wall clock.
+
 Staging is reported in ms per GiB: the batch stager against fac_haystack_stage_device on the same
 bytes. One JSON line per configuration; "gate" is true when (a) beats (b) per document by more than
 (b)'s own spread and (a)'s records for the sample equal (b)'s.
@@ -266,6 +275,91 @@ def run_replace(name, nbytes, L, sample, rounds, profile_only):
             "bytes_equal": bool(same), "gate": bool(same and min(b_doc) - r_doc > max(b_doc) - min(b_doc))}
 
 
+def run_segment(name, nbytes, L, sample, rounds):
+    w, engine = workload(name, nbytes)
+    data = w.haystack
+    off = cut_documents(data, L)
+    nd = len(off) - 1
+    dev = torch.device("cuda", engine.device)
+    t_data = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
+    t_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    sh = stream.cuda_stream
+    opts = SearchOptions().threshold(w.threshold)  # normalised by the calls: Default + NonOverlapping
+    opts.order_, opts.overlap_ = Order.Default, Overlap.NonOverlapping
+    table = ReplacementTable(engine, [None] * len(w.patterns))  # all keep: the output is the input
+    bufs = {"rec": torch.empty(max(1 << 16, len(data) // 16) * 32, dtype=torch.uint8, device=dev),
+            "seg": torch.empty(max(1 << 16, len(data) // 8) * 32, dtype=torch.uint8, device=dev),
+            "out": torch.empty(2 * len(data) + (1 << 20), dtype=torch.uint8, device=dev)}
+    t_out_off = torch.empty(nd + 1, dtype=torch.int64, device=dev)
+    sb = StagedBatch.from_device(engine, t_data.data_ptr(), t_off.data_ptr(), nd, len(data), stream=sh)
+
+    def grown(key, unit, call):
+        while True:
+            try:
+                return call(bufs[key])
+            except Exception as ex:  # FAC_E_OUTPUT_CAPACITY: grow and run again
+                need = getattr(ex, "needed", 0)
+                if not need:
+                    raise
+                bufs[key] = torch.empty(int(need * 1.1 + 1024) * unit, dtype=torch.uint8, device=dev)
+
+    modes = {"strip_prefix": _native.FAC_RENDER_STRIP_PREFIX, "strip_suffix": _native.FAC_RENDER_STRIP_SUFFIX,
+             "segment_text": _native.FAC_RENDER_SEGMENT_TEXT}
+    legs = {k: (lambda m=m: grown("out", 1, lambda o: sb.render_bytes(m, opts, out=o, offsets_out=t_out_off, stream=sh)))
+            for k, m in modes.items()}
+    legs["segments"] = lambda: grown("seg", 32, lambda o: sb.segment_records(opts, out=o, doc_offsets_out=t_out_off,
+                                                                             stream=sh))
+    legs["search"] = lambda: grown("rec", 32, lambda o: sb.search_records(opts, out=o, stream=sh))
+    legs["replace_keep"] = lambda: grown("out", 1, lambda o: sb.replace_bytes(table, opts, out=o, offsets_out=t_out_off,
+                                                                              stream=sh))
+    loops = {"strip_prefix": lambda d: engine.strip_prefix(d, opts), "strip_suffix": lambda d: engine.strip_suffix(d, opts),
+             "segment_text": lambda d: engine.segment_text(d, opts),
+             "segments": lambda d: list(engine.segment_iter(d, opts))}
+    for _ in range(2):  # warm-up: buffers, tables, the output sizes
+        for fn in legs.values():
+            fn()
+    idx = np.unique(np.linspace(0, nd - 1, min(sample, nd)).astype(np.int64))
+    docs = [data[int(off[d]):int(off[d + 1])].decode("utf-8") for d in idx]
+    for d in docs[:50]:
+        loops["segment_text"](d)
+    ms = {k: [] for k in legs}
+    b_ms = {k: [] for k in loops}
+    sizes, same = {}, {}
+    for rnd in range(rounds):
+        for k, fn in legs.items():  # the legs alternate
+            t, (out, out_off) = timed(stream, fn)
+            ms[k].append(t)
+            sizes[k] = int(out.numel()) // (32 if k in ("segments", "search") else 1)
+        for k, fn in loops.items():
+            t0 = time.perf_counter()
+            per_doc = [fn(d) for d in docs]
+            b_ms[k].append(1e3 * (time.perf_counter() - t0))
+            if rnd == 0:  # the batch's answer for the sample against the loop's
+                out, out_off = legs[k]()
+                if k == "segments":
+                    host = np.frombuffer(out.cpu().numpy().tobytes(), dtype=_native.MATCH_DTYPE)
+                    same[k] = all([(int(r["start"]), int(r["end"])) for r in host[int(out_off[d]):int(out_off[d + 1])]] ==
+                                  [(sg.matched().start, sg.matched().end) if sg.matched() is not None else
+                                   (sg.unmatched().start, sg.unmatched().end) for sg in p] for d, p in zip(idx, per_doc))
+                else:
+                    host = out.cpu().numpy().tobytes()
+                    same[k] = all(host[int(out_off[d]):int(out_off[d + 1])] == p.encode("utf-8")
+                                  for d, p in zip(idx, per_doc))
+    med = lambda v: float(np.median(v))  # noqa: E731
+    spread = lambda v: max(v) - min(v)  # noqa: E731
+    res = {"leg": "segment", "config": name, "bytes": len(data), "L": L, "docs": nd, "sample": len(docs), "sizes": sizes,
+           "ms": {k: [round(x, 3) for x in v] for k, v in ms.items()},
+           "b_sample_ms": {k: [round(x, 2) for x in v] for k, v in b_ms.items()}, "equal": same}
+    for k in loops:
+        res[k + "_us_per_doc"] = round(1e3 * med(ms[k]) / nd, 4)
+        res[k + "_loop_us_per_doc"] = round(1e3 * med(b_ms[k]) / len(docs), 2)
+        res[k + "_over_search"] = round(med(ms[k]) / med(ms["search"]), 4)
+        res[k + "_minus_replace_keep_ms"] = round(med(ms[k]) - med(ms["replace_keep"]), 3)
+    res["spread_ms"] = {k: round(spread(v), 3) for k, v in ms.items()}
+    return res
+
+
 def prefilter_workload(name, nbytes):
     """c2 / c5 as workloads.config; c5n: c5's patterns and threshold over fresh filler words alone."""
     if name != "c5n":
@@ -389,6 +483,9 @@ def main():
                     help="time fac_search_batch_prefiltered against the plain batch, the one-haystack pre-filtered "
                          "search and the per-document Prefiltered loop (configs c2, c5, c5n; --pf-bytes each)")
     ap.add_argument("--pf-bytes", type=int, default=64 << 20)
+    ap.add_argument("--segment", action="store_true",
+                    help="time fac_render_batch (each mode) and fac_segment_batch against fac_search_batch, the "
+                         "all-keep fac_replace_batch and the per-document loops")
     args = ap.parse_args()
     if args.prefilter:
         for name in (args.configs if args.configs != ["c2", "c3"] else ["c2", "c5", "c5n"]):
@@ -399,6 +496,10 @@ def main():
         return
     for name in args.configs:
         for L in args.lengths:
+            if args.segment:
+                res = run_segment(name, args.c2_bytes if name == "c2" else args.c3_bytes, L, args.sample, args.rounds)
+                print(json.dumps(res), flush=True)
+                continue
             if args.replace:
                 res = run_replace(name, args.c2_bytes if name == "c2" else args.c3_bytes, L, args.sample, args.rounds,
                                   args.profile_only)
