@@ -1271,8 +1271,10 @@ int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* b
 
 // ---- batched replace (fac.h "Batched replace"): the table, then search + apply + splice
 
-int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
-                            const uint8_t* keep, uint64_t n_patterns, fac_replacements** out) {
+// insert_at NULL: fac_replacements_create
+int fac_replacements_create_templates(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
+                                      const uint8_t* keep, const uint64_t* insert_at, uint64_t n_patterns,
+                                      fac_replacements** out) {
   if (!engine || !out || !offsets) return fail(FAC_E_INVALID, "NULL argument");
   *out = nullptr;
   const fac::Engine& e = engine->e;
@@ -1284,6 +1286,7 @@ int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const
   if (bytes && !utf8) return fail(FAC_E_INVALID, "NULL argument");
   if (bytes >= (1ull << 32)) return fail(FAC_E_UNSUPPORTED, "a replacement table holds fewer than 2^32 bytes");
   std::vector<uint2> tab(std::max<uint64_t>(n_patterns, 1), make_uint2(0, 0));
+  std::vector<uint32_t> ins;  // filled only once a template entry is met
   for (uint64_t p = 0; p < n_patterns; ++p) {
     const uint64_t b = offsets[p], len = offsets[p + 1] - b;
     if (keep && keep[p]) {
@@ -1292,6 +1295,14 @@ int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const
     }
     if (!fac::utf8_valid(utf8 + b, len)) return fail(FAC_E_INVALID, "a replacement is not valid UTF-8");
     tab[p] = make_uint2((uint32_t)b, (uint32_t)len);
+    if (insert_at && insert_at[p] != FAC_NO_INSERT) {
+      const uint64_t k = insert_at[p];
+      if (k > len) return fail(FAC_E_INVALID, "a template's insert position lies behind its replacement");
+      if (k < len && (utf8[b + k] & 0xC0) == 0x80)
+        return fail(FAC_E_INVALID, "a template's insert position lies inside a character");
+      if (ins.empty()) ins.assign(tab.size(), fac::kReplaceNoInsert);
+      ins[p] = (uint32_t)k;
+    }
   }
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
   fac_replacements* fr = new (std::nothrow) fac_replacements();
@@ -1300,12 +1311,14 @@ int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const
   t.device = e.device;
   t.n_patterns = n_patterns;
   if (hipMalloc((void**)&t.d_tab, tab.size() * sizeof(uint2)) != hipSuccess ||
-      hipMalloc((void**)&t.d_bytes, std::max<uint64_t>(bytes, 16)) != hipSuccess) {
+      hipMalloc((void**)&t.d_bytes, std::max<uint64_t>(bytes, 16)) != hipSuccess ||
+      (!ins.empty() && hipMalloc((void**)&t.d_ins, ins.size() * sizeof(uint32_t)) != hipSuccess)) {
     fac_replacements_free(fr);
     return fail(FAC_E_OOM, "hipMalloc of the replacement table failed");
   }
   if (hipMemcpy(t.d_tab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess ||
-      (bytes && hipMemcpy(t.d_bytes, utf8, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+      (bytes && hipMemcpy(t.d_bytes, utf8, bytes, hipMemcpyHostToDevice) != hipSuccess) ||
+      (t.d_ins && hipMemcpy(t.d_ins, ins.data(), ins.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)) {
     fac_replacements_free(fr);
     return fail(FAC_E_HIP, "upload of the replacement table failed");
   }
@@ -1313,11 +1326,17 @@ int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const
   return FAC_OK;
 }
 
+int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
+                            const uint8_t* keep, uint64_t n_patterns, fac_replacements** out) {
+  return fac_replacements_create_templates(engine, utf8, offsets, keep, nullptr, n_patterns, out);
+}
+
 void fac_replacements_free(fac_replacements* replacements) {
   if (!replacements) return;
   if (replacements->t.d_tab || replacements->t.d_bytes) (void)hipSetDevice(replacements->t.device);
   if (replacements->t.d_tab) (void)hipFree(replacements->t.d_tab);
   if (replacements->t.d_bytes) (void)hipFree(replacements->t.d_bytes);
+  if (replacements->t.d_ins) (void)hipFree(replacements->t.d_ins);
   delete replacements;
 }
 
@@ -1400,6 +1419,110 @@ int fac_replace_batch_prefiltered(const fac_engine* engine, const fac_batch* bat
                                   const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
                                   uint64_t* n_replaced, fac_stats* stats) {
   return replace_batch_impl(engine, batch, replacements, args, out, out_len, out_offsets, n_replaced, stats, true);
+}
+
+// ---- batched extraction (fac.h "Batched extraction"): search + apply with the options as passed,
+// then one string per kept record
+
+// The body of fac_extract_batch and fac_extract_batch_prefiltered (prefilter: as search_batch_impl)
+static int extract_batch_impl(const fac_engine* engine, const fac_batch* batch, const fac_replacements* table,
+                              const fac_extract_args* args, fac_match** records, uint64_t* n_items, uint64_t* doc_offsets,
+                              uint8_t** text, uint64_t* text_len, uint64_t** item_offsets, fac_stats* stats,
+                              bool prefilter) {
+  if (!engine || !batch || !args || !n_items || !text_len) return fail(FAC_E_INVALID, "NULL argument");
+  if (!args->device_records != !args->device_text)
+    return fail(FAC_E_INVALID, "device_records and device_text are set together or not at all");
+  if (!args->device_records && (!records || !text)) return fail(FAC_E_INVALID, "NULL argument");
+  if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
+    return fail(FAC_E_INVALID, "bad order/overlap");
+  if (records) *records = nullptr;
+  if (text) *text = nullptr;
+  if (item_offsets) *item_offsets = nullptr;
+  *n_items = 0;
+  *text_len = 0;
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  const fac::ReplaceTable* t = table ? &table->t : nullptr;
+  if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
+  if (t && (t->device != e.device || t->n_patterns != e.pats.size()))
+    return fail(FAC_E_INVALID, "the replacement table was built for another engine");
+  if (e.has_map && !b.h.ascii)
+    return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
+  const uint64_t nd = b.n_docs;
+  std::string err;
+  BatchKept k(st);
+  if (int rc = batch_kept(e, b, args->threshold, args->order, args->overlap, args->unique_ids, prefilter, st,
+                          args->device_doc_offsets, stats, k, err))
+    return fail(rc, err);
+  DevMem obuf(st);
+  fac::ExtractPlan plan;
+  if (int rc = fac::extract_plan_device(b, t, k.res, k.n_res, k.d_doc, st, plan, err)) return fail(rc, err);
+  *n_items = k.n_res;
+  *text_len = plan.total;
+  if (plan.total >= (1ull << fac::kDocTagShift))
+    return fail(FAC_E_UNSUPPORTED, "the extracted text would hold 2^40 bytes or more");
+  if (args->device_records && (k.n_res > args->device_record_cap || plan.total > args->device_text_cap))
+    return fail(FAC_E_OUTPUT_CAPACITY,
+                "device output buffer too small (*n_items = records, *text_len = bytes needed)");
+  uint8_t* d_text = static_cast<uint8_t*>(args->device_text);
+  if (!d_text) {
+    if (int rc = obuf.alloc(plan.total, err)) return fail(rc, err);
+    d_text = static_cast<uint8_t*>(obuf.p);
+  }
+  if (int rc = fac::extract_copy_device(b, t, k.res, plan, d_text, err)) return fail(rc, err);
+  // the text and the item offsets travel on st; deliver_records synchronises it
+  uint8_t* h_text = nullptr;
+  uint64_t* h_off = nullptr;
+  if (!args->device_text) {
+    h_text = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(plan.total, 1)));
+    if (!h_text) return fail(FAC_E_OOM, "out of host memory");
+  }
+  if (item_offsets) {
+    h_off = static_cast<uint64_t*>(std::malloc((k.n_res + 1) * 8));
+    if (!h_off) {
+      std::free(h_text);
+      return fail(FAC_E_OOM, "out of host memory");
+    }
+  }
+  if ((h_text && plan.total && hipMemcpyAsync(h_text, d_text, plan.total, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (h_off && hipMemcpyAsync(h_off, plan.d_item_off, (k.n_res + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (args->device_item_offsets && hipMemcpyAsync(args->device_item_offsets, plan.d_item_off, (k.n_res + 1) * 8,
+                                                   hipMemcpyDeviceToDevice, st) != hipSuccess)) {
+    (void)hipStreamSynchronize(st);
+    std::free(h_text);
+    std::free(h_off);
+    return fail(FAC_E_HIP, "copy of the batch's extracted text failed");
+  }
+  fac_batch_args ra{};
+  ra.device_out = args->device_records;
+  ra.device_cap = args->device_record_cap;
+  uint64_t n_recs = 0;
+  if (int rc = deliver_records(&ra, k.res, k.n_res, k.d_doc, nd, st, records, &n_recs, doc_offsets)) {
+    (void)hipStreamSynchronize(st);
+    std::free(h_text);
+    std::free(h_off);
+    return rc;
+  }
+  if (h_text) *text = h_text;
+  if (h_off) *item_offsets = h_off;
+  return FAC_OK;
+}
+
+int fac_extract_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* table,
+                      const fac_extract_args* args, fac_match** records, uint64_t* n_items, uint64_t* doc_offsets,
+                      uint8_t** text, uint64_t* text_len, uint64_t** item_offsets, fac_stats* stats) {
+  return extract_batch_impl(engine, batch, table, args, records, n_items, doc_offsets, text, text_len, item_offsets,
+                            stats, false);
+}
+
+int fac_extract_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_replacements* table,
+                                  const fac_extract_args* args, fac_match** records, uint64_t* n_items,
+                                  uint64_t* doc_offsets, uint8_t** text, uint64_t* text_len, uint64_t** item_offsets,
+                                  fac_stats* stats) {
+  return extract_batch_impl(engine, batch, table, args, records, n_items, doc_offsets, text, text_len, item_offsets,
+                            stats, true);
 }
 
 // ---- batched segmentation (fac.h "Batched segmentation"): search + apply, then the walk of

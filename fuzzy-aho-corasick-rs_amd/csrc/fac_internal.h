@@ -512,11 +512,16 @@ int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t
 // kReplaceKeep for "keep the matched text" (the callback's None, matches.rs:180-183).
 constexpr uint32_t kReplaceKeep = 0xFFFFFFFFu;
 constexpr uint32_t kReplaceTile = 4096;  // output bytes one workgroup of replace_copy_kernel owns
+// A template entry (fac_replacements_create_templates) also has an insert position k in d_ins: its
+// piece is bytes [0, k) of the entry, the matched text, bytes [k, len). kReplaceNoInsert: a plain
+// entry. d_ins exists only for tables that hold a template; the others run the kernels without it.
+constexpr uint32_t kReplaceNoInsert = 0xFFFFFFFFu;
 struct ReplaceTable {
   int device = 0;
   uint64_t n_patterns = 0;
   uint2* d_tab = nullptr;
   uint8_t* d_bytes = nullptr;
+  uint32_t* d_ins = nullptr;
 };
 // The plan of one call: per kept record {output offset of its piece within its document's output
 // (bit 63: the guard skipped the record), source offset its preceding gap starts at}, and the
@@ -580,7 +585,54 @@ __device__ inline void chunk_store(const Chunk16& c, uint8_t* __restrict__ out, 
     for (uint32_t t = 0; t < c.filled; ++t) out[t] = (uint8_t)(t < 8 ? c.lo >> (8 * t) : c.hi >> (8 * (t - 8)));
   }
 }
+// One output piece of a table entry t (ins: its insert position) for a match whose text is `tlen`
+// bytes is up to three source runs: pre = rep[t.x, t.x + k), text = the match's bytes,
+// suf = rep[t.x + k, t.x + len). A plain entry is pre alone (k = len), "keep" is text alone, and
+// any run may be empty (replace_copy_kernel<true>, extract_copy_kernel).
+__device__ inline uint64_t piece_len(uint2 t, uint32_t ins, uint64_t tlen) {
+  if (t.y == kReplaceKeep) return tlen;
+  return (uint64_t)t.y + (ins != kReplaceNoInsert ? tlen : 0);
+}
+// Run `run` (0 pre, 1 text, 2 suf) of that piece: where its bytes start and how many they are.
+__device__ inline void piece_run(uint2 t, uint32_t ins, const uint8_t* __restrict__ rep,
+                                 const uint8_t* __restrict__ text, uint64_t tlen, int run,
+                                 const uint8_t*& src, uint64_t& rl) {
+  const bool keep = t.y == kReplaceKeep, slot = keep || ins != kReplaceNoInsert;
+  const uint32_t len = keep ? 0u : t.y, k = keep ? 0u : (ins != kReplaceNoInsert ? ins : len);
+  if (run == 0) {
+    src = rep + t.x;
+    rl = k;
+  } else if (run == 1) {
+    src = text;
+    rl = slot ? tlen : 0;
+  } else {
+    src = rep + t.x + k;
+    rl = len - k;
+  }
+}
 #endif
+
+// extract_kernels.hip: the strings of a batch's kept records (fac.h fac_extract_batch;
+// FuzzyMatches::matched_strings, matches.rs:513-515, or the table's piece per record). Item i is
+// the string of record i: bytes [d_item_off[i], d_item_off[i + 1]) of the output.
+struct ExtractPlan {
+  hipStream_t s = nullptr;
+  void* mem = nullptr;
+  uint64_t* d_item_off = nullptr;  // n_items + 1 output offsets
+  uint64_t* d_src = nullptr;       // per item: the global byte its matched text starts at
+  uint64_t n_items = 0;
+  uint64_t total = 0;  // output bytes of the whole batch
+  ~ExtractPlan() {
+    if (mem) call_scratch_give(mem, s);
+  }
+};
+// d_recs / d_doc_off: apply_batch_device's result, any order and overlap. t NULL: every item is its
+// record's matched text. Writes and scans the item lengths on s; synchronises once to read total.
+int extract_plan_device(const Batch& b, const ReplaceTable* t, const fac_match* d_recs, uint64_t n_recs,
+                        const uint64_t* d_doc_off, hipStream_t s, ExtractPlan& plan, std::string& err);
+// Writes the plan.total output bytes to d_out (asynchronous on plan.s).
+int extract_copy_device(const Batch& b, const ReplaceTable* t, const fac_match* d_recs, const ExtractPlan& plan,
+                        uint8_t* d_out, std::string& err);
 
 // segment_kernels.hip: the segmentation helpers of a batch (fac.h fac_segment_batch and
 // fac_render_batch; matches.rs:218-594 per document). The modes are fac.h's FAC_RENDER_*, and

@@ -17,6 +17,11 @@
 //   gap | piece) cursor over runs of source bytes until its 16 bytes are full: documents of 0-3
 //   bytes, empty gaps and empty replacements are runs of length 0 the cursor steps over. No atomics,
 //   no LDS beyond the two tile bounds, one 16-byte store per lane.
+//
+// Both kernels are templates on TPL, chosen by the table: false is the code above and nothing else;
+// true (a table with template entries, ReplaceTable::d_ins) makes a piece the up to three runs of
+// fac_internal.h piece_run -- entry[..k], the matched text, entry[k..] -- and the cursor's state
+// (gap | pre | text | suf).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,10 +41,12 @@ static_assert(kThreads * kChunk == kReplaceTile, "one 16-byte chunk per lane");
 // One thread per document (batch_walk_kernel's shape, and its limit: a document with very many
 // records is walked by one lane). out_len has n_docs + 1 entries, the last one 0, so the exclusive
 // scan's last output is the batch's total.
+template <bool TPL>
 __global__ void replace_plan_kernel(const fac_match* __restrict__ m, const uint64_t* __restrict__ doc_off,
                                     const uint64_t* __restrict__ offsets, uint64_t n_docs,
-                                    const uint2* __restrict__ tab, ulonglong2* __restrict__ plan,
-                                    uint64_t* __restrict__ out_len, unsigned long long* __restrict__ n_applied) {
+                                    const uint2* __restrict__ tab, const uint32_t* __restrict__ ins,
+                                    ulonglong2* __restrict__ plan, uint64_t* __restrict__ out_len,
+                                    unsigned long long* __restrict__ n_applied) {
   const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t applied = 0;
   if (d < n_docs) {
@@ -50,9 +57,14 @@ __global__ void replace_plan_kernel(const fac_match* __restrict__ m, const uint6
       const uint64_t ms = m[i].start, me = m[i].end;
       if (ms >= last) {
         const uint64_t gap = ms - last;
-        const uint32_t rl = tab[m[i].pattern_index].y;
         plan[i] = make_ulonglong2(o + gap, last);
-        o += gap + (rl == kReplaceKeep ? me - ms : (uint64_t)rl);
+        if constexpr (TPL) {
+          const uint32_t p = m[i].pattern_index;
+          o += gap + piece_len(tab[p], ins[p], me - ms);
+        } else {
+          const uint32_t rl = tab[m[i].pattern_index].y;
+          o += gap + (rl == kReplaceKeep ? me - ms : (uint64_t)rl);
+        }
         last = me;
         ++applied;
       } else {
@@ -77,11 +89,12 @@ __device__ inline uint64_t doc_of(const uint64_t* __restrict__ out_off, uint64_t
   return lo;
 }
 
+template <bool TPL>
 __global__ __launch_bounds__(kThreads) void replace_copy_kernel(
     const uint8_t* __restrict__ utf8, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ out_off,
     uint64_t n_docs, const fac_match* __restrict__ m, const uint64_t* __restrict__ doc_off,
-    const ulonglong2* __restrict__ plan, const uint2* __restrict__ tab, const uint8_t* __restrict__ rep,
-    uint8_t* __restrict__ out, uint64_t total, int wide) {
+    const ulonglong2* __restrict__ plan, const uint2* __restrict__ tab, const uint32_t* __restrict__ ins,
+    const uint8_t* __restrict__ rep, uint8_t* __restrict__ out, uint64_t total, int wide) {
   __shared__ uint64_t s_doc[2];
   const uint64_t tile0 = (uint64_t)blockIdx.x * kReplaceTile;
   if (tile0 >= total) return;
@@ -102,7 +115,9 @@ __global__ __launch_bounds__(kThreads) void replace_copy_kernel(
   uint64_t dbase = offsets[d], dlen = offsets[d + 1] - dbase;
   const uint64_t r = g - out_off[d];
   uint64_t k, skip;
-  int piece;  // 0: the gap before record k (the tail for k == e), 1: record k's piece
+  // 0: the gap before record k (the tail for k == e), 1: record k's piece; TPL: 1-3 = the piece's
+  // pre, text and suf runs
+  int piece;
   {
     uint64_t lo = b, hi = e;
     while (lo < hi) {
@@ -143,7 +158,10 @@ __global__ __launch_bounds__(kThreads) void replace_copy_kernel(
       }
     } else if (!(plan[k].x & kSkip)) {
       const uint2 t = tab[m[k].pattern_index];
-      if (t.y == kReplaceKeep) {
+      if constexpr (TPL) {
+        piece_run(t, ins[m[k].pattern_index], rep, utf8 + dbase + m[k].start, m[k].end - m[k].start, piece - 1, src,
+                  rl);
+      } else if (t.y == kReplaceKeep) {
         src = utf8 + dbase + m[k].start;
         rl = m[k].end - m[k].start;
       } else {
@@ -165,8 +183,12 @@ __global__ __launch_bounds__(kThreads) void replace_copy_kernel(
     }
     // next run
     if (piece) {
-      ++k;
-      piece = 0;
+      if (!TPL || piece == 3) {
+        ++k;
+        piece = 0;
+      } else {
+        ++piece;
+      }
     } else if (k < e) {
       piece = 1;
     } else {
@@ -219,8 +241,9 @@ int replace_plan_device(const Batch& b, const ReplaceTable& t, const fac_match* 
   plan.d_out_off = reinterpret_cast<uint64_t*>(base + o_off);
   unsigned long long* d_scal = reinterpret_cast<unsigned long long*>(base + o_scal);
   RP_TRY(hipMemsetAsync(d_scal, 0, 16, s));
-  hipLaunchKernelGGL(replace_plan_kernel, dim3((uint32_t)((nd + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                     d_recs, d_doc_off, b.d_offsets, nd, t.d_tab, plan.d_plan, d_len, d_scal);
+  const auto plan_kernel = t.d_ins ? replace_plan_kernel<true> : replace_plan_kernel<false>;
+  hipLaunchKernelGGL(plan_kernel, dim3((uint32_t)((nd + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, d_recs,
+                     d_doc_off, b.d_offsets, nd, t.d_tab, t.d_ins, plan.d_plan, d_len, d_scal);
   RP_TRY(hipGetLastError());
   RP_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_len, plan.d_out_off, (uint64_t)0, nd + 1,
                                  rocprim::plus<uint64_t>(), s));
@@ -238,9 +261,10 @@ int replace_copy_device(const Batch& b, const ReplaceTable& t, const fac_match* 
   if (!plan.total) return FAC_OK;  // (then no document has output, and n_docs may be 0)
   const uint64_t tiles = (plan.total + kReplaceTile - 1) / kReplaceTile;  // < 2^28: total < 2^40
   const int wide = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0 ? 1 : 0;
-  hipLaunchKernelGGL(replace_copy_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, plan.s, b.h.d_utf8, b.d_offsets,
-                     plan.d_out_off, b.n_docs, d_recs, d_doc_off, plan.d_plan, t.d_tab, t.d_bytes, d_out, plan.total,
-                     wide);
+  const auto copy_kernel = t.d_ins ? replace_copy_kernel<true> : replace_copy_kernel<false>;
+  hipLaunchKernelGGL(copy_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, plan.s, b.h.d_utf8, b.d_offsets,
+                     plan.d_out_off, b.n_docs, d_recs, d_doc_off, plan.d_plan, t.d_tab, t.d_ins, t.d_bytes, d_out,
+                     plan.total, wide);
   RP_TRY(hipGetLastError());
   return FAC_OK;
 }

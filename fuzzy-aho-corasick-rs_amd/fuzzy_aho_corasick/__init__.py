@@ -5,7 +5,7 @@ FuzzyLimits, FuzzyPenalties, Pattern, SearchOptions, Order, Overlap, FuzzyMatch,
 Segment, Similarity, SearchError. The search itself runs in HIP kernels (libfac.so).
 """
 from .engine import (FuzzyAhoCorasick, FuzzyAhoCorasickBuilder, FuzzyReplacer, Prefiltered, ReplacementTable,
-                     StagedBatch, StagedHaystack, StreamMatch, batch_offsets, replacement_table)
+                     StagedBatch, StagedHaystack, StreamMatch, Wrap, batch_offsets, replacement_table, template_table)
 from .matches import FuzzyMatch, FuzzyMatches, Segment, UnmatchedSegment
 from .structs import (DEFAULT_THRESHOLD, DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge,
                       Order, Overlap, Pattern, SearchError, SearchOptions, Similarity,
@@ -13,7 +13,7 @@ from .structs import (DEFAULT_THRESHOLD, DeviceError, FuzzyLimits, FuzzyPenaltie
 
 __all__ = [
     "FuzzyAhoCorasick", "FuzzyAhoCorasickBuilder", "FuzzyReplacer", "Prefiltered", "StagedHaystack", "StreamMatch",
-    "StagedBatch", "batch_offsets", "ReplacementTable", "replacement_table",
+    "StagedBatch", "batch_offsets", "ReplacementTable", "replacement_table", "Wrap", "template_table",
     "FuzzyMatch", "FuzzyMatches", "Segment", "UnmatchedSegment", "DEFAULT_THRESHOLD", "DeviceError",
     "FuzzyLimits", "FuzzyPenalties", "HaystackTooLarge", "Order", "Overlap", "Pattern", "SearchError",
     "SearchOptions", "Similarity", "UnsupportedConfiguration",

@@ -102,6 +102,16 @@ class fac_replace_args(ctypes.Structure):
                 ("device_out_offsets", ctypes.c_void_p)]
 
 
+class fac_extract_args(ctypes.Structure):
+    _fields_ = [("threshold", ctypes.c_float), ("order", ctypes.c_int32), ("overlap", ctypes.c_int32),
+                ("unique_ids", ctypes.POINTER(ctypes.c_uint64)), ("stream", ctypes.c_void_p),
+                ("device_records", ctypes.c_void_p), ("device_record_cap", ctypes.c_uint64),
+                ("device_doc_offsets", ctypes.c_void_p), ("device_text", ctypes.c_void_p),
+                ("device_text_cap", ctypes.c_uint64), ("device_item_offsets", ctypes.c_void_p)]
+
+
+FAC_NO_INSERT = 0xFFFFFFFFFFFFFFFF  # insert_at of a plain entry (fac_replacements_create_templates)
+EXTRACT_TILE = 4096  # output bytes one workgroup of the extraction's copy kernel owns
 REPLACE_TILE = 4096  # output bytes one workgroup of the splice's copy kernel owns (kReplaceTile)
 SEGMENT_TILE = 4096  # output bytes one workgroup of the render modes' copy kernel owns (kSegmentTile)
 FAC_UNMATCHED = 0xFFFFFFFF  # pattern_index of an unmatched segment (fac_segment_batch)
@@ -210,7 +220,15 @@ SIGNATURES = {
                                                      ctypes.c_uint64]),
     "fac_replacements_create": (ctypes.c_int, [_engine_p, ctypes.c_char_p, _u64p, ctypes.c_char_p, ctypes.c_uint64,
                                                _P(ctypes.c_void_p)]),
+    "fac_replacements_create_templates": (ctypes.c_int, [_engine_p, ctypes.c_char_p, _u64p, ctypes.c_char_p, _u64p,
+                                                         ctypes.c_uint64, _P(ctypes.c_void_p)]),
     "fac_replacements_free": (None, [ctypes.c_void_p]),
+    "fac_extract_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_extract_args),
+                                         _P(_P(fac_match)), _u64p, _u64p, _P(_P(ctypes.c_uint8)), _u64p, _P(_u64p),
+                                         _P(fac_stats)]),
+    "fac_extract_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_extract_args),
+                                                     _P(_P(fac_match)), _u64p, _u64p, _P(_P(ctypes.c_uint8)), _u64p,
+                                                     _P(_u64p), _P(fac_stats)]),
     "fac_replace_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_replace_args),
                                          _P(_P(ctypes.c_uint8)), _u64p, _u64p, _u64p, _P(fac_stats)]),
     "fac_replace_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, _P(fac_replace_args),

@@ -6,7 +6,7 @@ import ctypes
 import os
 import sys
 import time
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 from . import _native
 
@@ -97,7 +97,7 @@ class FuzzyAhoCorasickBuilder:
         pats, repl = [], []
         for p, r in pairs:
             pats.append(Pattern.from_(p))
-            repl.append(str(r))
+            repl.append(r if isinstance(r, Wrap) else str(r))
         return FuzzyReplacer(self.build(pats), repl)
 
 
@@ -389,6 +389,20 @@ class FuzzyAhoCorasick:
         out, off = StagedBatch(self, data, offsets).replace_bytes(table, opts)
         return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
+    def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None) -> List[List[str]]:
+        """Per text, one string per match of `self.search(t, opts)`, in its order, as one call
+        (fac_extract_batch): the matched text, or with `replacements` (one entry per pattern, or a
+        ReplacementTable) what replace would put in its place -- the entry, `Wrap` rendered around
+        the matched text, the matched text for None."""
+        table = replacements
+        if replacements is not None and not isinstance(replacements, ReplacementTable):
+            table = ReplacementTable(self, replacements)
+        return _extract_batch(self, [t.encode("utf-8") for t in texts], opts or SearchOptions(), table, False)
+
+    def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None) -> List[List[str]]:
+        """`[self.search(t, opts).matched_strings() for t in texts]` as one call (matches.rs:513-515)."""
+        return self.extract_batch(texts, opts)
+
     # -- the other segmentation helpers of a whole batch (fac_render_batch, fac_segment_batch): each is
     # one device call; whitespace is Rust's char::is_whitespace (DESIGN.md 6a "Batched segmentation")
     def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
@@ -476,8 +490,33 @@ class Prefiltered:
         for d, t in enumerate(texts):
             if out[d] is None:
                 ms = self.engine._search_ranked(t, opts.threshold_, order, overlap, prefilter=True)
-                out[d] = ms.replace(lambda m: _as_text(reps[m.pattern_index]))
+                out[d] = ms.replace(lambda m: _rendered_entry(reps[m.pattern_index], m))
         return out
+
+    def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None) -> List[List[str]]:
+        """`engine.extract_batch` over the pre-filtered search: the ASCII texts as one pre-filtered
+        batch (fac_extract_batch_prefiltered), the others through `search`, results in input order."""
+        opts = opts or SearchOptions()
+        texts = list(texts)
+        enc = [t.encode("utf-8") for t in texts]
+        out = [None] * len(texts)
+        idx = self._batch_parts(enc)
+        if isinstance(replacements, ReplacementTable):
+            table, reps = replacements, replacements.replacements
+        else:
+            reps = None if replacements is None else list(replacements)
+            table = ReplacementTable(self.engine, reps) if idx and reps is not None else None
+        if idx:
+            for d, items in zip(idx, _extract_batch(self.engine, [enc[d] for d in idx], opts, table, True)):
+                out[d] = items
+        for d, t in enumerate(texts):
+            if out[d] is None:
+                out[d] = [_item_text(reps, m) for m in self.search(t, opts)]
+        return out
+
+    def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None) -> List[List[str]]:
+        """`[self.search(t, opts).matched_strings() for t in texts]`, batched as extract_batch is."""
+        return self.extract_batch(texts, opts)
 
 
     def _segmented(self, haystack: str, opts: SearchOptions) -> FuzzyMatches:
@@ -531,6 +570,20 @@ class Prefiltered:
 
 def _as_text(r):
     return bytes(r).decode("utf-8") if isinstance(r, (bytes, bytearray, memoryview)) else r
+
+
+def _item_text(reps, m) -> str:
+    """The item fac_extract_batch gives the match m: its entry's replacement, or the matched text
+    where there is no table or the entry is "keep"."""
+    r = None if reps is None else _rendered_entry(reps[m.pattern_index], m)
+    return m.text if r is None else r
+
+
+def _extract_batch(engine: "FuzzyAhoCorasick", enc, opts: SearchOptions, table, prefilter: bool) -> List[List[str]]:
+    data, offsets = batch_offsets(enc)
+    _, doc_off, text, item_off = StagedBatch(engine, data, offsets).extract(table, opts, prefilter=prefilter)
+    return [[text[int(item_off[i]):int(item_off[i + 1])].decode("utf-8")
+             for i in range(int(doc_off[d]), int(doc_off[d + 1]))] for d in range(len(enc))]
 
 
 def _render_batch(engine: "FuzzyAhoCorasick", texts, mode: int, opts: SearchOptions, prefilter: bool) -> List[str]:
@@ -1164,6 +1217,75 @@ class StagedBatch:
         finally:
             _native.lib.fac_buffer_free(ptr)
 
+    def extract(self, table: "ReplacementTable" = None, opts: SearchOptions = None, records_out=None, text_out=None,
+                doc_offsets_out=None, item_offsets_out=None, stream=None, stats=None, prefilter: bool = False):
+        """fac_extract_batch (`prefilter`: fac_extract_batch_prefiltered): (records, doc_offsets, text,
+        item_offsets). The records are search_records' for the same options; item i, the string of
+        record i, is text[item_offsets[i]:item_offsets[i + 1]]: the matched text
+        (FuzzyMatches::matched_strings) or, with `table`, what replace would put in its place.
+        Document d owns [doc_offsets[d], doc_offsets[d + 1]) of records and items. `records_out` and
+        `text_out` (uint8 CUDA tensors, given together) leave records and text in HBM and are returned
+        cut to their filled parts; FAC_E_OUTPUT_CAPACITY is raised as DeviceError with `.needed`
+        records and `.needed_text` bytes when either is too small (nothing is written then).
+        `doc_offsets_out` / `item_offsets_out`: int64 CUDA tensors that receive the two indexes in HBM
+        (n_docs + 1 entries; one more than the records `records_out` holds); item_offsets is then
+        the filled part of `item_offsets_out` and no copy of it visits the host."""
+        import numpy as np
+        opts = opts or SearchOptions()
+        if (records_out is None) != (text_out is None):
+            raise ValueError("records_out and text_out are given together or not at all")
+        a = _native.fac_extract_args()
+        a.threshold = f32(opts.threshold_)
+        a.order = opts.order_.value
+        a.overlap = opts.overlap_.value
+        a.unique_ids = self.engine._unique_ids()
+        a.stream = stream or None
+        doc_off = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        n, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+        recs = ctypes.POINTER(_native.fac_match)()
+        text = ctypes.POINTER(ctypes.c_uint8)()
+        ioff = ctypes.POINTER(ctypes.c_uint64)()
+        if records_out is not None:
+            a.device_records = records_out.data_ptr()
+            a.device_record_cap = records_out.numel() // _native.REC_BYTES
+            a.device_text = text_out.data_ptr()
+            a.device_text_cap = text_out.numel() * text_out.element_size()
+        if doc_offsets_out is not None:
+            if doc_offsets_out.numel() < self.n_docs + 1 or doc_offsets_out.element_size() != 8:
+                raise ValueError("doc_offsets_out needs n_docs + 1 64-bit entries")
+            a.device_doc_offsets = doc_offsets_out.data_ptr()
+        if item_offsets_out is not None:
+            if records_out is None or item_offsets_out.numel() < 1 or item_offsets_out.element_size() != 8:
+                raise ValueError("item_offsets_out needs records_out and 64-bit entries, one more than its records")
+            a.device_item_offsets = item_offsets_out.data_ptr()
+            a.device_record_cap = min(a.device_record_cap, item_offsets_out.numel() - 1)
+        fn = _native.lib.fac_extract_batch_prefiltered if prefilter else _native.lib.fac_extract_batch
+        dev = records_out is not None
+        rc = fn(self.engine._h, self._h, table._h if table is not None else None, ctypes.byref(a),
+                None if dev else ctypes.byref(recs), ctypes.byref(n),
+                doc_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), None if dev else ctypes.byref(text),
+                ctypes.byref(nbytes), None if item_offsets_out is not None else ctypes.byref(ioff),
+                ctypes.byref(stats) if stats is not None else None)
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed, ex.needed_text = int(n.value), int(nbytes.value)
+                raise
+        if item_offsets_out is not None:
+            item_off = item_offsets_out[: n.value + 1]
+        else:
+            try:
+                item_off = np.ctypeslib.as_array(ioff, shape=(n.value + 1,)).copy()
+            finally:
+                _native.lib.fac_buffer_free(ioff)
+        if dev:
+            return records_out[: n.value * _native.REC_BYTES], doc_off, text_out[: nbytes.value], item_off
+        try:
+            return _native.take_records(recs, n.value), doc_off, ctypes.string_at(text, nbytes.value), item_off
+        finally:
+            _native.lib.fac_buffer_free(text)
+
 
 def replacement_table(replacements) -> Tuple[bytes, List[int], bytes]:
     """(utf8, offsets, keep) of one replacement per pattern, the layout fac_replacements_create
@@ -1186,17 +1308,54 @@ def replacement_table(replacements) -> Tuple[bytes, List[int], bytes]:
     return b"".join(parts), offsets, bytes(keep)
 
 
+class Wrap(NamedTuple):
+    """A template replacement: the match becomes prefix + m.text + suffix, the callback
+    `|m| Some(format!("{prefix}{}{suffix}", m.text))` (matches.rs:445-446) -- highlighting, tagging,
+    bracketing. `str` or `bytes` halves, each valid UTF-8 on its own."""
+    prefix: Union[str, bytes]
+    suffix: Union[str, bytes] = ""
+
+    def render(self, text: str) -> str:
+        return _as_text(self.prefix) + text + _as_text(self.suffix)
+
+
+def template_table(replacements) -> Tuple[bytes, List[int], bytes, List[int]]:
+    """(utf8, offsets, keep, insert_at), the layout fac_replacements_create_templates takes:
+    replacement_table's first three, a `Wrap` entry holding prefix + suffix as its bytes, and
+    insert_at[p] = len(prefix) in bytes for a `Wrap`, _native.FAC_NO_INSERT otherwise. Pure Python."""
+    flat, insert_at = [], []
+    for r in replacements:
+        if isinstance(r, Wrap):
+            data, off, _ = replacement_table([r.prefix, r.suffix])
+            flat.append(data)
+            insert_at.append(off[1])
+        else:
+            flat.append(r)
+            insert_at.append(_native.FAC_NO_INSERT)
+    return replacement_table(flat) + (insert_at,)
+
+
+def _rendered_entry(r, m) -> Optional[str]:
+    """What the callback of a table entry returns for the match m (None: keep the matched text)."""
+    return r.render(m.text) if isinstance(r, Wrap) else _as_text(r)
+
+
 class ReplacementTable:
-    """One replacement per pattern of `engine` (None = keep), validated and uploaded once
-    (fac_replacements_create); freed with the object."""
+    """One replacement per pattern of `engine` (None = keep, `Wrap` = a template around the matched
+    text), validated and uploaded once (fac_replacements_create, or
+    fac_replacements_create_templates when a `Wrap` is present); freed with the object."""
 
     def __init__(self, engine: FuzzyAhoCorasick, replacements):
         self.replacements = list(replacements)
-        data, offsets, keep = replacement_table(self.replacements)
+        data, offsets, keep, insert_at = template_table(self.replacements)
         self.engine, self.n_patterns = engine, len(keep)
         off = (ctypes.c_uint64 * len(offsets))(*offsets)
         h = ctypes.c_void_p()
-        rc = _native.lib.fac_replacements_create(engine._h, data, off, keep, len(keep), ctypes.byref(h))
+        if any(isinstance(r, Wrap) for r in self.replacements):
+            ins = (ctypes.c_uint64 * len(insert_at))(*insert_at)
+            rc = _native.lib.fac_replacements_create_templates(engine._h, data, off, keep, ins, len(keep), ctypes.byref(h))
+        else:
+            rc = _native.lib.fac_replacements_create(engine._h, data, off, keep, len(keep), ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h
@@ -1209,22 +1368,33 @@ class ReplacementTable:
 
 
 class FuzzyReplacer:
-    """replacer.rs:9-52"""
+    """replacer.rs:9-52; a replacement may be a `Wrap` (prefix + m.text + suffix)."""
 
     def __init__(self, engine: FuzzyAhoCorasick, replacements: List[str]):
         self.engine = engine
         self.replacements = replacements
 
-    def replace(self, text: str, opts: SearchOptions) -> str:
-        return self.engine.replace(text, opts, lambda m: self.replacements[m.pattern_index])
+    def _callback(self, m):
+        return _rendered_entry(self.replacements[m.pattern_index], m)
 
-    def replace_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
-        """`[self.replace(t, opts) for t in texts]` as one device pass (fac_replace_batch)."""
+    def replace(self, text: str, opts: SearchOptions) -> str:
+        return self.engine.replace(text, opts, self._callback)
+
+    def extract_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[str]]:
+        """Per text, the replacement of every match `engine.search(t, opts)` finds, as one device pass
+        (fac_extract_batch): the canonical form of each mention."""
+        return self.engine.extract_batch(texts, opts, self._device_table())
+
+    def _device_table(self) -> "ReplacementTable":
         key = tuple(self.replacements)
         if getattr(self, "_table", None) is None or self._table[0] != key:
             self._table = (key, ReplacementTable(self.engine, self.replacements))
-        return self.engine.replace_batch(texts, opts, self._table[1])
+        return self._table[1]
+
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+        """`[self.replace(t, opts) for t in texts]` as one device pass (fac_replace_batch)."""
+        return self.engine.replace_batch(texts, opts, self._device_table())
 
     def replace_stream(self, reader, writer, threshold: float) -> int:
         """replacer.rs:35-44"""
-        return self.engine.replace_stream(reader, writer, threshold, lambda m: self.replacements[m.pattern_index])
+        return self.engine.replace_stream(reader, writer, threshold, self._callback)

@@ -331,7 +331,8 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  * segment_iter and split (fac_segment_batch), strip_prefix, strip_suffix and segment_text
  * (fac_render_batch). Every one of these calls has a pre-filtered form for all-ASCII batches
  * (fac_search_batch_prefiltered, fac_replace_batch_prefiltered, fac_segment_batch_prefiltered,
- * fac_render_batch_prefiltered below). Multi-GPU batches are not provided.
+ * fac_render_batch_prefiltered below). The matched strings of a batch, or each match's replacement,
+ * come from fac_extract_batch and fac_extract_batch_prefiltered. Multi-GPU batches are not provided.
  *
  * Limits of the pre-filtered forms: where the filter runs, the batch must be all ASCII -- one
  * non-ASCII document gives FAC_E_UNSUPPORTED with nothing written (a non-ASCII document's symbol
@@ -419,15 +420,33 @@ int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* b
  *
  * A replacement table gives each pattern its canonical form, or marks it "keep" (the callback's
  * None, matches.rs:180-183: the matched text stays). It is the per-pattern table FuzzyReplacer
- * uses (replacer.rs:24); a per-match callback cannot run on the device. Replacement p is bytes
- * [offsets[p], offsets[p+1]) of utf8 (offsets[0] == 0, non-decreasing, empty = deletion), each
- * valid UTF-8 on its own; keep: NULL, or one byte per pattern, non-zero = keep (its bytes are
+ * uses (replacer.rs:24); a per-match callback cannot run on the device, but the callback the crate
+ * documents, format!("**{}**", m.text) (matches.rs:445-446), is a template -- prefix + m.text +
+ * suffix -- and those the table holds too (fac_replacements_create_templates below).
+ * Replacement p is bytes [offsets[p], offsets[p+1]) of utf8 (offsets[0] == 0, non-decreasing,
+ * empty = deletion), each valid UTF-8 on its own; keep: NULL, or one byte per pattern, non-zero = keep (its bytes are
  * ignored). Validated and uploaded once. FAC_E_INVALID: n_patterns differs from the engine's, bad
  * offsets or invalid UTF-8; FAC_E_UNSUPPORTED: 2^32 bytes of replacements or more. */
 typedef struct fac_replacements fac_replacements;
 int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
                             const uint8_t* keep, uint64_t n_patterns, fac_replacements** out);
 void fac_replacements_free(fac_replacements* replacements);
+
+/* fac_replacements_create with template entries: the replacement of a match m of pattern p is
+ * entry[..k] + m.text + entry[k..], the callback Some(format!("{pre}{}{suf}", m.text)) -- highlighting,
+ * tagging, bracketing. insert_at: NULL (the call is fac_replacements_create), or one value per
+ * pattern: FAC_NO_INSERT for a plain entry, or the byte position k in [0, len_p] the matched text goes
+ * to, on a UTF-8 character boundary of entry p, so that both halves are valid UTF-8 on their own.
+ * keep[p] != 0 wins over insert_at[p] as it wins over the bytes; an empty entry with k = 0 is "keep"
+ * byte for byte. FAC_E_INVALID: k > len_p or k inside a character; everything else as
+ * fac_replacements_create. The result is an ordinary table: fac_replace_batch,
+ * fac_replace_batch_prefiltered and fac_extract_batch take it as they take any other, a skipped
+ * record contributes nothing, template or not, and only a piece's length and bytes change. A table
+ * without a template entry runs the same device code as one of fac_replacements_create. */
+#define FAC_NO_INSERT UINT64_MAX
+int fac_replacements_create_templates(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
+                                      const uint8_t* keep, const uint64_t* insert_at, uint64_t n_patterns,
+                                      fac_replacements** out);
 
 typedef struct fac_replace_args {
   float threshold;
@@ -470,6 +489,52 @@ int fac_replace_batch(const fac_engine* engine, const fac_batch* batch, const fa
 int fac_replace_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_replacements* replacements,
                                   const fac_replace_args* args, uint8_t** out, uint64_t* out_len, uint64_t* out_offsets,
                                   uint64_t* n_replaced, fac_stats* stats);
+
+/* ---- Batched extraction: FuzzyMatches::matched_strings (matches.rs:513-515) of every document of
+ * a staged batch, cut out on the device: a list-of-strings column, one string per kept record.
+ *
+ * For every document d, ms = engine.search(doc_d, opts) with the options exactly as passed (there is
+ * no `segmented` normalisation: matched_strings works on whatever search returned). With table NULL
+ * document d's items are ms.matched_strings(); with a table, item = callback(m), or m.text where the
+ * callback gives None -- plain, "keep" and template entries all count (the canonical form of each
+ * mention, say). Records and items are returned together and index the same: item i is the string
+ * of record i, bytes [item_offsets[i], item_offsets[i+1]) of the text, and document d owns
+ * [doc_offsets[d], doc_offsets[d+1]) of both. For Unsorted+Keep the order within a document is as
+ * unspecified as fac_search_batch's; the pairing of record and item is not. Items may overlap in
+ * the source (Overlap::Keep), so the text can exceed the batch, and may be empty. */
+typedef struct fac_extract_args {
+  float threshold;
+  int32_t order;               /* as fac_matches_apply */
+  int32_t overlap;             /* as fac_matches_apply */
+  const uint64_t* unique_ids;  /* as fac_batch_args */
+  void* stream;
+  void* device_records;        /* optional: records stay in HBM (with device_text) */
+  uint64_t device_record_cap;  /* records device_records holds */
+  uint64_t* device_doc_offsets; /* optional: n_docs+1 entries on the device */
+  void* device_text;           /* optional: the items' bytes stay in HBM (with device_records) */
+  uint64_t device_text_cap;    /* bytes device_text holds */
+  uint64_t* device_item_offsets; /* optional: device_record_cap+1 entries on the device */
+} fac_extract_args;
+
+/* doc_offsets: the caller's host array of n_docs+1 entries (may be NULL). Host results: *records
+ * (fac_matches_free), *text and *item_offsets (*n_items + 1 entries; may be NULL), both
+ * library-allocated and freed with fac_buffer_free. device_records and device_text are set together
+ * or not at all (FAC_E_INVALID otherwise); then records and text go to those buffers,
+ * device_item_offsets receives the first *n_items + 1 offsets, and records / text may be NULL.
+ * *n_items and *text_len are the counts either way. FAC_E_OUTPUT_CAPACITY: either device buffer is
+ * too small; nothing was written to either, and *n_items and *text_len hold what is needed.
+ * FAC_E_INVALID for a table of another pattern count or device, FAC_E_UNSUPPORTED (never a partial
+ * result) for 2^40 text bytes or more; other errors and limits, auto-beam and mapping engines as
+ * fac_search_batch. */
+int fac_extract_batch(const fac_engine* engine, const fac_batch* batch, const fac_replacements* table,
+                      const fac_extract_args* args, fac_match** records, uint64_t* n_items, uint64_t* doc_offsets,
+                      uint8_t** text, uint64_t* text_len, uint64_t** item_offsets, fac_stats* stats);
+
+/* fac_extract_batch over fac_search_batch_prefiltered's records; fallback and limits as that call. */
+int fac_extract_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_replacements* table,
+                                  const fac_extract_args* args, fac_match** records, uint64_t* n_items,
+                                  uint64_t* doc_offsets, uint8_t** text, uint64_t* text_len, uint64_t** item_offsets,
+                                  fac_stats* stats);
 
 /* ---- Batched segmentation: segment_iter, split, strip_prefix, strip_suffix and segment_text
  * (query.rs:98-170, matches.rs:218-594) of every document of a staged batch, walked on the device.

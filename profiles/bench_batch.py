@@ -42,6 +42,18 @@ With --segment the legs are (DESIGN.md §6a "Batched segmentation"):
   (b') the per-document loops engine.strip_prefix(doc, opts), strip_suffix, segment_text and
        list(engine.segment_iter(doc, opts)) over the fixed sample, host wall clock.
 
+With --template the legs are (DESIGN.md §6a "Template replacements and extraction"):
+
+  (r)  fac_replace_batch with the plain upper-case table of --replace,
+  (t)  the same batch with every entry Wrap("<b>", "</b>"): (t) - (r) is what the three-run pieces
+       and the longer output cost, beside a hipMemcpyDtoDAsync of (t)'s output size.
+
+With --extract:
+
+  (x)  fac_extract_batch with a NULL table (matched_strings), records, text and both indexes left
+       in HBM,
+  (a)  fac_search_batch with the same options and device_out: (x) - (a) is the extraction.
+
 Staging is reported in ms per GiB: the batch stager against fac_haystack_stage_device on the same
 bytes. One JSON line per configuration; "gate" is true when (a) beats (b) per document by more than
 (b)'s own spread and (a)'s records for the sample equal (b)'s.
@@ -360,6 +372,101 @@ def run_segment(name, nbytes, L, sample, rounds):
     return res
 
 
+def dtod_copy_ms(stream, sh, src, nbytes, rounds):
+    """The byte movers' yardstick: hipMemcpyDtoDAsync of nbytes on the stream, or None."""
+    try:
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        hip.hipMemcpyDtoDAsync.restype = ctypes.c_int
+        dst = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+        rcs = []
+        cp = lambda: rcs.append(hip.hipMemcpyDtoDAsync(dst.data_ptr(), src.data_ptr(), nbytes, sh))  # noqa: E731
+        cp()
+        ms = [round(timed(stream, cp)[0], 4) for _ in range(rounds)]
+        return None if any(rcs) or not torch.equal(dst, src[:nbytes]) else ms
+    except (OSError, AttributeError):
+        return None
+
+
+def run_template_extract(name, nbytes, L, rounds, leg, profile_only):
+    """--template: (r) fac_replace_batch with the plain upper-case table against (t) the same batch
+    with every entry Wrap("<b>", "</b>"). --extract: (x) fac_extract_batch with a NULL table against
+    (a) fac_search_batch with the same options, both with their results left in HBM."""
+    from fuzzy_aho_corasick import Wrap
+    w, engine = workload(name, nbytes)
+    data = w.haystack
+    off = cut_documents(data, L)
+    nd = len(off) - 1
+    dev = torch.device("cuda", engine.device)
+    t_data = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
+    t_off = torch.from_numpy(off.view(np.int64).copy()).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    sh = stream.cuda_stream
+    opts = SearchOptions().threshold(w.threshold)
+    if leg == "template":
+        opts.order_, opts.overlap_ = Order.Default, Overlap.NonOverlapping
+    plain = ReplacementTable(engine, [(p if isinstance(p, str) else p.pattern).upper() for p in w.patterns])
+    wrapped = ReplacementTable(engine, [Wrap("<b>", "</b>")] * len(w.patterns))
+    bufs = {"rec": torch.empty(max(1 << 16, len(data) // 16) * 32, dtype=torch.uint8, device=dev),
+            "out": torch.empty(len(data) + (1 << 20), dtype=torch.uint8, device=dev)}
+    t_doc_off = torch.empty(nd + 1, dtype=torch.int64, device=dev)
+    sb = StagedBatch.from_device(engine, t_data.data_ptr(), t_off.data_ptr(), nd, len(data), stream=sh)
+
+    def grown(call, unit):
+        """unit: what the error's `.needed` counts, "out" bytes or "rec" records (`.needed_text`: bytes)"""
+        while True:
+            try:
+                return call()
+            except Exception as ex:  # FAC_E_OUTPUT_CAPACITY: grow and run again
+                need = {"out": getattr(ex, "needed_text", 0), "rec": 0}
+                need[unit] = max(need[unit], getattr(ex, "needed", 0))
+                if not any(need.values()):
+                    raise
+                if need["out"] > bufs["out"].numel():
+                    bufs["out"] = torch.empty(int(need["out"] * 1.1 + 1024), dtype=torch.uint8, device=dev)
+                if need["rec"] > bufs["rec"].numel() // 32:
+                    bufs["rec"] = torch.empty(int(need["rec"] * 1.1 + 1024) * 32, dtype=torch.uint8, device=dev)
+                    bufs["ioff"] = torch.empty(bufs["rec"].numel() // 32 + 1, dtype=torch.int64, device=dev)
+
+    bufs["ioff"] = torch.empty(bufs["rec"].numel() // 32 + 1, dtype=torch.int64, device=dev)
+
+    bufs["ioff"] = torch.empty(bufs["rec"].numel() // 32 + 1, dtype=torch.int64, device=dev)
+    if leg == "template":
+        legs = {"r": lambda: grown(lambda: sb.replace_bytes(plain, opts, out=bufs["out"], offsets_out=t_doc_off,
+                                                            stream=sh), "out"),
+                "t": lambda: grown(lambda: sb.replace_bytes(wrapped, opts, out=bufs["out"], offsets_out=t_doc_off,
+                                                            stream=sh), "out")}
+    else:
+        legs = {"x": lambda: grown(lambda: sb.extract(None, opts, records_out=bufs["rec"], text_out=bufs["out"],
+                                                      doc_offsets_out=t_doc_off, item_offsets_out=bufs["ioff"],
+                                                      stream=sh), "rec"),
+                "a": lambda: grown(lambda: sb.search_records(opts, out=bufs["rec"], doc_offsets_out=t_doc_off, stream=sh),
+                                   "rec")}
+    for _ in range(2):  # warm-up: buffers, tables, the output sizes
+        for fn in legs.values():
+            fn()
+    first = "t" if leg == "template" else "x"
+    if profile_only:
+        for _ in range(3):
+            legs[first]()
+        return None
+    ms = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():  # the legs alternate
+            t, res = timed(stream, fn)
+            ms[k].append(t)
+            if k == first:
+                out_bytes = int((res[0] if leg == "template" else res[2]).numel())
+                items = int(sb.replaced) if leg == "template" else int(res[0].numel()) // 32
+    med = lambda v: float(np.median(v))  # noqa: E731
+    other = "r" if leg == "template" else "a"
+    return {"leg": leg, "config": name, "bytes": len(data), "L": L, "docs": nd, "out_bytes": out_bytes, "items": items,
+            "ms": {k: [round(x, 3) for x in v] for k, v in ms.items()},
+            "spread_ms": {k: round(max(v) - min(v), 3) for k, v in ms.items()},
+            first + "_minus_" + other + "_ms": round(med(ms[first]) - med(ms[other]), 3),
+            "dtod_copy_ms": dtod_copy_ms(stream, sh, bufs["out"], out_bytes, rounds)}
+
+
 def prefilter_workload(name, nbytes):
     """c2 / c5 as workloads.config; c5n: c5's patterns and threshold over fresh filler words alone."""
     if name != "c5n":
@@ -486,6 +593,10 @@ def main():
     ap.add_argument("--segment", action="store_true",
                     help="time fac_render_batch (each mode) and fac_segment_batch against fac_search_batch, the "
                          "all-keep fac_replace_batch and the per-document loops")
+    ap.add_argument("--template", action="store_true",
+                    help="time fac_replace_batch with a table of Wrap entries against the plain table")
+    ap.add_argument("--extract", action="store_true",
+                    help="time fac_extract_batch (NULL table) against fac_search_batch with the same options")
     args = ap.parse_args()
     if args.prefilter:
         for name in (args.configs if args.configs != ["c2", "c3"] else ["c2", "c5", "c5n"]):
@@ -496,6 +607,12 @@ def main():
         return
     for name in args.configs:
         for L in args.lengths:
+            if args.template or args.extract:
+                res = run_template_extract(name, args.c2_bytes if name == "c2" else args.c3_bytes, L, args.rounds,
+                                           "template" if args.template else "extract", args.profile_only)
+                if res is not None:
+                    print(json.dumps(res), flush=True)
+                continue
             if args.segment:
                 res = run_segment(name, args.c2_bytes if name == "c2" else args.c3_bytes, L, args.sample, args.rounds)
                 print(json.dumps(res), flush=True)
