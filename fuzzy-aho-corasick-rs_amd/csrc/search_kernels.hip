@@ -1845,6 +1845,8 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
             vis[slot].packed = w[u].w;
           }
         } else {
+          // ne <= EL.cap: the snapshot was built in this launch_pass call, where P.ecap only grows and
+          // a build refuses a best list past it (cache levels must not outlive the call that set P.ecap)
           EL.buf[i - nq - nv] = w[u];
         }
       }
@@ -3288,6 +3290,7 @@ __global__ __launch_bounds__(256) void rc_lookup_kernel(SearchParams P) {
 // records and are marked RC_DONE.
 constexpr uint32_t LANE_RUN = 1u, LANE_OK = 2u, LANE_BAIL = 3u;
 constexpr uint32_t LANE_CHUNK = 4096;
+constexpr uint32_t LANE_ESLICE = 1024;  // emit scratch entries of a lane workgroup's slice (P.ecap's default)
 __device__ unsigned long long g_lane_dbg[8];  // diagnostics (FAC_RC_DEBUG): taken, finished, bailed, lane runs
 // Lane ring entries are 12 bytes in three LDS planes (node, penalty, position word): the position word
 // packs j_rel and me_rel (8 bits each) and the four edit counts (4 bits each). A state that does not
@@ -3549,7 +3552,8 @@ __global__ __launch_bounds__(64) void lane_window_kernel(SearchParams P) {
   __shared__ uint32_t s_q[3 * QL * 64];  // ring slot i of lane l at i * 64 + l, three planes
   // best lists in this workgroup's slice of the emit scratch (read only on emissions; keeping them out
   // of LDS lets more waves share a CU): entry i of lane l at i * 64 + l
-  uint4* s_e = P.ebuf + (size_t)blockIdx.x * P.ecap;
+  static_assert(ELN * 64 <= LANE_ESLICE, "lane best lists must fit the workgroup's emit scratch slice");
+  uint4* s_e = P.ebuf + (size_t)blockIdx.x * max(P.ecap, LANE_ESLICE);
   __shared__ uint64_t s_list[128];
   const uint32_t lane = lane_id();
   uint64_t popped_lane = 0, cached_lane = 0;
@@ -5533,8 +5537,16 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   // beamed passes spill every window whose pending count passes 2 bw from the dedup-free first pass
   // (C3: ~5 % of its windows): a list too short re-runs the whole pass
   uint64_t spill_cap = std::max<uint64_t>(4096, windows / (P.beam ? 8 : 32));
+  // diagnostics: first sizes of the three buffers whose overflow re-runs the whole pass (the loop
+  // below), so small inputs reach those branches; the growth rules are the loop's own
+  if (const char* v = diag_env("FAC_OUT_CAP0")) out_cap = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+  if (const char* v = diag_env("FAC_SPILL_CAP0")) spill_cap = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+  if (const char* v = diag_env("FAC_ECAP0"))
+    P.ecap = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1u << 20, std::strtoull(v, nullptr, 10)));
   const uint32_t max_grid = (uint32_t)cus * 16;
-  HIP_TRY(d_ebuf.alloc((size_t)max_grid * P.ecap * sizeof(uint4), stream));
+  // a slice per wave slot; the lane kernel's workgroups take slices of at least LANE_ESLICE entries
+  auto ebuf_bytes = [&]() { return (size_t)max_grid * std::max<uint32_t>(P.ecap, LANE_ESLICE) * sizeof(uint4); };
+  HIP_TRY(d_ebuf.alloc(ebuf_bytes(), stream));
   HIP_TRY(d_cnt.alloc(N_COUNTERS * sizeof(unsigned long long), stream));
   // wave slots: a ring of max_grid slots per stream a slot-using kernel runs on (this one, the
   // level-1 build's); beamed engines: each slot's beam-selection scratch, sized for 256-state rings
@@ -6154,7 +6166,6 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   auto launch_lane = [&]() -> int {
     // one wave per workgroup; each takes its best lists from its own emit-scratch slice
     const uint32_t lgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((windows + LANE_CHUNK - 1) / LANE_CHUNK, (uint64_t)max_grid));
-    static_assert(16 * 64 <= 1024, "lane best lists must fit the emit scratch slice (P.ecap >= 1024)");
     // 12-state rings by default: 10 KB of LDS, so 16 waves per CU instead of 12 with 16 states, and the
     // windows that need 13-16 states (the ones that held a wave longest) go to the dedup-free pass.
     // C3: lane 13.6 -> 7.1 ms, wave 41.0 -> 45.0 ms (133.5 vs 135.7 per step); fresh words 447.5 vs
@@ -6184,12 +6195,17 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       diag_env("FAC_RC_CHUNK") ? std::strtoul(diag_env("FAC_RC_CHUNK"), nullptr, 10) : rc_auto));
   PoolBuf d_dl, d_dlm;     // the windows the dense bitmaps leave open (dl_*_kernel) and their masks
   bool kp_listed = false;  // the main pass walks the key part's window list (no prefix cache)
-  if (P.rc_mode == 0 && P.kp_wlist) {
-    P.win_list = P.kp_wlist;
+  // the pass's source windows: the key part's list, or null for every window. The dense list below
+  // is built from it and stands in P.kp_wlist for the lookups of one run only: a re-run of the pass
+  // builds it again from the same source
+  const uint64_t* const src_wlist = P.kp_wlist;
+  if (P.rc_mode == 0 && src_wlist) {
+    P.win_list = src_wlist;
     kp_listed = true;
   }
   for (;;) {
     if (pass_windows == 0) break;
+    P.kp_wlist = src_wlist;
     // spilled windows are few and heavy: one per block turn; behind the prefix-cache lookups most
     // windows are done, so chunks are larger (fewer hand-out atomics; the group prescan skips them)
     P.chunk = kp_listed ? (uint32_t)base_chunk : P.win_list ? 1u : (P.rc_mode == 1 ? rc_chunk : (uint32_t)base_chunk);
@@ -6230,7 +6246,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
         HIP_TRY(hipGetLastError());
         P.kp_wlist = static_cast<const uint64_t*>(d_dl.p);
         lk_windows = listed;
-        dense_done += pass_windows - listed;
+        dense_done = pass_windows - listed;  // (a first-variant pass: a re-run counts the same windows)
       }
       // the open windows' hits, compacted per region (entries: n_reg * RC_REGION at most)
       const uint64_t n_reg = std::max<uint64_t>(1, (lk_windows + RC_REGION - 1) / RC_REGION);
@@ -6363,7 +6379,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     if (flags & ERR_EMIT) {
       if (P.ecap < (1u << 20)) {
         P.ecap *= 8;
-        HIP_TRY(d_ebuf.alloc((size_t)max_grid * P.ecap * sizeof(uint4), stream));
+        HIP_TRY(d_ebuf.alloc(ebuf_bytes(), stream));
         ++retries;
         continue;
       }

@@ -31,7 +31,9 @@
  *
  * Diagnostics: the library reads FAC_* environment knobs (kernel variants, prefix-cache levels,
  * FAC_GRAPHEME_LIMIT, ...) only when FAC_DIAGNOSTICS=1 is set; otherwise the search path depends
- * on the arguments alone.
+ * on the arguments alone. FAC_OUT_CAP0, FAC_ECAP0 and FAC_SPILL_CAP0 (each >= 1) set the first size
+ * of a search pass's record buffer, per-window best lists and spill list, whose overflow re-runs
+ * the pass with a larger buffer: results never depend on them.
  */
 #ifndef FAC_H
 #define FAC_H
