@@ -28,6 +28,9 @@ struct fac_haystack {
 struct fac_stream {
   fac::StreamCore* s = nullptr;
 };
+struct fac_replace_stream {
+  fac::StreamCore* s = nullptr;
+};
 struct fac_batch {
   fac::Batch b;
 };
@@ -703,8 +706,10 @@ namespace fac {
 // depends on where its text starts and ends), windows out of order or overlapping beyond their
 // neighbours, or pre-filter tables that need the packed full scan.
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
-                         bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err) {
+                         bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
+                         std::vector<uint64_t>* win_off) {
   owned.clear();
+  if (win_off) win_off->assign(n_windows + 1, 0);  // (the early returns below: no records at all)
   if (!h.ascii || h.open_end || h.base || n_windows == 0 || n_windows >= (1u << 24) || h.len >= (1ull << kWinTagShift))
     return FAC_E_UNSUPPORTED;
   std::vector<std::pair<uint64_t, uint64_t>> span(n_windows);
@@ -773,7 +778,7 @@ int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* win
         return FAC_E_HIP;
       }
     }
-    windows_owned_host(e, recs, own, owned);
+    windows_owned_host(e, recs, own, owned, win_off);
     return FAC_OK;
   }
 }
@@ -930,20 +935,18 @@ int fac_stream_window_staged_device(const fac_engine* engine, const fac_haystack
   }
 }
 
-int fac_stream_windows_staged_device(const fac_engine* engine, const fac_haystack* hay, const uint64_t* windows,
-                                     uint64_t n_windows, float threshold, int32_t prefilter, void* stream, void* device_out,
-                                     uint64_t device_cap, uint64_t* n_out, fac_stats* stats) {
-  if (!engine || !hay || !n_out || (!windows && n_windows) || (!device_out && device_cap))
-    return fail(FAC_E_INVALID, "NULL argument");
-  *n_out = 0;
+// The owned records of a run of stream windows, in window order (win_off, optional: their CSR
+// index): batched where the run qualifies (stream_windows_batch), window by window otherwise.
+static int owned_windows(const fac_engine* engine, const fac_haystack* hay, const uint64_t* windows, uint64_t n_windows,
+                         float threshold, int32_t prefilter, void* stream, std::vector<fac_match>& owned,
+                         std::vector<uint64_t>* win_off, fac_stats* stats) {
   const fac::Haystack& h = hay->h;
   if (h.open_end || h.base) return fail(FAC_E_INVALID, "stream windows are cut from a whole staged haystack");
   const fac::Engine& e = engine->e;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
-  std::vector<fac_match> owned;
   std::string err;
-  int rc = fac::stream_windows_batch(e, h, windows, n_windows, threshold, prefilter != 0, st, owned, stats, err);
+  int rc = fac::stream_windows_batch(e, h, windows, n_windows, threshold, prefilter != 0, st, owned, stats, err, win_off);
   if (rc == FAC_E_UNSUPPORTED) {  // window by window (fac_stream_window_staged)
     owned.clear();
     for (uint64_t w = 0; w < n_windows; ++w) {
@@ -952,18 +955,90 @@ int fac_stream_windows_staged_device(const fac_engine* engine, const fac_haystac
       rc = fac_stream_window_staged(engine, hay, windows[4 * w], windows[4 * w + 1], windows[4 * w + 2], windows[4 * w + 3],
                                     threshold, prefilter, stream, &part, &np, stats);
       if (rc) return rc;
+      if (win_off) (*win_off)[w] = owned.size();
       owned.insert(owned.end(), part, part + np);
       fac_matches_free(part);
     }
+    if (win_off) (*win_off)[n_windows] = owned.size();
   } else if (rc) {
     return fail(rc, err);
   }
+  return FAC_OK;
+}
+
+int fac_stream_windows_staged_device(const fac_engine* engine, const fac_haystack* hay, const uint64_t* windows,
+                                     uint64_t n_windows, float threshold, int32_t prefilter, void* stream, void* device_out,
+                                     uint64_t device_cap, uint64_t* n_out, fac_stats* stats) {
+  if (!engine || !hay || !n_out || (!windows && n_windows) || (!device_out && device_cap))
+    return fail(FAC_E_INVALID, "NULL argument");
+  *n_out = 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<fac_match> owned;
+  if (int rc = owned_windows(engine, hay, windows, n_windows, threshold, prefilter, stream, owned, nullptr, stats)) return rc;
   *n_out = owned.size();
   if (owned.size() > device_cap) return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*n_out = records needed)");
   if (!owned.empty() &&
       (hipMemcpyAsync(device_out, owned.data(), owned.size() * sizeof(fac_match), hipMemcpyHostToDevice, st) != hipSuccess ||
        hipStreamSynchronize(st) != hipSuccess))
     return fail(FAC_E_HIP, "hipMemcpyAsync of the owned records failed");
+  return FAC_OK;
+}
+
+int fac_replace_windows_staged_device(const fac_engine* engine, const fac_haystack* hay, const uint64_t* windows,
+                                      uint64_t n_windows, const fac_replacements* replacements, float threshold,
+                                      int32_t prefilter, void* stream, uint64_t* emitted, void* device_out,
+                                      uint64_t device_cap, uint64_t* out_len, uint64_t* n_applied, uint64_t* n_skipped,
+                                      fac_stats* stats) {
+  if (!engine || !hay || !replacements || !emitted || !out_len || (!windows && n_windows) || (!device_out && device_cap))
+    return fail(FAC_E_INVALID, "NULL argument");
+  *out_len = 0;
+  if (n_applied) *n_applied = 0;
+  if (n_skipped) *n_skipped = 0;
+  const fac::Engine& e = engine->e;
+  const fac::Haystack& h = hay->h;
+  const fac::ReplaceTable& t = replacements->t;
+  if (h.open_end || h.base) return fail(FAC_E_INVALID, "stream windows are cut from a whole staged haystack");
+  if (h.device != e.device) return fail(FAC_E_INVALID, "haystack was staged for another device");
+  if (t.device != e.device || t.n_patterns != e.pats.size())
+    return fail(FAC_E_INVALID, "the replacement table was built for another engine");
+  if (n_windows == 0) return FAC_OK;  // (no window, no commit point: the cursor stays)
+  std::string err;
+  if (!h.ascii)
+    if (int hrc = fac::ensure_host(h, err)) return fail(hrc, err);
+  // the windows in bytes of the staged text: records come back at those offsets (base = the window's
+  // first byte), and base - that byte must be one value, the stream offset of the text's byte 0
+  auto byte_of = [&](uint64_t g) { return h.ascii ? g : (g < h.n ? h.starts[g] : h.len); };
+  std::vector<uint64_t> local(windows, windows + 4 * n_windows), commit(n_windows);
+  uint64_t shift = 0;
+  for (uint64_t w = 0; w < n_windows; ++w) {
+    const uint64_t g1 = std::min(windows[4 * w + 1], h.n), g0 = std::min(windows[4 * w], g1);
+    const uint64_t b0 = byte_of(g0), b1 = byte_of(g1), base = windows[4 * w + 3];
+    if (base < b0 || (w && base - b0 != shift))
+      return fail(FAC_E_INVALID, "every window's base must place the staged text at the same stream offset");
+    shift = base - b0;
+    local[4 * w + 3] = b0;
+    commit[w] = b0 + std::min(windows[4 * w + 2], b1 - b0);
+  }
+  if (*emitted < shift || *emitted - shift > h.len)
+    return fail(FAC_E_INVALID, "*emitted lies outside the staged text");
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e.stream;
+  std::vector<fac_match> owned;
+  std::vector<uint64_t> win_off(n_windows + 1, 0);
+  if (int rc = owned_windows(engine, hay, local.data(), n_windows, threshold, prefilter, stream, owned, &win_off, stats))
+    return rc;
+  fac::StreamReplacePlan plan;
+  if (int rc = fac::replace_stream_plan_device(t, owned, win_off, commit, *emitted - shift, st, plan, err))
+    return fail(rc, err);
+  *out_len = plan.total;
+  if (plan.total >= (1ull << fac::kDocTagShift)) return fail(FAC_E_UNSUPPORTED, "the output would hold 2^40 bytes or more");
+  if (plan.total > device_cap)
+    return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*out_len = bytes needed)");
+  if (int rc = fac::replace_stream_copy_device(h.d_utf8, t, plan, static_cast<uint8_t*>(device_out), err))
+    return fail(rc, err);
+  if (hipStreamSynchronize(st) != hipSuccess) return fail(FAC_E_HIP, "the splice of the stream windows failed");
+  *emitted = plan.e_out + shift;
+  if (n_applied) *n_applied = plan.n_replaced;
+  if (n_skipped) *n_skipped = plan.n_skipped;
   return FAC_OK;
 }
 
@@ -1663,6 +1738,49 @@ uint64_t fac_stream_total(const fac_stream* stream) { return stream ? stream->s-
 uint64_t fac_stream_committed(const fac_stream* stream) { return stream ? fac::stream_committed(*stream->s) : 0; }
 
 void fac_stream_close(fac_stream* stream) {
+  if (!stream) return;
+  fac::stream_close(stream->s);
+  delete stream;
+}
+
+int fac_replace_stream_open(const fac_engine* engine, const fac_replacements* replacements, float threshold,
+                            uint64_t window_bytes, fac_replace_stream** out) {
+  if (!engine || !replacements || !out) return fail(FAC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  if (replacements->t.device != engine->e.device || replacements->t.n_patterns != engine->e.pats.size())
+    return fail(FAC_E_INVALID, "the replacement table was built for another engine");
+  fac_replace_stream* fs = new (std::nothrow) fac_replace_stream();
+  if (!fs) return fail(FAC_E_OOM, "out of host memory");
+  fs->s = fac::stream_open(engine->e, threshold, window_bytes, &replacements->t);
+  *out = fs;
+  return FAC_OK;
+}
+
+int fac_replace_stream_feed(fac_replace_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, uint8_t** out,
+                            uint64_t* out_len) {
+  if (!stream || !out || !out_len || (len && !data)) return fail(FAC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  *out_len = 0;
+  std::string err;
+  fac::StreamCore& s = *stream->s;
+  const int rc = fac::stream_feed(s, data, len, eof != 0, err);
+  if (rc) return fail(rc, err);
+  *out = static_cast<uint8_t*>(std::malloc(std::max<size_t>(s.ready_out.size(), 1)));
+  if (!*out) return fail(FAC_E_OOM, "out of host memory");
+  if (!s.ready_out.empty()) std::memcpy(*out, s.ready_out.data(), s.ready_out.size());
+  *out_len = s.ready_out.size();
+  s.ready_out.clear();
+  return FAC_OK;
+}
+
+uint64_t fac_replace_stream_written(const fac_replace_stream* stream) { return stream ? stream->s->written : 0; }
+
+void fac_replace_stream_counts(const fac_replace_stream* stream, uint64_t* applied, uint64_t* skipped) {
+  if (applied) *applied = stream ? stream->s->applied : 0;
+  if (skipped) *skipped = stream ? stream->s->skipped : 0;
+}
+
+void fac_replace_stream_close(fac_replace_stream* stream) {
   if (!stream) return;
   fac::stream_close(stream->s);
   delete stream;

@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <condition_variable>
 #include <cstdint>
 #include <memory>
 #include <mutex>
@@ -547,6 +548,29 @@ int replace_plan_device(const Batch& b, const ReplaceTable& t, const fac_match* 
 int replace_copy_device(const Batch& b, const ReplaceTable& t, const fac_match* d_recs, const uint64_t* d_doc_off,
                         const ReplacePlan& plan, uint8_t* d_out, std::string& err);
 
+// The plan of a run of consecutive stream windows (fac.h fac_replace_windows_staged_device, the
+// replace stream's tasks; stream.rs:465-517 + ReplaceCursor::emit_window, :645-705): the run's source
+// range [e_in, e_out) of the resident text is one document of replace_copy_kernel. d_recs holds the
+// records rebased to e_in, d_view that document's {byte range, record range, output range} (d_out_off
+// points at the last pair).
+struct StreamReplacePlan : ReplacePlan {
+  fac_match* d_recs = nullptr;
+  uint64_t* d_view = nullptr;
+  uint64_t e_out = 0;      // ReplaceCursor::emitted after the run's last window
+  uint64_t n_skipped = 0;  // records the guard `match_start < emitted` skipped (:671)
+};
+// recs: the owned records of the windows in window order (sorted here by (start, end) within a window
+// where the ranking left them otherwise, stream.rs:515), win_off their CSR index (n_windows + 1),
+// commit each window's commit point, e_in the cursor on entry; every offset is a byte of the resident
+// text. Uploads them, runs the carry chain over the windows and the per-record plan on s;
+// synchronises once to read total, e_out and the counts back.
+int replace_stream_plan_device(const ReplaceTable& t, std::vector<fac_match>& recs, const std::vector<uint64_t>& win_off,
+                               const std::vector<uint64_t>& commit, uint64_t e_in, hipStream_t s, StreamReplacePlan& plan,
+                               std::string& err);
+// Writes the plan.total output bytes, spliced from d_text, to d_out (asynchronous on plan.s).
+int replace_stream_copy_device(const uint8_t* d_text, const ReplaceTable& t, const StreamReplacePlan& plan, uint8_t* d_out,
+                               std::string& err);
+
 #if defined(__HIPCC__)
 // The 16 output bytes a lane of an output-stationary byte mover owns (replace_copy_kernel,
 // piece_copy_kernel), little-endian in two registers, filled run by run.
@@ -788,9 +812,21 @@ struct StreamCore {
   uint64_t handed = 0;  // commit point of the last window whose matches were handed out
   int failed = 0;
   std::string fail_msg;
+  uint64_t batch_bytes = 32ull << 20;  // text a task collects before it is dispatched (FAC_STREAM_BATCH_BYTES)
+  // replace mode (fac_replace_stream_*): the table, the output ready to hand out, the totals of the
+  // tasks handed out, and ReplaceCursor::emitted (stream.rs:645-648) as it passes from task to task:
+  // cur_emitted is the cursor after task cur_seq - 1, and task cur_seq plans next
+  const ReplaceTable* table = nullptr;
+  std::vector<uint8_t> ready_out;
+  uint64_t written = 0, applied = 0, skipped = 0;
+  std::mutex cur_mu;
+  std::condition_variable cur_cv;
+  uint64_t cur_seq = 0, cur_emitted = 0;
+  bool cur_failed = false;
 };
 
-StreamCore* stream_open(const Engine& e, float threshold, uint64_t window);
+// table: NULL for a search stream; else the stream replaces (the table outlives the stream)
+StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table = nullptr);
 int stream_feed(StreamCore& s, const uint8_t* data, uint64_t len, bool eof, std::string& err);
 void stream_close(StreamCore* s);
 uint64_t stream_committed(const StreamCore& s);  // commit point of the windows handed out so far
@@ -816,12 +852,15 @@ struct WinOwn {
   uint64_t byte_base, commit, base;
 };
 constexpr uint32_t kWinTagShift = 40;
+// win_off (optional): the CSR index of the windows into `out`, wins.size() + 1 entries
 void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std::vector<WinOwn>& wins,
-                        std::vector<fac_match>& out);
+                        std::vector<fac_match>& out, std::vector<uint64_t>* win_off = nullptr);
 // api.cpp: a batch of stream windows (g_begin, g_end, commit_bytes, base) x n of a whole staged ASCII
 // haystack searched in one pass; FAC_E_UNSUPPORTED when the batch does not qualify (see there)
+// win_off (optional): the CSR index of the windows into `owned`, n_windows + 1 entries
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
-                         bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err);
+                         bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
+                         std::vector<uint64_t>* win_off = nullptr);
 // merged bitap windows (prefilter.rs:319-342) of a text view of a staged haystack (view.ascii:
 // bytes [text_base, text_base + n) of h.d_utf8; else graphemes [text_base, text_base + n)); windows
 // in the view's local grapheme coordinates

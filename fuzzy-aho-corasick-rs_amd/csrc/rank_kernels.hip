@@ -649,8 +649,9 @@ int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t
 // sorted().non_overlapping() and the matches starting before its commit point, rebased to stream
 // offsets (stream.rs:262-297), appended to `out` in window order with the tag cleared.
 void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std::vector<WinOwn>& wins,
-                        std::vector<fac_match>& out) {
+                        std::vector<fac_match>& out, std::vector<uint64_t>* win_off) {
   const size_t nw = wins.size();
+  if (win_off) win_off->assign(nw + 1, out.size());
   std::vector<uint64_t> first(nw + 1, 0);
   auto tag = [](const fac_match& m) { return (uint32_t)(m.start >> kWinTagShift); };
   constexpr uint64_t low = (1ull << kWinTagShift) - 1;
@@ -668,6 +669,7 @@ void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std
   }
   std::vector<fac_match> v;
   for (size_t w = 0; w < nw; ++w) {
+    if (win_off) (*win_off)[w] = out.size();
     if (first[w] == first[w + 1]) continue;
     v.assign(by.begin() + (ptrdiff_t)first[w], by.begin() + (ptrdiff_t)first[w + 1]);
     std::sort(v.begin(), v.end(), RankCmpHost{e.pat_bytes.data(), 1});
@@ -680,6 +682,7 @@ void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std
       out.push_back(m);
     }
   }
+  if (win_off) (*win_off)[nw] = out.size();
 }
 
 namespace {

@@ -16,6 +16,12 @@
 // sorted().non_overlapping() and keeps the matches it owns (stream.rs:262-297). Batch k + 1's
 // copies and kernels overlap batch k's (double buffering) while the host cuts the windows of batch
 // k + 2. Finished batches are handed out strictly in window order.
+//
+// Replace mode (fac_replace_stream_*; stream.rs:465-517 + ReplaceCursor::emit_window, :645-705): a
+// task's text stays on the device after the search, its owned records go back up, and the plan and
+// copy kernels of replace_kernels.hip splice the task's output, which is copied to the host and
+// handed out in stream order. A task's plan starts from its predecessor's cursor (`emitted`), so
+// after its search a worker waits for task k - 1's plan; the searches still overlap.
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +48,9 @@ struct StreamTask {
   std::vector<StreamWin> wins;
   std::vector<fac_match> res;  // owned matches of every window, in window order, absolute offsets
   std::vector<uint8_t> res_text;
+  uint64_t seq = 0;          // dispatch order (replace mode: the cursor's order)
+  std::vector<uint8_t> out;  // replace mode: the task's spliced output
+  uint64_t applied = 0, skipped = 0;
   int rc = FAC_OK;
   std::string err;
   bool done = false;
@@ -63,7 +72,8 @@ std::mutex g_done_mu;  // guards StreamTask::done across workers and the feeding
 std::condition_variable g_done_cv;
 
 // Search one window (text[off, off + len) of the task) and keep the matches it owns (stream.rs:262-297).
-int search_one_window(const StreamCore& s, StreamWorker& w, const StreamTask& t, const StreamWin& win,
+// shift: the stream offset the records are rebased to, less the window's offset in the task's text
+int search_one_window(const StreamCore& s, StreamWorker& w, const StreamTask& t, const StreamWin& win, uint64_t shift,
                       std::vector<fac_match>& owned, std::string& err) {
   Haystack h;
   int rc = stage_haystack(*s.e, t.text.data() + win.off, win.len, h, err, -1, w.stream);
@@ -84,8 +94,8 @@ int search_one_window(const StreamCore& s, StreamWorker& w, const StreamTask& t,
       for (const fac_match& m : res) {
         if (m.start >= win.commit) continue;
         fac_match a = m;
-        a.start += t.base + win.off;
-        a.end += t.base + win.off;
+        a.start += shift + win.off;
+        a.end += shift + win.off;
         owned.push_back(a);
       }
   }
@@ -93,49 +103,150 @@ int search_one_window(const StreamCore& s, StreamWorker& w, const StreamTask& t,
   return rc;
 }
 
+// Replace mode: the splice of a task. d_text: the task's text if the search left it on the device,
+// else it is uploaded here. owned / win_off: the task's owned records at offsets of its text, in
+// window order, and their CSR index. Waits for the predecessor's cursor, plans from it, copies the
+// output back and passes the cursor on -- also when the task failed, so no successor waits forever.
+void splice_task(StreamCore& s, StreamWorker& w, StreamTask& t, const uint8_t* d_text, std::vector<fac_match>& owned,
+                 const std::vector<uint64_t>& win_off) {
+  void* up = nullptr;
+  if (!t.rc && !d_text && !t.text.empty()) {
+    hipError_t he = hipSuccess;
+    up = call_scratch_take(t.text.size(), w.stream, &he);
+    if (he != hipSuccess || !up) {
+      up = nullptr;
+      t.rc = FAC_E_OOM;
+      t.err = std::string("hipMalloc: ") + hipGetErrorString(he);
+    } else if (hipMemcpyAsync(up, t.text.data(), t.text.size(), hipMemcpyHostToDevice, w.stream) != hipSuccess) {
+      t.rc = FAC_E_HIP;
+      t.err = "upload of a stream task's text failed";
+    }
+    d_text = static_cast<const uint8_t*>(up);
+  }
+  uint64_t emitted = 0;
+  {
+    std::unique_lock<std::mutex> lk(s.cur_mu);
+    s.cur_cv.wait(lk, [&] { return s.cur_seq == t.seq; });
+    emitted = s.cur_emitted;
+    if (s.cur_failed && !t.rc) {
+      t.rc = FAC_E_INTERNAL;
+      t.err = "an earlier task of the stream failed";
+    }
+  }
+  if (!t.rc) {
+    std::vector<uint64_t> commit(t.wins.size());
+    for (size_t i = 0; i < t.wins.size(); ++i) commit[i] = t.wins[i].off + t.wins[i].commit;
+    StreamReplacePlan plan;
+    t.rc = replace_stream_plan_device(*s.table, owned, win_off, commit, emitted - t.base, w.stream, plan, t.err);
+    if (!t.rc && plan.total >= (1ull << kDocTagShift)) {
+      t.rc = FAC_E_UNSUPPORTED;
+      t.err = "a stream task's output would hold 2^40 bytes or more";
+    }
+    if (!t.rc && plan.total) {
+      hipError_t he = hipSuccess;
+      void* d_out = call_scratch_take(plan.total, w.stream, &he);
+      if (he != hipSuccess || !d_out) {
+        t.rc = FAC_E_OOM;
+        t.err = std::string("hipMalloc: ") + hipGetErrorString(he);
+      } else {
+        t.out.resize(plan.total);
+        t.rc = replace_stream_copy_device(d_text, *s.table, plan, static_cast<uint8_t*>(d_out), t.err);
+        if (!t.rc && (hipMemcpyAsync(t.out.data(), d_out, plan.total, hipMemcpyDeviceToHost, w.stream) != hipSuccess ||
+                      hipStreamSynchronize(w.stream) != hipSuccess)) {
+          t.rc = FAC_E_HIP;
+          t.err = "copy of a stream task's output failed";
+        }
+        call_scratch_give(d_out, w.stream);
+      }
+    }
+    if (!t.rc) {
+      emitted = t.base + plan.e_out;
+      t.applied = plan.n_replaced;
+      t.skipped = plan.n_skipped;
+    }
+  }
+  if (up) {
+    (void)hipStreamSynchronize(w.stream);  // (an error path may leave the upload in flight)
+    call_scratch_give(up, w.stream);
+  }
+  {
+    std::lock_guard<std::mutex> lk(s.cur_mu);
+    s.cur_emitted = emitted;
+    s.cur_failed = s.cur_failed || t.rc != FAC_OK;
+    s.cur_seq = t.seq + 1;
+  }
+  s.cur_cv.notify_all();
+}
+
 // Search a batch of windows. An all-ASCII batch is staged once and searched as one launch over its
 // windows (stream_windows_batch: each window its own text, ranked and cut per window); otherwise each
 // window is staged and searched alone (its grapheme segmentation depends on where its text starts
 // and ends).
-void run_window_task(const StreamCore& s, StreamWorker& w, StreamTask& t) {
+void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
+  const bool replace = s.table != nullptr;
+  // replace mode keeps the records at offsets of the task's text, which the splice reads
+  const uint64_t shift = replace ? 0 : t.base;
   std::vector<fac_match> owned;
-  bool batched = false;
+  std::vector<uint64_t> win_off(t.wins.size() + 1, 0);
+  bool batched = false, staged = false;
+  Haystack h;  // the whole task's text (the batched path); resident until the splice is done
   if (t.wins.size() > 1 && ascii_only(t.text.data(), t.text.size())) {
-    Haystack h;
     t.rc = stage_haystack(*s.e, t.text.data(), t.text.size(), h, t.err, 1, w.stream);
+    staged = true;
     if (!t.rc) {
       std::vector<uint64_t> wins(4 * t.wins.size());
       for (size_t i = 0; i < t.wins.size(); ++i) {
         wins[4 * i] = t.wins[i].off;
         wins[4 * i + 1] = t.wins[i].off + t.wins[i].len;
         wins[4 * i + 2] = t.wins[i].commit;
-        wins[4 * i + 3] = t.base + t.wins[i].off;
+        wins[4 * i + 3] = shift + t.wins[i].off;
       }
       const int rc = stream_windows_batch(*s.e, h, wins.data(), t.wins.size(), s.threshold, false, w.stream, owned,
-                                          nullptr, t.err);
+                                          nullptr, t.err, &win_off);
       if (rc != FAC_E_UNSUPPORTED) {
         t.rc = rc;
         batched = true;
       }
     }
-    free_haystack(h);
     if (t.rc) batched = true;  // a staging failure is the task's error
   }
   if (!batched) {
     owned.clear();
-    for (const StreamWin& win : t.wins)
-      if ((t.rc = search_one_window(s, w, t, win, owned, t.err))) break;
+    for (size_t i = 0; i < t.wins.size(); ++i) {
+      win_off[i] = owned.size();
+      if ((t.rc = search_one_window(s, w, t, t.wins[i], shift, owned, t.err))) break;
+    }
+    win_off[t.wins.size()] = owned.size();
   }
-  if (!t.rc)
+  if (replace) {
+    splice_task(s, w, t, staged && !t.rc ? h.d_utf8 : nullptr, owned, win_off);
+  } else if (!t.rc) {
     for (const fac_match& m : owned) {
       t.res.push_back(m);
       t.res_text.insert(t.res_text.end(), t.text.begin() + (ptrdiff_t)(m.start - t.base),
                         t.text.begin() + (ptrdiff_t)(m.end - t.base));
     }
+  }
+  if (staged) free_haystack(h);
   std::vector<uint8_t>().swap(t.text);
 }
 
-void worker_loop(const StreamCore* s, StreamWorker* w) {
+// Replace mode, after a task threw: if its splice did not pass the cursor on, step over the task once
+// its predecessor has finished (it will: it was dispatched earlier, to the other worker), so that the
+// successor does not wait forever.
+void pass_cursor(StreamCore& s, const StreamTask& t) {
+  if (!s.table) return;
+  {
+    std::unique_lock<std::mutex> lk(s.cur_mu);
+    s.cur_cv.wait(lk, [&] { return s.cur_seq >= t.seq; });
+    if (s.cur_seq > t.seq) return;
+    s.cur_failed = true;
+    s.cur_seq = t.seq + 1;
+  }
+  s.cur_cv.notify_all();
+}
+
+void worker_loop(StreamCore* s, StreamWorker* w) {
   (void)hipSetDevice(s->e->device);
   scratch_bind(&w->scratch);
   for (;;) {
@@ -152,9 +263,11 @@ void worker_loop(const StreamCore* s, StreamWorker* w) {
     } catch (const std::bad_alloc&) {
       t->rc = FAC_E_OOM;
       t->err = "out of host memory while searching a stream window";
+      pass_cursor(*s, *t);
     } catch (const std::exception& ex) {
       t->rc = FAC_E_INTERNAL;
       t->err = std::string("stream window: ") + ex.what();
+      pass_cursor(*s, *t);
     }
     {
       std::lock_guard<std::mutex> lk(g_done_mu);
@@ -182,6 +295,12 @@ int collect(StreamCore& s, bool all, std::string& err) {
     }
     s.ready.insert(s.ready.end(), t->res.begin(), t->res.end());
     s.ready_text.insert(s.ready_text.end(), t->res_text.begin(), t->res_text.end());
+    if (!s.failed) {
+      s.ready_out.insert(s.ready_out.end(), t->out.begin(), t->out.end());
+      s.written += t->out.size();
+      s.applied += t->applied;
+      s.skipped += t->skipped;
+    }
     delete t;
   }
   if (s.failed) {
@@ -204,6 +323,7 @@ int dispatch(StreamCore& s, StreamTask* t, std::string& err) {
       return rc;
     }
   }
+  t->seq = s.seq;
   StreamWorker* w = s.workers[s.seq++ % StreamCore::depth];
   s.inflight.push_back(t);
   {
@@ -219,7 +339,7 @@ int dispatch(StreamCore& s, StreamTask* t, std::string& err) {
 // window plus whole 64 KiB reads (the last one partial at the end of the input); fed in larger pieces,
 // the buffer is cut the same way. Consecutive windows join the pending batch, dispatched once it holds
 // kBatchBytes of text or the input ends.
-constexpr uint64_t kRead = 64 * 1024, kBatchBytes = 32ull << 20;
+constexpr uint64_t kRead = 64 * 1024;
 
 int flush_batch(StreamCore& s, std::string& err) {
   if (!s.pending) return FAC_OK;
@@ -269,7 +389,7 @@ int pump(StreamCore& s, bool eof, std::string& err) {
     at += commit;
     s.base += commit;
     s.carry = len - commit;
-    if (t->text.size() >= kBatchBytes)
+    if (t->text.size() >= s.batch_bytes)
       if (int rc = flush_batch(s, err)) {
         s.buf.erase(s.buf.begin(), s.buf.begin() + (ptrdiff_t)at);
         return rc;
@@ -292,10 +412,13 @@ int stream_feed(StreamCore& s, const uint8_t* data, uint64_t len, bool eof, std:
   return pump(s, eof, err);
 }
 
-StreamCore* stream_open(const Engine& e, float threshold, uint64_t window) {
+StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table) {
   StreamCore* s = new StreamCore();
   s->e = &e;
   s->threshold = threshold;
+  s->table = table;
+  if (const char* v = diag_env("FAC_STREAM_BATCH_BYTES"))  // diagnostics: task boundaries at small sizes
+    s->batch_bytes = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
   if (window) s->window = window;
   s->overlap = e.max_match_graphemes + 1;  // stream_overlap (stream.rs:256-258)
   (void)hipSetDevice(e.device);

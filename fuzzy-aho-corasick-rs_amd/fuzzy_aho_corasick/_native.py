@@ -195,6 +195,17 @@ SIGNATURES = {
     "fac_stream_committed": (ctypes.c_uint64, [ctypes.c_void_p]),
     "fac_stream_close": (None, [ctypes.c_void_p]),
     "fac_buffer_free": (None, [ctypes.c_void_p]),
+    "fac_replace_windows_staged_device": (ctypes.c_int, [_engine_p, _hay_p, _u64p, ctypes.c_uint64, ctypes.c_void_p,
+                                                         ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, _u64p,
+                                                         ctypes.c_void_p, ctypes.c_uint64, _u64p, _u64p, _u64p,
+                                                         _P(fac_stats)]),
+    "fac_replace_stream_open": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint64,
+                                               _P(ctypes.c_void_p)]),
+    "fac_replace_stream_feed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int32,
+                                               _P(_P(ctypes.c_uint8)), _u64p]),
+    "fac_replace_stream_written": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "fac_replace_stream_counts": (None, [ctypes.c_void_p, _u64p, _u64p]),
+    "fac_replace_stream_close": (None, [ctypes.c_void_p]),
     "fac_prefilter_windows": (ctypes.c_int64, [_engine_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_float,
                                                _u64p, ctypes.c_uint64]),
     "fac_engine_num_nodes": (ctypes.c_uint64, [_engine_p]),

@@ -265,7 +265,20 @@ class FuzzyAhoCorasick:
         Every owned match (per window: sorted().non_overlapping(), start < commit, ordered by
         (start, end)) is replaced by `callback(m)` (a str; None keeps the matched text) unless it
         starts inside text already written; everything else is copied through. Text before the
-        stream's commit point is written as soon as it is committed. Returns the bytes written."""
+        stream's commit point is written as soon as it is committed. Returns the bytes written.
+        `callback` may be a ReplacementTable or a list with one entry per pattern (str / bytes, None =
+        keep, Wrap = a template): the splice then runs on the device (fac_replace_stream_*). A
+        callable is called per match on the host."""
+        if not callable(callback):
+            table = callback if isinstance(callback, ReplacementTable) else ReplacementTable(self, callback)
+            st = _ReplaceStream(self, table, threshold, window)
+            while True:
+                chunk = reader.read(READ_CHUNK)
+                out = st.feed(chunk or b"", eof=not chunk)
+                if out:
+                    writer.write(out)
+                if not chunk:
+                    return st.written()
         st = _Stream(self, threshold, window)
         pending = bytearray()  # stream bytes [emitted, read) not yet written
         emitted = written = 0
@@ -301,7 +314,8 @@ class FuzzyAhoCorasick:
             emit(ms, max(emitted, st.committed()))
 
     def replace_stream_parallel(self, reader, writer, threads: int, threshold: float, callback) -> int:
-        """stream.rs:533-638: same output as replace_stream (windows are pipelined on the device)."""
+        """stream.rs:533-638: same output as replace_stream (windows are pipelined on the device);
+        `callback` as there."""
         return self.replace_stream(reader, writer, threshold, callback)
 
     def apply_on_device(self, matches: FuzzyMatches, order: Order, overlap: Overlap) -> FuzzyMatches:
@@ -686,6 +700,46 @@ class _Stream:
             self._h = None
 
 
+class _ReplaceStream:
+    """fac_replace_stream: WindowReader + per-window search + the ReplaceCursor splice on the GPU
+    (stream.rs:465-517, 645-705) against a ReplacementTable."""
+
+    def __init__(self, engine: "FuzzyAhoCorasick", table: "ReplacementTable", threshold: float, window: int = 0):
+        h = ctypes.c_void_p()
+        rc = _native.lib.fac_replace_stream_open(engine._h, table._h, f32(threshold), window, ctypes.byref(h))
+        if rc:
+            _raise(rc)
+        self._h = h
+        self.engine, self.table = engine, table  # (the table must outlive the stream)
+
+    def feed(self, data: bytes, eof: bool = False) -> bytes:
+        """The output completed so far, in stream order."""
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        n = ctypes.c_uint64()
+        rc = _native.lib.fac_replace_stream_feed(self._h, data, len(data), int(eof), ctypes.byref(out), ctypes.byref(n))
+        if rc:
+            _raise(rc)
+        try:
+            return ctypes.string_at(out, n.value) if n.value else b""
+        finally:
+            _native.lib.fac_buffer_free(out)
+
+    def written(self) -> int:
+        return int(_native.lib.fac_replace_stream_written(self._h))
+
+    def counts(self) -> Tuple[int, int]:
+        """(records replaced, records skipped by the cursor's guard) in the output handed out so far."""
+        a, k = ctypes.c_uint64(), ctypes.c_uint64()
+        _native.lib.fac_replace_stream_counts(self._h, ctypes.byref(a), ctypes.byref(k))
+        return int(a.value), int(k.value)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _native.lib is not None:
+            _native.lib.fac_replace_stream_close(h)
+            self._h = None
+
+
 class StagedHaystack:
     """A haystack staged into HBM once (fac_haystack_stage) and searched many times.
 
@@ -881,6 +935,35 @@ class StagedHaystack:
             if rc:
                 _raise(rc)
             return out, n.value, st
+
+    def replace_windows_device(self, windows, table: "ReplacementTable", threshold: float, prefilter: bool, out,
+                               emitted: int = 0, stream=None):
+        """fac_replace_windows_staged_device: streaming replace (stream.rs:465-517 + ReplaceCursor::
+        emit_window, :645-705) of a run of consecutive stream windows, `windows` as in
+        stream_windows_device, spliced on the device from the staged text into `out` (a uint8 CUDA
+        tensor). `emitted`: the cursor on entry (what the previous call returned, 0 at the start of a
+        stream). Returns (the filled part of `out`, the cursor on return, records applied, records
+        skipped, fac_stats). FAC_E_OUTPUT_CAPACITY is raised as DeviceError with `.needed` bytes and
+        `.emitted`, the cursor the call left, when `out` is too small (nothing is written, the cursor
+        does not move)."""
+        import numpy as np
+        arr = np.ascontiguousarray(np.asarray(windows, dtype=np.uint64).reshape(-1, 4))
+        wp = arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        em = ctypes.c_uint64(emitted)
+        n, na, ns = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        st = _native.fac_stats()
+        cap = out.numel() * out.element_size()
+        rc = _native.lib.fac_replace_windows_staged_device(
+            self.engine._h, self._h, wp, len(arr), table._h, f32(threshold), int(prefilter), ctypes.c_void_p(stream or 0),
+            ctypes.byref(em), ctypes.c_void_p(out.data_ptr() if cap else 0), cap, ctypes.byref(n), ctypes.byref(na),
+            ctypes.byref(ns), ctypes.byref(st))
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed, ex.emitted = int(n.value), int(em.value)
+                raise
+        return out[: n.value], int(em.value), int(na.value), int(ns.value), st
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -1396,5 +1479,5 @@ class FuzzyReplacer:
         return self.engine.replace_batch(texts, opts, self._device_table())
 
     def replace_stream(self, reader, writer, threshold: float) -> int:
-        """replacer.rs:35-44"""
-        return self.engine.replace_stream(reader, writer, threshold, self._callback)
+        """replacer.rs:35-44, spliced on the device (fac_replace_stream_*)."""
+        return self.engine.replace_stream(reader, writer, threshold, self._device_table())

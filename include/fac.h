@@ -33,7 +33,9 @@
  * FAC_GRAPHEME_LIMIT, ...) only when FAC_DIAGNOSTICS=1 is set; otherwise the search path depends
  * on the arguments alone. FAC_OUT_CAP0, FAC_ECAP0 and FAC_SPILL_CAP0 (each >= 1) set the first size
  * of a search pass's record buffer, per-window best lists and spill list, whose overflow re-runs
- * the pass with a larger buffer: results never depend on them.
+ * the pass with a larger buffer: results never depend on them. FAC_STREAM_BATCH_BYTES (>= 1) replaces
+ * the 32 MiB of text a stream (fac_stream_*, fac_replace_stream_*) collects into one device task:
+ * results never depend on it either.
  */
 #ifndef FAC_H
 #define FAC_H
@@ -150,6 +152,7 @@ typedef struct fac_stats {
 
 typedef struct fac_engine fac_engine;
 typedef struct fac_haystack fac_haystack;
+typedef struct fac_replacements fac_replacements; /* a replacement table: "Batched replace" below */
 
 /* Last error text of the calling thread ("" if none). */
 const char* fac_last_error(void);
@@ -298,6 +301,33 @@ int fac_stream_windows_staged_device(const fac_engine* engine, const fac_haystac
                                      uint64_t n_windows, float threshold, int32_t prefilter, void* stream, void* device_out,
                                      uint64_t device_cap, uint64_t* n_out, fac_stats* stats);
 
+/* Streaming replace of a run of consecutive windows of a staged haystack, spliced on the device:
+ * FuzzyReplacer::replace_stream's loop body (replacer.rs:35-44 over stream.rs:480-490) for the
+ * windows given, with callback(m) = the table's entry for m.pattern_index (plain, "keep" or template).
+ * `windows` holds fac_stream_windows_staged_device's 4-tuples, and the owned records come from that
+ * call's code path (batched where the run qualifies, window by window otherwise), each window's
+ * sorted by (start, end) (window_replace_matches, stream.rs:496-517). base - byte start of g_begin
+ * must be the same for every window: it is the stream offset of the haystack's byte 0
+ * (FAC_E_INVALID otherwise, and for an *emitted outside the staged text). Window w + 1's text starts
+ * at window w's commit point, as the reader cuts them (stream.rs:140-158).
+ * The windows are then walked with ReplaceCursor::emit_window (stream.rs:645-705): *emitted is
+ * ReplaceCursor::emitted on entry (0 for the first call of a stream) and on return; a record that
+ * starts before the cursor is skipped (:671), the others are replaced, the text between is copied
+ * through from the staged haystack (it does not cross the host again), and each window flushes up to
+ * its commit point (:696-702). The call writes stream bytes [*emitted on entry, *emitted on return),
+ * spliced, to device_out (device_cap bytes on the engine's device): *out_len bytes, valid UTF-8;
+ * *n_applied / *n_skipped (may be NULL) count the records replaced and the records the guard
+ * skipped. Consecutive calls that carry *emitted give the output of one call over all the windows.
+ * FAC_E_OUTPUT_CAPACITY: device_cap is too small; nothing was written, *out_len holds the bytes
+ * needed and *emitted is unchanged. FAC_E_INVALID for a table of another pattern count or device,
+ * FAC_E_UNSUPPORTED for an output of 2^40 bytes or more; other errors as
+ * fac_stream_windows_staged_device. */
+int fac_replace_windows_staged_device(const fac_engine* engine, const fac_haystack* hay, const uint64_t* windows,
+                                      uint64_t n_windows, const fac_replacements* replacements, float threshold,
+                                      int32_t prefilter, void* stream, uint64_t* emitted, void* device_out,
+                                      uint64_t device_cap, uint64_t* out_len, uint64_t* n_applied, uint64_t* n_skipped,
+                                      fac_stats* stats);
+
 /* Prefiltered::raw on a staged haystack (prefilter.rs:146-155, 304-374): the bitap scan and the
  * window merge run on the device-resident text, each merged window is re-searched as its own
  * sub-haystack, results are best-per-(start, end, pattern) and sorted. Falls back to the full
@@ -429,7 +459,6 @@ int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* b
  * empty = deletion), each valid UTF-8 on its own; keep: NULL, or one byte per pattern, non-zero = keep (its bytes are
  * ignored). Validated and uploaded once. FAC_E_INVALID: n_patterns differs from the engine's, bad
  * offsets or invalid UTF-8; FAC_E_UNSUPPORTED: 2^32 bytes of replacements or more. */
-typedef struct fac_replacements fac_replacements;
 int fac_replacements_create(const fac_engine* engine, const uint8_t* utf8, const uint64_t* offsets,
                             const uint8_t* keep, uint64_t n_patterns, fac_replacements** out);
 void fac_replacements_free(fac_replacements* replacements);
@@ -618,6 +647,31 @@ uint64_t fac_stream_total(const fac_stream* stream);
 uint64_t fac_stream_committed(const fac_stream* stream);
 void fac_stream_close(fac_stream* stream);
 void fac_buffer_free(void* p);
+
+/* Streaming replace against a replacement table: FuzzyReplacer::replace_stream (replacer.rs:35-44;
+ * stream.rs:465-492 with ReplaceCursor::emit_window, :645-705) with callback(m) = the table's entry
+ * for m.pattern_index. Windows are cut exactly as fac_stream_feed cuts them (64 KiB reads, the valid
+ * UTF-8 prefix, the commit point at the overlap-th grapheme from the end, window growth;
+ * stream.rs:102-158), so bytes after the last window's valid prefix are never written
+ * (stream.rs:117-131). Each task of consecutive windows keeps its text on the device after the
+ * search; its owned records are uploaded, the splice is planned and copied there
+ * (fac_replace_windows_staged_device's kernels), and the output comes back. Two tasks are in flight:
+ * their searches overlap, and a task's plan waits only for its predecessor's cursor. Each feed
+ * returns the output completed so far (`*out`, *out_len bytes, fac_buffer_free), strictly in stream
+ * order; pass eof = 1 (data may be empty) once the input has ended. The table must outlive the
+ * stream. FAC_E_INVALID for a table of another pattern count or device; other errors as
+ * fac_stream_feed. */
+typedef struct fac_replace_stream fac_replace_stream;
+int fac_replace_stream_open(const fac_engine* engine, const fac_replacements* replacements, float threshold,
+                            uint64_t window_bytes, fac_replace_stream** out);
+int fac_replace_stream_feed(fac_replace_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, uint8_t** out,
+                            uint64_t* out_len);
+/* Bytes handed out so far: replace_stream's return value (ReplaceCursor::written) after the feed with eof. */
+uint64_t fac_replace_stream_written(const fac_replace_stream* stream);
+/* Records replaced, and records skipped because they start inside text an earlier window's match
+ * already wrote (stream.rs:671-675), in the output handed out so far. Either pointer may be NULL. */
+void fac_replace_stream_counts(const fac_replace_stream* stream, uint64_t* applied, uint64_t* skipped);
+void fac_replace_stream_close(fac_replace_stream* stream);
 
 /* Diagnostics: the merged candidate windows (grapheme ranges [start, end)) of the bitap
  * pre-filter for `threshold` (prefilter.rs:319-342). Returns the window count (writes up to `cap`
