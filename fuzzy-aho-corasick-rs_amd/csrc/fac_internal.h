@@ -300,6 +300,9 @@ struct SearchParams {
   // dense start-level key bitmaps (rc_dense_*_kernel, search_kernels.hip): rank table, alphabet size,
   // "final without records" and "cached" bits over the keys of ranked characters; null: none
   const uint32_t* rc_dense;
+  // diagnostics (FAC_RC_FULL_SWEEP=1): the build epilogue sweeps the dedup table for final keys too
+  // and re-reads every slot in both writing passes (the epilogue before the single sweep; same pool)
+  int32_t rc_full_sweep;
 };
 
 constexpr unsigned ERR_QUEUE = 1u, ERR_VISITED = 2u, ERR_EMIT = 4u, ERR_HALO = 8u, ERR_OUT = 16u, ERR_SPILL = 32u;

@@ -3865,28 +3865,36 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
           const uint32_t nq = qlen - qhead;
           // live dedup entries: a key is only met again at its own j, and every future state's j is
           // at least the smallest j in the queue (j never decreases along a path)
+          // A final key (empty queue) has no future state, so no dedup entry is live: nv = jlive =
+          // ncheck = 0 without a look at the table. FAC_RC_FULL_SWEEP=1 (A/B) sweeps it all the same.
+          const bool full = P.rc_full_sweep != 0;
+          const bool sweep = nq != 0 || full;  // wave-uniform
           uint32_t jmin = 0xFFFFu;
-          for (uint32_t i = lane; i < nq; i += 64) jmin = min(jmin, s_q[(qhead + i) & (QCAP - 1)].jm & 0xFFFFu);
-          jmin = wave_min_u32(jmin);
-          auto live = [&](const KState& k) { return k.node != EMPTY && (k.jm & 0xFFFFu) >= jmin; };
           uint32_t nv = 0, jlive = 0;  // 1 + the largest j among the live entries (0: none)
-          // each lane's VCAP/64 slots, their live bits kept; the entries are read from LDS again by the
-          // writing passes below (held in registers, the 8 slots' 32 VGPRs made this the kernel's
-          // register peak and pushed loop state into scratch)
+          // each lane's VCAP/64 slots: their live bits are kept, and of those the check bits (j + 1 <=
+          // jbeam[0]: a live entry has j + 1 <= jlive, so that is j + 1 <= jcheck below). The writing
+          // passes read from LDS again only the entries they store (held in registers, the 8 slots' 32
+          // VGPRs made this the kernel's register peak and pushed loop state into scratch)
           constexpr uint32_t NSL = VCAP ? VCAP / 64 : 1;
-          uint32_t lmask = 0;
-          if constexpr (VCAP > 0) {
+          uint32_t lmask = 0, cmask = 0;
+          if (sweep) {
+            for (uint32_t i = lane; i < nq; i += 64) jmin = min(jmin, s_q[(qhead + i) & (QCAP - 1)].jm & 0xFFFFu);
+            jmin = wave_min_u32(jmin);
+            if constexpr (VCAP > 0) {
 #pragma unroll
-            for (uint32_t u = 0; u < NSL; ++u) {
-              const KState kvu = s_vis[u * 64 + lane];
-              const bool lv = live(kvu);
-              lmask |= (lv ? 1u : 0u) << u;
-              nv += (uint32_t)__popcll(__ballot(lv));
-              jlive = max(jlive, lv ? (kvu.jm & 0xFFFFu) + 1u : 0u);
+              for (uint32_t u = 0; u < NSL; ++u) {
+                const KState kvu = s_vis[u * 64 + lane];
+                const uint32_t j = kvu.jm & 0xFFFFu;
+                const bool lv = kvu.node != EMPTY && j >= jmin;
+                lmask |= (lv ? 1u : 0u) << u;
+                cmask |= (lv && j + 1u <= jbeam[0] ? 1u : 0u) << u;
+                nv += (uint32_t)__popcll(__ballot(lv));
+                jlive = max(jlive, lv ? j + 1u : 0u);
+              }
             }
+            jlive = wave_inclusive_max(jlive);
+            jlive = shfl_u32(jlive, 63);
           }
-          jlive = wave_inclusive_max(jlive);
-          jlive = shfl_u32(jlive, 63);
           bool bad = (wave_or(err) & (ERR_QUEUE | ERR_VISITED | ERR_EMIT)) != 0 || EL.n > P.rc_emax || nv > P.rc_vmax;
           if (bad && lane == 0) {  // diagnostics (FAC_RC_DEBUG): why keys stay uncached
             const unsigned we = wave_or(err);
@@ -3920,17 +3928,36 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
           uint32_t ncheck = 0;
           if constexpr (VCAP > 0) {
             uint32_t at0 = 0;
-            for (uint32_t pass = 0; pass < 2 && !bad; ++pass) {
+            if (!full) {
+              // one pass per class, skipped when the class is empty wave-wide: no check entries
+              // (jcheck == 0: every key of an unbeamed engine, every final key), or nothing but them
+              for (uint32_t pass = jcheck ? 0u : 1u; pass < 2 && !bad && at0 < nv; ++pass) {
+                const uint32_t pm = pass == 0 ? cmask : lmask & ~cmask;
 #pragma unroll
-              for (uint32_t u = 0; u < NSL; ++u) {
-                const KState kvu = s_vis[u * 64 + lane];
-                const bool chk = (kvu.jm & 0xFFFFu) + 1u <= jcheck;
-                const bool occ = ((lmask >> u) & 1u) && (pass == 0 ? chk : !chk);
-                const uint64_t m = __ballot(occ);
-                if (occ) dst[nq + at0 + prefix_below(m)] = make_uint4(kvu.node, kvu.jm, __float_as_uint(kvu.pen), kvu.packed);
-                at0 += (uint32_t)__popcll(m);
+                for (uint32_t u = 0; u < NSL; ++u) {
+                  const bool occ = (pm >> u) & 1u;
+                  const uint64_t m = __ballot(occ);
+                  if (occ) {
+                    const KState kvu = s_vis[u * 64 + lane];
+                    dst[nq + at0 + prefix_below(m)] = make_uint4(kvu.node, kvu.jm, __float_as_uint(kvu.pen), kvu.packed);
+                  }
+                  at0 += (uint32_t)__popcll(m);
+                }
+                if (pass == 0) ncheck = at0;
               }
-              if (pass == 0) ncheck = at0;
+            } else {  // FAC_RC_FULL_SWEEP: both passes over every slot, each entry read again
+              for (uint32_t pass = 0; pass < 2 && !bad; ++pass) {
+#pragma unroll
+                for (uint32_t u = 0; u < NSL; ++u) {
+                  const KState kvu = s_vis[u * 64 + lane];
+                  const bool chk = (kvu.jm & 0xFFFFu) + 1u <= jcheck;
+                  const bool occ = ((lmask >> u) & 1u) && (pass == 0 ? chk : !chk);
+                  const uint64_t m = __ballot(occ);
+                  if (occ) dst[nq + at0 + prefix_below(m)] = make_uint4(kvu.node, kvu.jm, __float_as_uint(kvu.pen), kvu.packed);
+                  at0 += (uint32_t)__popcll(m);
+                }
+                if (pass == 0) ncheck = at0;
+              }
             }
           }
           EP_LAP(35);
@@ -5652,6 +5679,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   P.rc_kstart = 0;
   P.live_nqmax = 0;
   P.rc_lane_flush = diag_env("FAC_RC_NO_LANE") ? 0 : 1;
+  P.rc_full_sweep = diag_env("FAC_RC_FULL_SWEEP") ? 1 : 0;  // env: A/B knob
   P.dyn_chunks = diag_env("FAC_STATIC_GRID") ? 0 : 1;
   const bool root_out = !e.nodes.empty() && e.nodes[0].out_end > e.nodes[0].out_begin;
   const char* rc_min = diag_env("FAC_RC_MIN");  // env knobs: tests force it on / pin K, A/B turns it off
@@ -6119,23 +6147,25 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     if (P.rc_mode == 1 && diag_env("FAC_RC_DEBUG")) {  // diagnostics: keys, pool use, cached entries
       unsigned long long rcn[2] = {0, 0};
       HIP_TRY(hipMemcpy(rcn, d_rcn.p, sizeof(rcn), hipMemcpyDeviceToHost));
-      auto cached_of = [&](const RcTable& T, uint32_t ne, uint64_t& qsum) -> uint64_t {
+      // fin: of the cached keys, the final ones (empty queue; the build epilogue skips their table sweep)
+      auto cached_of = [&](const RcTable& T, uint32_t ne, uint64_t& qsum, uint64_t& fin) -> uint64_t {
         std::vector<uint32_t> cntv(ne);
         if (ne && hipMemcpy(cntv.data(), T.count, ne * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
         uint64_t c = 0;
         for (uint32_t v : cntv)
-          if (v != EMPTY) ++c, qsum += v;
+          if (v != EMPTY) ++c, qsum += v, fin += v == 0;
         return c;
       };
-      uint64_t q1 = 0;
-      const uint64_t c1 = cached_of(L1, n_ent1, q1);
+      uint64_t q1 = 0, f1 = 0;
+      const uint64_t c1 = cached_of(L1, n_ent1, q1, f1);
       std::string lv;
       for (size_t x = 0; x < Lx.size(); ++x) {
-        uint64_t q = 0;
-        const uint64_t c = cached_of(Lx[x], n_entx[x], q);
-        char b[160];
-        std::snprintf(b, sizeof(b), " | k=%u entries=%u cached=%llu mean_queue=%.1f", Lx[x].k, n_entx[x],
-                      (unsigned long long)c, c ? (double)q / c : 0.0);
+        uint64_t q = 0, f = 0;
+        const uint64_t c = cached_of(Lx[x], n_entx[x], q, f);
+        char b[200];
+        std::snprintf(b, sizeof(b), " | k=%u entries=%u cached=%llu final=%llu open=%llu mean_queue=%.1f", Lx[x].k,
+                      n_entx[x], (unsigned long long)c, (unsigned long long)f, (unsigned long long)(c - f),
+                      c ? (double)q / c : 0.0);
         lv += b;
       }
       {
@@ -6146,13 +6176,14 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
         std::memset(gb, 0, sizeof(gb));
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_bad), gb, sizeof(gb)));
       }
-      uint64_t q0 = 0;
-      const uint64_t c0 = n_ent0 ? cached_of(L0, n_ent0, q0) : 0;
-      std::fprintf(stderr, "FAC_RC windows=%llu L0 k=%u entries=%u cached=%llu mean_queue=%.1f | L1 k=%u keys=%llu cached=%llu "
-                   "mean_queue=%.1f%s | pool %.1f MB\n",
-                   (unsigned long long)windows, L0.k, n_ent0, (unsigned long long)c0, c0 ? (double)q0 / c0 : 0.0, L1.k,
-                   (unsigned long long)l1_keys, (unsigned long long)c1, c1 ? (double)q1 / c1 : 0.0, lv.c_str(),
-                   rcn[1] * 16.0 / 1e6);
+      uint64_t q0 = 0, f0 = 0;
+      const uint64_t c0 = n_ent0 ? cached_of(L0, n_ent0, q0, f0) : 0;
+      std::fprintf(stderr, "FAC_RC windows=%llu L0 k=%u entries=%u cached=%llu final=%llu open=%llu mean_queue=%.1f | L1 k=%u "
+                   "keys=%llu cached=%llu final=%llu open=%llu mean_queue=%.1f%s | pool %.1f MB\n",
+                   (unsigned long long)windows, L0.k, n_ent0, (unsigned long long)c0, (unsigned long long)f0,
+                   (unsigned long long)(c0 - f0), c0 ? (double)q0 / c0 : 0.0, L1.k, (unsigned long long)l1_keys,
+                   (unsigned long long)c1, (unsigned long long)f1, (unsigned long long)(c1 - f1),
+                   c1 ? (double)q1 / c1 : 0.0, lv.c_str(), rcn[1] * 16.0 / 1e6);
     }
   }
   const double t_cache = host_ms();
