@@ -509,6 +509,35 @@ uint64_t fac_haystack_grapheme_starts(const fac_haystack* hay, uint64_t* out, ui
   return h.n;
 }
 
+int64_t fac_haystack_symbol_ids(const fac_engine* engine, const fac_haystack* hay, void* stream, uint8_t* out,
+                                uint64_t cap) {
+  if (!engine || !hay || (cap && !out)) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
+  const fac::Engine& e = engine->e;
+  const fac::Haystack& h = hay->h;
+  if (!e.bitap_ok) return -1;
+  if (h.device != e.device) return -(int64_t)fail(FAC_E_INVALID, "haystack was staged for another device");
+  if (h.n == 0) return 0;
+  if (hipSetDevice(e.device) != hipSuccess) return -(int64_t)fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e.stream;
+  hipError_t he = hipSuccess;
+  uint8_t* d_ids = static_cast<uint8_t*>(fac::call_scratch_take(h.n, st, &he));
+  if (he != hipSuccess || !d_ids) return -(int64_t)fail(FAC_E_OOM, std::string("hipMalloc: ") + hipGetErrorString(he));
+  std::string err;
+  int rc = FAC_OK;
+  if (h.ascii) rc = fac::transcode_ascii_device(e, h.d_utf8, h.n, d_ids, st, err);
+  else rc = fac::symbol_ids_device(e, h, 0, h.n, d_ids, st, err);
+  const uint64_t take = std::min(cap, h.n);
+  if (!rc && ((take && hipMemcpyAsync(out, d_ids, take, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+              hipStreamSynchronize(st) != hipSuccess)) {
+    rc = FAC_E_HIP;
+    err = "copy of the symbol ids failed";
+  }
+  if (rc) (void)hipStreamSynchronize(st);
+  fac::call_scratch_give(d_ids, st);
+  if (rc) return -(int64_t)fail(rc, err);
+  return (int64_t)h.n;
+}
+
 void fac_haystack_free(fac_haystack* hay) {
   if (!hay) return;
   fac::free_haystack(hay->h);
@@ -613,7 +642,8 @@ struct DevMem {
 
 // The staged bytes [bs, be) = graphemes [g0, g1) searched as a text of their own (search_raw on a
 // slice: is_ascii is re-decided on the slice, search.rs:196, prefilter.rs:349-350). A Unicode
-// haystack's host copies must be fetched first (ensure_host).
+// haystack's host copies must be fetched first (ensure_host); slice_descs_device computes the same
+// on the device, with no host copy.
 fac::SegDesc slice_view(const fac::Haystack& h, uint64_t g0, uint64_t g1) {
   const uint64_t bs = h.ascii ? g0 : (g0 < h.n ? h.starts[g0] : h.len);
   const uint64_t be = h.ascii ? g1 : (g1 < h.n ? h.starts[g1] : h.len);
@@ -630,28 +660,40 @@ fac::SegDesc slice_view(const fac::Haystack& h, uint64_t g0, uint64_t g1) {
   return s;
 }
 
+}  // namespace
+
+namespace fac {
+
+static uint64_t seg_windows(const std::vector<SegDesc>& segs) {
+  uint64_t w = 0;
+  for (const SegDesc& s : segs) w += std::min(s.w_end, s.n) > s.w_begin ? std::min(s.w_end, s.n) - s.w_begin : 0;
+  return w;
+}
+
 // Prefiltered::raw on a text view of a staged haystack (prefilter.rs:304-374): bitap windows on the
 // device, each merged window re-searched as its own sub-haystack, best per (start, end, pattern) by
 // strictly greater similarity, sorted. Falls back to the full search of the view where the
-// reference does (:311-317).
-int prefiltered_view(const fac::Engine& e, const fac::Haystack& h, const fac::SegDesc& view, float threshold,
-                     hipStream_t stream, std::vector<fac_match>& merged, fac_stats* stats, std::string& err) {
+// reference does (:311-317). Nothing of the text or of its grapheme starts is copied to the host:
+// what comes back are the merged-window pairs, for Unicode text their descriptors, and the records.
+int prefiltered_view(const Engine& e, const Haystack& h, const SegDesc& view, float threshold, hipStream_t stream,
+                     std::vector<fac_match>& merged, fac_stats* stats, std::string& err, uint64_t* searched) {
   merged.clear();
   std::vector<uint32_t> ks;
-  if (!e.bitap_ok || !prefilter_ks(e, threshold, ks))  // prefilter.rs:151-155, 311-317
-    return fac::launch_search(e, h, {view}, threshold, stream, merged, stats, err);
+  if (!e.bitap_ok || !prefilter_ks(e, threshold, ks)) {  // prefilter.rs:151-155, 311-317
+    if (searched) *searched += seg_windows({view});
+    return launch_search(e, h, {view}, threshold, stream, merged, stats, err);
+  }
   std::vector<std::pair<uint64_t, uint64_t>> windows;
-  int rc = fac::prefilter_windows(e, h, view, ks, stream, windows, stats, err);
+  int rc = prefilter_windows(e, h, view, ks, stream, windows, stats, err);
   if (rc) return rc;
-  if (!view.ascii && (rc = fac::ensure_host(h, err))) return rc;  // slice_view reads the host copies
   // Re-search each merged window as its own haystack (prefilter.rs:344-350): the slice re-decides
   // is_ascii, so an all-ASCII slice of a Unicode haystack is searched byte-wise.
-  std::vector<fac::SegDesc> segs;
+  std::vector<SegDesc> segs;
   segs.reserve(windows.size());
-  for (auto& w : windows) {
-    const uint64_t gs = w.first, ge = std::min<uint64_t>(w.second, view.n);
-    if (view.ascii) {  // byte-wise view: windows are bytes of h.d_utf8 from view.text_base
-      fac::SegDesc s{};
+  if (view.ascii) {  // byte-wise view: windows are bytes of h.d_utf8 from view.text_base
+    for (auto& w : windows) {
+      const uint64_t gs = w.first, ge = std::min<uint64_t>(w.second, view.n);
+      SegDesc s{};
       s.ascii = 1u;
       s.text_base = view.text_base + gs;
       s.n = ge - gs;
@@ -661,13 +703,15 @@ int prefiltered_view(const fac::Engine& e, const fac::Haystack& h, const fac::Se
       s.w_begin = 0;
       s.w_end = s.n;
       segs.push_back(s);
-    } else {
-      segs.push_back(slice_view(h, view.text_base + gs, view.text_base + ge));
     }
+  } else {  // graphemes of the staged text: byte ranges and is_ascii per window from the device
+    for (auto& w : windows) w = {view.text_base + w.first, view.text_base + std::min<uint64_t>(w.second, view.n)};
+    if ((rc = slice_descs_device(h, windows, stream ? stream : e.stream, segs, err))) return rc;
   }
   if (segs.empty()) return FAC_OK;
+  if (searched) *searched += seg_windows(segs);
   std::vector<fac_match> res;
-  rc = fac::launch_search(e, h, segs, threshold, stream, res, stats, err);
+  rc = launch_search(e, h, segs, threshold, stream, res, stats, err);
   if (rc) return rc;
   std::map<std::tuple<uint64_t, uint64_t, uint32_t>, fac_match> best;
   for (const fac_match& m : res) {
@@ -678,6 +722,30 @@ int prefiltered_view(const fac::Engine& e, const fac::Haystack& h, const fac::Se
   }
   merged.reserve(best.size());
   for (auto& kv : best) merged.push_back(kv.second);
+  return FAC_OK;
+}
+
+}  // namespace fac
+
+namespace {
+
+using fac::prefiltered_view;
+
+// A stream window's view of a whole staged haystack: graphemes [g0, g1) as a text of their own.
+// A Unicode haystack's view comes from the device (no host copy of the text or the starts).
+int window_view(const fac::Engine& e, const fac::Haystack& h, uint64_t g0, uint64_t g1, hipStream_t st, fac::SegDesc& view,
+                std::string& err) {
+  if (h.ascii) {
+    view = slice_view(h, g0, g1);
+    return FAC_OK;
+  }
+  if (hipSetDevice(e.device) != hipSuccess) {
+    err = "hipSetDevice failed";
+    return FAC_E_HIP;
+  }
+  std::vector<fac::SegDesc> v;
+  if (int rc = fac::slice_descs_device(h, {{g0, g1}}, st ? st : e.stream, v, err)) return rc;
+  view = v[0];
   return FAC_OK;
 }
 
@@ -707,7 +775,7 @@ namespace fac {
 // neighbours, or pre-filter tables that need the packed full scan.
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
                          bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
-                         std::vector<uint64_t>* win_off) {
+                         std::vector<uint64_t>* win_off, uint64_t* searched) {
   owned.clear();
   if (win_off) win_off->assign(n_windows + 1, 0);  // (the early returns below: no records at all)
   if (!h.ascii || h.open_end || h.base || n_windows == 0 || n_windows >= (1u << 24) || h.len >= (1ull << kWinTagShift))
@@ -758,6 +826,7 @@ int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* win
     }
   }
   if (segs.empty()) return FAC_OK;
+  if (searched) *searched += seg_windows(segs);
   uint64_t cap = 1u << 16;
   for (;;) {  // raw records into a device buffer, grown and searched again if it was too small
     DevMem raw(st);
@@ -829,14 +898,12 @@ int fac_stream_window_staged(const fac_engine* engine, const fac_haystack* hay, 
   if (h.open_end || h.base) return fail(FAC_E_INVALID, "stream windows are cut from a whole staged haystack");
   g_end = std::min(g_end, h.n);
   g_begin = std::min(g_begin, g_end);
-  std::string herr;
-  if (!h.ascii)
-    if (int hrc = fac::ensure_host(h, herr)) return fail(hrc, herr);
-  const fac::SegDesc view = slice_view(h, g_begin, g_end);
   const fac::Engine& e = engine->e;
   hipStream_t st = static_cast<hipStream_t>(stream);
   std::vector<fac_match> v;
   std::string err;
+  fac::SegDesc view{};
+  if (int vrc = window_view(e, h, g_begin, g_end, st, view, err)) return fail(vrc, err);
   int rc = prefilter ? prefiltered_view(e, h, view, threshold, st, v, stats, err)
                      : fac::launch_search(e, h, {view}, threshold, st, v, stats, err);
   if (rc) return fail(rc, err);
@@ -867,12 +934,11 @@ int fac_stream_window_staged_device(const fac_engine* engine, const fac_haystack
   g_end = std::min(g_end, h.n);
   g_begin = std::min(g_begin, g_end);
   std::string err;
-  if (!h.ascii)
-    if (int hrc = fac::ensure_host(h, err)) return fail(hrc, err);
-  const fac::SegDesc view = slice_view(h, g_begin, g_end);
   const fac::Engine& e = engine->e;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  fac::SegDesc view{};
+  if (int vrc = window_view(e, h, g_begin, g_end, st, view, err)) return fail(vrc, err);
   // the window's searched segments: Prefiltered::raw's merged bitap windows (disjoint and not
   // adjacent, so their records never share a (start, end, pattern) key and the reference's
   // best-per-key merge is a no-op before the ranking), or the whole view where it falls back
@@ -888,9 +954,9 @@ int fac_stream_window_staged_device(const fac_engine* engine, const fac_haystack
     std::vector<std::pair<uint64_t, uint64_t>> windows;
     if (int rc = fac::prefilter_windows(e, h, view, ks, st, windows, stats, err)) return fail(rc, err);
     t_pf = ms_since(t0);
-    for (auto& w : windows) {
-      const uint64_t gs = w.first, ge = std::min<uint64_t>(w.second, view.n);
-      if (view.ascii) {
+    if (view.ascii) {
+      for (auto& w : windows) {
+        const uint64_t gs = w.first, ge = std::min<uint64_t>(w.second, view.n);
         fac::SegDesc s{};
         s.ascii = 1u;
         s.text_base = view.text_base + gs;
@@ -901,9 +967,10 @@ int fac_stream_window_staged_device(const fac_engine* engine, const fac_haystack
         s.w_begin = 0;
         s.w_end = s.n;
         segs.push_back(s);
-      } else {
-        segs.push_back(slice_view(h, view.text_base + gs, view.text_base + ge));
       }
+    } else {
+      for (auto& w : windows) w = {view.text_base + w.first, view.text_base + std::min<uint64_t>(w.second, view.n)};
+      if (int rc = fac::slice_descs_device(h, windows, st ? st : e.stream, segs, err)) return fail(rc, err);
     }
   } else {
     segs.push_back(view);
@@ -1061,7 +1128,7 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
 // The reference falls back to the plain search when the engine has no filter or some pattern's
 // k_for exceeds 24 (prefilter.rs:151-155, 311-317): engine and threshold alone decide, so a fallback
 // call is the plain batch call for any batch. Where the filter runs, the batch must be all ASCII
-// (a non-ASCII document's symbol ids need the host's folded-string lookup, ensure_symbols).
+// (its one scan resets at document starts in byte coordinates; Unicode documents are not wired in).
 static int batch_prefilter(const fac::Engine& e, const fac::Batch& b, float threshold, bool prefilter, hipStream_t st,
                            fac::BatchWindows& pw, bool& filtered, fac_stats* stats, std::string& err) {
   filtered = false;
@@ -1704,13 +1771,20 @@ int fac_render_batch_prefiltered(const fac_engine* engine, const fac_batch* batc
 }
 
 int fac_stream_open(const fac_engine* engine, float threshold, uint64_t window_bytes, fac_stream** out) {
+  return fac_stream_open_ex(engine, threshold, window_bytes, 0, out);
+}
+
+int fac_stream_open_ex(const fac_engine* engine, float threshold, uint64_t window_bytes, int32_t prefilter,
+                       fac_stream** out) {
   if (!engine || !out) return fail(FAC_E_INVALID, "NULL argument");
   fac_stream* fs = new (std::nothrow) fac_stream();
   if (!fs) return fail(FAC_E_OOM, "out of host memory");
-  fs->s = fac::stream_open(engine->e, threshold, window_bytes);
+  fs->s = fac::stream_open(engine->e, threshold, window_bytes, nullptr, prefilter != 0);
   *out = fs;
   return FAC_OK;
 }
+
+uint64_t fac_stream_windows_searched(const fac_stream* stream) { return stream ? stream->s->windows_searched : 0; }
 
 int fac_stream_feed(fac_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, fac_match** out,
                     uint64_t* n_out, uint8_t** text, uint64_t* text_len) {
@@ -1745,13 +1819,22 @@ void fac_stream_close(fac_stream* stream) {
 
 int fac_replace_stream_open(const fac_engine* engine, const fac_replacements* replacements, float threshold,
                             uint64_t window_bytes, fac_replace_stream** out) {
+  return fac_replace_stream_open_ex(engine, replacements, threshold, window_bytes, 0, out);
+}
+
+uint64_t fac_replace_stream_windows_searched(const fac_replace_stream* stream) {
+  return stream ? stream->s->windows_searched : 0;
+}
+
+int fac_replace_stream_open_ex(const fac_engine* engine, const fac_replacements* replacements, float threshold,
+                               uint64_t window_bytes, int32_t prefilter, fac_replace_stream** out) {
   if (!engine || !replacements || !out) return fail(FAC_E_INVALID, "NULL argument");
   *out = nullptr;
   if (replacements->t.device != engine->e.device || replacements->t.n_patterns != engine->e.pats.size())
     return fail(FAC_E_INVALID, "the replacement table was built for another engine");
   fac_replace_stream* fs = new (std::nothrow) fac_replace_stream();
   if (!fs) return fail(FAC_E_OOM, "out of host memory");
-  fs->s = fac::stream_open(engine->e, threshold, window_bytes, &replacements->t);
+  fs->s = fac::stream_open(engine->e, threshold, window_bytes, &replacements->t, prefilter != 0);
   *out = fs;
   return FAC_OK;
 }

@@ -331,6 +331,18 @@ struct PfTables {
   }
 };
 
+// A device lookup "folded grapheme -> id" (stage_kernels.hip): an open-addressing table over a hash
+// of the grapheme's folded code points. A slot holds an entry's index + 1 (0: empty), an entry
+// {hash, offset of its key in the pool, key length in code points, id}; the pool holds every key's
+// code points. Keys have any length and ids are 32 bits, so the same structure can hold Engine::gid_of.
+struct GraphemeTable {
+  uint32_t* d_slots = nullptr;
+  uint4* d_ents = nullptr;
+  uint32_t* d_pool = nullptr;
+  uint32_t mask = 0;  // slots - 1
+  uint32_t n_keys = 0, n_pool = 0;
+};
+
 struct Engine {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -407,6 +419,7 @@ struct Engine {
   uint64_t* d_sim_keys = nullptr;
   float* d_sim_vals = nullptr;
   uint8_t* d_ascii_id = nullptr;
+  GraphemeTable sym_tab;  // symbol_ids on the device (bitap_ok engines; symbol_ids_device)
   uint32_t* d_edge_gid = nullptr;
   uint32_t* d_ascii_gid = nullptr;
   uint2* d_map_range = nullptr;
@@ -444,14 +457,12 @@ struct Haystack {
   uint64_t off_cap = 0;          // entries d_off / d_text32 hold (kept when staged again)
   void* d_stage = nullptr;       // staging scratch (stage_device), kept when staged again
   size_t stage_cap = 0;
-  // host copies, fetched from the device on first use (ensure_host): the UTF-8 bytes (pre-filter
-  // slices re-decide is_ascii; host transcodes) and the grapheme byte starts (Unicode only)
+  // host copies, fetched from the device on first use (ensure_host): the UTF-8 bytes (the mapping
+  // engines' host transcode, shard planning) and the grapheme byte starts (Unicode only)
   mutable std::vector<uint8_t> utf8;
   mutable std::vector<uint64_t> starts;
   mutable bool host_ready = false;
   mutable std::mutex host_mu;
-  mutable std::vector<uint8_t> sym;  // prefilter symbol ids per grapheme (Unicode only, lazy)
-  mutable bool sym_ready = false;
   mutable uint32_t* d_gid = nullptr;  // grapheme ids (Unicode, engines with mappings; lazy)
   mutable const void* gid_engine = nullptr;
   int device = 0;
@@ -816,6 +827,11 @@ struct StreamCore {
   int failed = 0;
   std::string fail_msg;
   uint64_t batch_bytes = 32ull << 20;  // text a task collects before it is dispatched (FAC_STREAM_BATCH_BYTES)
+  uint64_t read = 64 * 1024;  // the reader's read() size (stream.rs:102-158; FAC_STREAM_READ_BYTES)
+  // every window's text is searched as Prefiltered::search (fac_stream_open_ex; prefilter.rs:304-374)
+  bool prefilter = false;
+  // start windows of the segments handed to the search launcher, for the windows handed out so far
+  uint64_t windows_searched = 0;
   // replace mode (fac_replace_stream_*): the table, the output ready to hand out, the totals of the
   // tasks handed out, and ReplaceCursor::emitted (stream.rs:645-648) as it passes from task to task:
   // cur_emitted is the cursor after task cur_seq - 1, and task cur_seq plans next
@@ -829,7 +845,8 @@ struct StreamCore {
 };
 
 // table: NULL for a search stream; else the stream replaces (the table outlives the stream)
-StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table = nullptr);
+StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table = nullptr,
+                        bool prefilter = false);
 int stream_feed(StreamCore& s, const uint8_t* data, uint64_t len, bool eof, std::string& err);
 void stream_close(StreamCore* s);
 uint64_t stream_committed(const StreamCore& s);  // commit point of the windows handed out so far
@@ -838,7 +855,22 @@ uint64_t stream_committed(const StreamCore& s);  // commit point of the windows 
 int stage_device(const Engine& e, Haystack& h, hipStream_t st, std::string& err, int mode);
 // graphemes of a staged haystack that start before byte b (a grapheme boundary), synchronously on st
 int graphemes_before(const Haystack& h, uint64_t b, hipStream_t st, uint64_t& out, std::string& err);
-void ensure_symbols(const Engine& e, const Haystack& h);
+// stage_kernels.hip: the lookup table of `keys` (folded grapheme, id), built on the device
+int grapheme_table_build(const std::vector<std::pair<std::u32string, uint32_t>>& keys, GraphemeTable& t, hipStream_t st,
+                         std::string& err);
+void grapheme_table_free(GraphemeTable& t);
+// The pre-filter's symbol id (prefilter.rs:262-280; 0 = other) of graphemes [g0, g1) of a staged
+// Unicode haystack, written to d_ids[0, g1 - g0) on st (asynchronous): symbol_ids_kernel
+int symbol_ids_device(const Engine& e, const Haystack& h, uint64_t g0, uint64_t g1, uint8_t* d_ids, hipStream_t st,
+                      std::string& err);
+// search_kernels.hip: the same for ASCII text (prefilter.rs:253-258): d_ids[i] = ascii_id[d_utf8[i]], i < n
+int transcode_ascii_device(const Engine& e, const uint8_t* d_utf8, uint64_t n, uint8_t* d_ids, hipStream_t st,
+                           std::string& err);
+// The descriptors of graphemes [gs, ge) x n of a staged Unicode haystack, each searched as a text of
+// its own (search_raw on a slice re-decides is_ascii, search.rs:196, prefilter.rs:349-350):
+// slice_desc_kernel on st, then the n descriptors are read back (synchronous)
+int slice_descs_device(const Haystack& h, const std::vector<std::pair<uint64_t, uint64_t>>& spans, hipStream_t st,
+                       std::vector<SegDesc>& out, std::string& err);
 int apply_matches(const Engine& e, std::vector<fac_match>& v, int order, int overlap, const uint64_t* unique_ids,
                   std::string& err);
 // stream.rs window_matches' tail on the device (rank_kernels.hip): the n raw records of one window
@@ -863,7 +895,7 @@ void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std
 // win_off (optional): the CSR index of the windows into `owned`, n_windows + 1 entries
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
                          bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
-                         std::vector<uint64_t>* win_off = nullptr);
+                         std::vector<uint64_t>* win_off = nullptr, uint64_t* searched = nullptr);
 // merged bitap windows (prefilter.rs:319-342) of a text view of a staged haystack (view.ascii:
 // bytes [text_base, text_base + n) of h.d_utf8; else graphemes [text_base, text_base + n)); windows
 // in the view's local grapheme coordinates
@@ -881,6 +913,11 @@ int prefilter_windows_ex(const Engine& e, const Haystack& h, const SegDesc& view
                          hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>* wins,
                          std::vector<std::pair<uint64_t, uint64_t>>& windows, std::vector<uint32_t>* run_win,
                          fac_stats* stats, std::string& err);
+// api.cpp: Prefiltered::raw on a text view of a staged haystack (prefilter.rs:304-374); the plain
+// search of the view where the reference falls back. searched (optional): += the start windows of
+// the segments handed to the search launcher
+int prefiltered_view(const Engine& e, const Haystack& h, const SegDesc& view, float threshold, hipStream_t stream,
+                     std::vector<fac_match>& merged, fac_stats* stats, std::string& err, uint64_t* searched = nullptr);
 // force_ascii: -1 decide from the bytes (search.rs:196), 0 Unicode graphemes, 1 ASCII bytes (a
 // shard of a haystack whose global is_ascii is already known)
 int stage_haystack(const Engine& e, const uint8_t* utf8, uint64_t len, Haystack& h, std::string& err,

@@ -5202,6 +5202,8 @@ int upload_engine(Engine& e, std::string& err) {
     // the packed masks depend on the per-call edit budgets: prefilter_windows builds them
     std::vector<uint8_t> aid(e.ascii_id, e.ascii_id + 128);
     if ((rc = upload(aid, &e.d_ascii_id, err))) return rc;
+    // folded pattern grapheme -> symbol id, for the transcode of Unicode text (symbol_ids_kernel)
+    if ((rc = grapheme_table_build(e.symbol_ids, e.sym_tab, e.stream, err))) return rc;
   }
   // Pageable hipMemcpy may return before the DMA lands and the engine's stream is non-blocking:
   // make the tables visible to every stream before the first launch.
@@ -5217,6 +5219,7 @@ void free_engine_device(Engine& e) {
                   e.d_map_ent, e.d_map_hay};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  grapheme_table_free(e.sym_tab);
   e.pf_cache.clear();
   for (int i = 0; i < Engine::kScratch; ++i)
     if (e.scratch_p[i]) {
@@ -5277,8 +5280,6 @@ int stage_haystack_device(const Engine& e, const uint8_t* d_utf8, uint64_t len, 
     h.utf8.clear();
     h.starts.clear();
   }
-  h.sym_ready = false;
-  h.sym.clear();
   if (h.d_gid) HIP_TRY(hipFree(h.d_gid));
   h.d_gid = nullptr;
   h.gid_engine = nullptr;
@@ -5301,8 +5302,6 @@ int stage_haystack_device(const Engine& e, const uint8_t* d_utf8, uint64_t len, 
   return rc;
 }
 
-// Bit-parallel pre-filter transcode of a Unicode haystack (prefilter.rs:262-280): symbol id of
-// every folded grapheme, computed on first use (only pre-filtered searches need it).
 int ensure_host(const Haystack& h, std::string& err) {
   std::lock_guard<std::mutex> lk(h.host_mu);
   if (h.host_ready) return FAC_OK;
@@ -5315,22 +5314,6 @@ int ensure_host(const Haystack& h, std::string& err) {
   }
   h.host_ready = true;
   return FAC_OK;
-}
-
-void ensure_symbols(const Engine& e, const Haystack& h) {
-  if (h.ascii || h.sym_ready) return;
-  std::string err;
-  if (ensure_host(h, err)) return;
-  h.sym.assign(h.n, 0);
-  std::u32string g;
-  const uint8_t* utf8 = h.utf8.data();
-  for (uint64_t i = 0; i < h.n; ++i) {
-    const uint64_t b = h.starts[i], en = i + 1 < h.n ? h.starts[i + 1] : h.len;
-    fold_grapheme(utf8, b, en, e.case_insensitive, g);
-    auto it = std::lower_bound(e.symbol_ids.begin(), e.symbol_ids.end(), std::make_pair(g, 0u));
-    if (it != e.symbol_ids.end() && it->first == g) h.sym[i] = (uint8_t)it->second;
-  }
-  h.sym_ready = true;
 }
 
 void free_haystack(Haystack& h) {
@@ -6957,6 +6940,16 @@ int qgram_candidates(const Engine& e, const PfTables& T, QgramParams& Q, uint64_
   return FAC_OK;
 }
 
+int transcode_ascii_device(const Engine& e, const uint8_t* d_utf8, uint64_t n, uint8_t* d_ids, hipStream_t stream,
+                           std::string& err) {
+  if (n == 0) return FAC_OK;
+  const uint64_t threads = (n + 15) / 16;
+  hipLaunchKernelGGL(transcode_ascii_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, d_utf8, n,
+                     e.d_ascii_id, d_ids);
+  HIP_TRY(hipGetLastError());
+  return FAC_OK;
+}
+
 int prefilter_windows(const Engine& e, const Haystack& h, const SegDesc& view, const std::vector<uint32_t>& ks,
                       hipStream_t stream, std::vector<std::pair<uint64_t, uint64_t>>& windows, fac_stats* stats,
                       std::string& err) {
@@ -6995,9 +6988,9 @@ int prefilter_windows_ex(const Engine& e, const Haystack& h, const SegDesc& view
       hipLaunchKernelGGL(transcode_ascii_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, vb, n,
                          e.d_ascii_id, static_cast<uint8_t*>(d_ids.p));
       HIP_TRY(hipGetLastError());
-    } else {
-      ensure_symbols(e, h);
-      HIP_TRY(hipMemcpyAsync(d_ids.p, h.sym.data() + view.text_base, n, hipMemcpyHostToDevice, stream));
+    } else {  // Unicode text (prefilter.rs:262-280): the id of every folded grapheme, looked up on the device
+      if (int rc = symbol_ids_device(e, h, view.text_base, view.text_base + n, static_cast<uint8_t*>(d_ids.p), stream, err))
+        return rc;
     }
   }
   const uint64_t n_words = (n + 31) / 32;

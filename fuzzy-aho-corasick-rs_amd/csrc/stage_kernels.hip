@@ -675,6 +675,283 @@ int graphemes_before(const Haystack& h, uint64_t b, hipStream_t st, uint64_t& ou
   return FAC_OK;
 }
 
+// ---------------------------------------------------------------- grapheme lookup (GraphemeTable)
+// The pre-filter's transcode of a Unicode haystack (prefilter.rs:262-280): the symbol id of every
+// folded grapheme, looked up in the engine's table of pattern graphemes. The key of a grapheme is its
+// folded code-point sequence (unicode.cpp fold_grapheme); the hash only picks the first slot, a hit
+// is decided by comparing the code points.
+namespace {
+
+constexpr uint32_t kGtSlotsLds = 1024, kGtKeysLds = 512, kGtPoolLds = 2048;  // 20 KiB of LDS per workgroup
+
+__device__ __forceinline__ uint32_t gt_hash_step(uint32_t h, uint32_t cp) { return (h ^ cp) * 16777619u; }  // FNV-1a
+constexpr uint32_t kGtHashInit = 2166136261u;
+__device__ __forceinline__ uint32_t gt_hash_end(uint32_t h) { return h ^ (h >> 15); }
+
+// unicode.cpp lower_full: the full lowercase of one code point, up to 3 outputs. A BMP code point
+// whose first lowercase code point is itself has no entry (an entry maps to something else first).
+__device__ __forceinline__ int lower_full_dev(const uint16_t* __restrict__ ltab, uint32_t cp, uint32_t out[3]) {
+  if (cp < 0x80u) {
+    out[0] = (cp - 'A' < 26u) ? cp + 32u : cp;
+    return 1;
+  }
+  if (cp < 0x10000u && ltab[cp] == cp) {
+    out[0] = cp;
+    return 1;
+  }
+  uint32_t lo = 0, hi = sizeof(kLowerMap) / sizeof(kLowerMap[0]);
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (kLowerMap[mid].cp < cp) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo < sizeof(kLowerMap) / sizeof(kLowerMap[0]) && kLowerMap[lo].cp == cp) {
+    const int k = kLowerMap[lo].n;
+    for (int t = 0; t < k; ++t) out[t] = kLowerMap[lo].out[t];
+    return k;
+  }
+  out[0] = cp;
+  return 1;
+}
+
+// f(code point) -> bool for every folded code point of bytes [b, e), in order, until f returns false
+template <typename F>
+__device__ __forceinline__ void for_folded(const uint8_t* __restrict__ s, uint64_t b, uint64_t e,
+                                           const uint16_t* __restrict__ ltab, int ci, F f) {
+  uint64_t i = b;
+  while (i < e) {
+    const uint32_t cp = decode(s, e, i);
+    if (!ci) {
+      if (!f(cp)) return;
+      continue;
+    }
+    uint32_t lo[3];
+    const int k = lower_full_dev(ltab, cp, lo);
+    for (int t = 0; t < k; ++t)
+      if (!f(lo[t])) return;
+  }
+}
+
+// One thread per key: its entry {hash, pool offset, length, id}, and the first free slot from its
+// hash on takes the entry (slots = a power of two > the key count, so a free slot exists).
+__global__ void grapheme_table_build_kernel(const uint32_t* __restrict__ pool, const uint2* __restrict__ keys,
+                                            const uint32_t* __restrict__ ids, uint32_t n_keys, uint32_t mask,
+                                            uint32_t* __restrict__ slots, uint4* __restrict__ ents) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_keys) return;
+  const uint2 key = keys[k];  // {pool offset, code points}
+  uint32_t h = kGtHashInit;
+  for (uint32_t i = 0; i < key.y; ++i) h = gt_hash_step(h, pool[key.x + i]);
+  h = gt_hash_end(h);
+  ents[k] = make_uint4(h, key.x, key.y, ids[k]);
+  for (uint32_t s = h & mask, probes = 0; probes <= mask; s = (s + 1) & mask, ++probes)
+    if (atomicCAS(&slots[s], 0u, k + 1) == 0u) return;
+}
+
+// One thread per grapheme g of [g0, g1): bytes [off[g], off[g + 1]) (the last grapheme ends at len)
+// are decoded and folded twice -- once for the hash and the length, once per probed entry of equal
+// hash and length to compare its key -- so a grapheme of any length needs no buffer. The table
+// (<= 255 symbols) is copied to LDS when it fits (lds != 0); the loads of off are coalesced and a
+// wave's graphemes are contiguous bytes. ids[g - g0] = the id, 0 = no pattern grapheme.
+__global__ __launch_bounds__(256) void symbol_ids_kernel(const uint8_t* __restrict__ utf8, uint64_t len,
+                                                         const uint64_t* __restrict__ off, uint64_t n, uint64_t g0,
+                                                         uint64_t g1, const uint16_t* __restrict__ ltab, int ci,
+                                                         const uint32_t* __restrict__ g_slots, const uint4* __restrict__ g_ents,
+                                                         const uint32_t* __restrict__ g_pool, uint32_t mask, uint32_t n_keys,
+                                                         uint32_t n_pool, int lds, uint8_t* __restrict__ ids) {
+  __shared__ uint32_t s_slots[kGtSlotsLds];
+  __shared__ uint4 s_ents[kGtKeysLds];
+  __shared__ uint32_t s_pool[kGtPoolLds];
+  const uint32_t* slots = g_slots;
+  const uint4* ents = g_ents;
+  const uint32_t* pool = g_pool;
+  if (lds) {  // (mask + 1 <= kGtSlotsLds, n_keys <= kGtKeysLds, n_pool <= kGtPoolLds: checked by the host)
+    for (uint32_t i = threadIdx.x; i <= mask; i += blockDim.x) s_slots[i] = g_slots[i];
+    for (uint32_t i = threadIdx.x; i < n_keys; i += blockDim.x) s_ents[i] = g_ents[i];
+    for (uint32_t i = threadIdx.x; i < n_pool; i += blockDim.x) s_pool[i] = g_pool[i];
+    __syncthreads();
+    slots = s_slots;
+    ents = s_ents;
+    pool = s_pool;
+  }
+  const uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= g1 || g >= n) return;
+  const uint64_t b = off[g], e = g + 1 < n ? off[g + 1] : len;
+  if (b >= e || e > len) {  // (never for a staged haystack)
+    ids[g - g0] = 0;
+    return;
+  }
+  uint32_t h = kGtHashInit, cnt = 0;
+  for_folded(utf8, b, e, ltab, ci, [&](uint32_t cp) {
+    h = gt_hash_step(h, cp);
+    ++cnt;
+    return true;
+  });
+  h = gt_hash_end(h);
+  uint32_t id = 0;
+  for (uint32_t s = h & mask, probes = 0; probes <= mask; s = (s + 1) & mask, ++probes) {
+    const uint32_t v = slots[s];
+    if (v == 0u) break;
+    const uint4 en = ents[v - 1];
+    if (en.x != h || en.z != cnt) continue;
+    uint32_t at = 0;
+    bool same = true;
+    for_folded(utf8, b, e, ltab, ci, [&](uint32_t cp) {
+      same = pool[en.y + at] == cp;
+      ++at;
+      return same;
+    });
+    if (same) {
+      id = en.w;
+      break;
+    }
+  }
+  ids[g - g0] = (uint8_t)id;
+}
+
+// One workgroup per merged window w = graphemes [gs, ge) of a staged Unicode haystack: its SegDesc
+// as a text of its own (api.cpp slice_view). bs = off[gs], be = off[ge] or len; the workgroup ORs the
+// bytes [bs, be) (aligned 8-byte words between a byte head and tail) to decide is_ascii.
+__global__ __launch_bounds__(256) void slice_desc_kernel(const uint8_t* __restrict__ utf8, uint64_t len,
+                                                         const uint64_t* __restrict__ off, uint64_t n,
+                                                         const uint64_t* __restrict__ spans, uint32_t n_spans,
+                                                         SegDesc* __restrict__ out) {
+  const uint32_t w = blockIdx.x;
+  if (w >= n_spans) return;
+  const uint64_t gs = spans[2 * w], ge = spans[2 * w + 1];
+  const uint64_t be = ge < n ? off[ge] : len;
+  const uint64_t bs = gs < n ? off[gs] : len;
+  uint64_t acc = 0;
+  if (bs < be && be <= len) {
+    const uint8_t* p = utf8 + bs;
+    const uint64_t cnt = be - bs;
+    const uint64_t mis = (8u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 7u)) & 7u;
+    const uint64_t head = mis < cnt ? mis : cnt;
+    const uint64_t words = (cnt - head) / 8, tail = head + words * 8;
+    for (uint64_t i = threadIdx.x; i < head; i += blockDim.x) acc |= p[i];
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(p + head);
+    for (uint64_t i = threadIdx.x; i < words; i += blockDim.x) acc |= q[i];
+    for (uint64_t i = tail + threadIdx.x; i < cnt; i += blockDim.x) acc |= p[i];
+  }
+  const int hi = __syncthreads_or((acc & 0x8080808080808080ull) != 0 ? 1 : 0);
+  if (threadIdx.x != 0) return;
+  const bool asc = hi == 0;
+  SegDesc s{};
+  s.ascii = asc ? 1u : 0u;
+  s.text_base = asc ? bs : gs;
+  s.n = asc ? be - bs : ge - gs;
+  s.avail = s.n;
+  s.hay_len = be - bs;
+  s.byte_base = bs;
+  s.w_begin = 0;
+  s.w_end = s.n;
+  out[w] = s;
+}
+
+}  // namespace
+
+int grapheme_table_build(const std::vector<std::pair<std::u32string, uint32_t>>& keys, GraphemeTable& t, hipStream_t st,
+                         std::string& err) {
+  grapheme_table_free(t);
+  std::vector<uint32_t> pool, ids;
+  std::vector<uint2> ks;
+  for (const auto& kv : keys) {
+    ks.push_back(make_uint2((uint32_t)pool.size(), (uint32_t)kv.first.size()));
+    ids.push_back(kv.second);
+    for (char32_t c : kv.first) pool.push_back((uint32_t)c);
+  }
+  if (pool.size() >= (1ull << 31) || keys.size() >= (1ull << 30)) {
+    err = "grapheme table too large";
+    return FAC_E_UNSUPPORTED;
+  }
+  uint32_t slots = 16;
+  while (slots < 2 * keys.size() + 1) slots *= 2;
+  t.mask = slots - 1;
+  t.n_keys = (uint32_t)keys.size();
+  t.n_pool = (uint32_t)pool.size();
+  ST_TRY(hipMalloc((void**)&t.d_slots, (size_t)slots * 4));
+  ST_TRY(hipMalloc((void**)&t.d_ents, std::max<size_t>(keys.size() * sizeof(uint4), 16)));
+  ST_TRY(hipMalloc((void**)&t.d_pool, std::max<size_t>(pool.size() * 4, 16)));
+  ST_TRY(hipMemsetAsync(t.d_slots, 0, (size_t)slots * 4, st));
+  if (keys.empty()) return FAC_OK;
+  uint2* d_keys = nullptr;
+  uint32_t* d_ids = nullptr;
+  ST_TRY(hipMalloc((void**)&d_keys, ks.size() * sizeof(uint2)));
+  hipError_t he = hipMalloc((void**)&d_ids, ids.size() * 4);
+  if (he == hipSuccess && !pool.empty()) he = hipMemcpyAsync(t.d_pool, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipMemcpyAsync(d_keys, ks.data(), ks.size() * sizeof(uint2), hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipMemcpyAsync(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) {
+    hipLaunchKernelGGL(grapheme_table_build_kernel, dim3((t.n_keys + 255) / 256), dim3(256), 0, st, t.d_pool, d_keys, d_ids,
+                       t.n_keys, t.mask, t.d_slots, t.d_ents);
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipStreamSynchronize(st);  // (the host vectors and the two temporaries go away)
+  (void)hipFree(d_keys);
+  if (d_ids) (void)hipFree(d_ids);
+  ST_TRY(he);
+  return FAC_OK;
+}
+
+void grapheme_table_free(GraphemeTable& t) {
+  if (t.d_slots) (void)hipFree(t.d_slots);
+  if (t.d_ents) (void)hipFree(t.d_ents);
+  if (t.d_pool) (void)hipFree(t.d_pool);
+  t = GraphemeTable{};
+}
+
+int symbol_ids_device(const Engine& e, const Haystack& h, uint64_t g0, uint64_t g1, uint8_t* d_ids, hipStream_t st,
+                      std::string& err) {
+  g1 = std::min(g1, h.n);
+  if (g0 >= g1) return FAC_OK;
+  const GraphemeTable& t = e.sym_tab;
+  if (h.ascii || !t.d_slots || !h.d_off) {
+    err = "internal: symbol_ids_device needs a staged Unicode haystack and an engine with a pre-filter";
+    return FAC_E_INTERNAL;
+  }
+  BmpTabs tabs;
+  if (int trc = bmp_tables(h.device, st, tabs, err)) return trc;
+  const int lds = (t.mask < kGtSlotsLds && t.n_keys <= kGtKeysLds && t.n_pool <= kGtPoolLds) ? 1 : 0;
+  const uint64_t blocks = (g1 - g0 + 255) / 256;  // (h.n <= u32::MAX graphemes: the grid fits)
+  hipLaunchKernelGGL(symbol_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n, g0, g1,
+                     tabs.l, e.case_insensitive ? 1 : 0, t.d_slots, t.d_ents, t.d_pool, t.mask, t.n_keys, t.n_pool, lds, d_ids);
+  ST_TRY(hipGetLastError());
+  return FAC_OK;
+}
+
+int slice_descs_device(const Haystack& h, const std::vector<std::pair<uint64_t, uint64_t>>& spans, hipStream_t st,
+                       std::vector<SegDesc>& out, std::string& err) {
+  out.assign(spans.size(), SegDesc{});
+  if (spans.empty()) return FAC_OK;
+  if (h.ascii || !h.d_off || spans.size() >= (1ull << 31)) {
+    err = "internal: slice_descs_device needs a staged Unicode haystack";
+    return FAC_E_INTERNAL;
+  }
+  std::vector<uint64_t> flat(2 * spans.size());
+  for (size_t i = 0; i < spans.size(); ++i) {
+    flat[2 * i + 1] = std::min(spans[i].second, h.n);
+    flat[2 * i] = std::min(spans[i].first, flat[2 * i + 1]);
+  }
+  hipError_t he = hipSuccess;
+  const size_t in_b = flat.size() * 8, out_b = spans.size() * sizeof(SegDesc);
+  uint8_t* mem = static_cast<uint8_t*>(call_scratch_take(in_b + out_b, st, &he));
+  ST_TRY(he);
+  uint64_t* d_spans = reinterpret_cast<uint64_t*>(mem);
+  SegDesc* d_out = reinterpret_cast<SegDesc*>(mem + in_b);  // (in_b is a multiple of 16)
+  he = hipMemcpyAsync(d_spans, flat.data(), in_b, hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) {
+    hipLaunchKernelGGL(slice_desc_kernel, dim3((uint32_t)spans.size()), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n,
+                       d_spans, (uint32_t)spans.size(), d_out);
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipMemcpyAsync(out.data(), d_out, out_b, hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);
+  else (void)hipStreamSynchronize(st);  // (the upload may be in flight: flat goes away)
+  call_scratch_give(mem, st);
+  ST_TRY(he);
+  return FAC_OK;
+}
+
 // ---------------------------------------------------------------- batch staging (fac_batch_*)
 // Every document of a batch is staged as if it were staged alone: the UTF-8 check and is_ascii
 // (search.rs:196) per document, UAX #29 segmentation of the non-ASCII documents from start-of-text

@@ -12,7 +12,9 @@
 // to one of `depth` (2) worker threads, batch k to worker k % depth. A worker owns a HIP stream and
 // a device scratch set. An all-ASCII batch is staged once (H2D) and its windows searched in one
 // launch, each as its own text (stream_windows_batch); a batch with other text stages and searches
-// its windows one by one (H2D + device segmentation + folding each). Every window is ranked
+// its windows one by one (H2D + device segmentation + folding each). A pre-filtered stream
+// (fac_stream_open_ex) searches every window's text as Prefiltered::search: the batched path hands the
+// flag to stream_windows_batch, a single window goes through prefiltered_view. Every window is ranked
 // sorted().non_overlapping() and keeps the matches it owns (stream.rs:262-297). Batch k + 1's
 // copies and kernels overlap batch k's (double buffering) while the host cuts the windows of batch
 // k + 2. Finished batches are handed out strictly in window order.
@@ -51,6 +53,7 @@ struct StreamTask {
   uint64_t seq = 0;          // dispatch order (replace mode: the cursor's order)
   std::vector<uint8_t> out;  // replace mode: the task's spliced output
   uint64_t applied = 0, skipped = 0;
+  uint64_t searched = 0;  // start windows of the segments handed to the search launcher
   int rc = FAC_OK;
   std::string err;
   bool done = false;
@@ -73,7 +76,7 @@ std::condition_variable g_done_cv;
 
 // Search one window (text[off, off + len) of the task) and keep the matches it owns (stream.rs:262-297).
 // shift: the stream offset the records are rebased to, less the window's offset in the task's text
-int search_one_window(const StreamCore& s, StreamWorker& w, const StreamTask& t, const StreamWin& win, uint64_t shift,
+int search_one_window(const StreamCore& s, StreamWorker& w, StreamTask& t, const StreamWin& win, uint64_t shift,
                       std::vector<fac_match>& owned, std::string& err) {
   Haystack h;
   int rc = stage_haystack(*s.e, t.text.data() + win.off, win.len, h, err, -1, w.stream);
@@ -88,7 +91,12 @@ int search_one_window(const StreamCore& s, StreamWorker& w, const StreamTask& t,
     seg.w_end = h.n;
     seg.ascii = h.ascii ? 1u : 0u;
     std::vector<fac_match> res;
-    rc = launch_search(*s.e, h, {seg}, s.threshold, w.stream, res, nullptr, err);
+    if (s.prefilter) {  // Prefiltered::search of the window's text (prefilter.rs:304-374)
+      rc = prefiltered_view(*s.e, h, seg, s.threshold, w.stream, res, nullptr, err, &t.searched);
+    } else {
+      t.searched += seg.w_end - seg.w_begin;
+      rc = launch_search(*s.e, h, {seg}, s.threshold, w.stream, res, nullptr, err);
+    }
     if (!rc) rc = apply_matches(*s.e, res, /*Default*/ 1, /*NonOverlapping*/ 1, nullptr, err);
     if (!rc)
       for (const fac_match& m : res) {
@@ -201,10 +209,12 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
         wins[4 * i + 2] = t.wins[i].commit;
         wins[4 * i + 3] = shift + t.wins[i].off;
       }
-      const int rc = stream_windows_batch(*s.e, h, wins.data(), t.wins.size(), s.threshold, false, w.stream, owned,
-                                          nullptr, t.err, &win_off);
-      if (rc != FAC_E_UNSUPPORTED) {
+      uint64_t searched = 0;
+      const int rc = stream_windows_batch(*s.e, h, wins.data(), t.wins.size(), s.threshold, s.prefilter, w.stream, owned,
+                                          nullptr, t.err, &win_off, &searched);
+      if (rc != FAC_E_UNSUPPORTED) {  // (unsupported: pre-filter tables that need the packed full scan)
         t.rc = rc;
+        t.searched += searched;
         batched = true;
       }
     }
@@ -301,6 +311,7 @@ int collect(StreamCore& s, bool all, std::string& err) {
       s.applied += t->applied;
       s.skipped += t->skipped;
     }
+    s.windows_searched += t->searched;
     delete t;
   }
   if (s.failed) {
@@ -338,8 +349,7 @@ int dispatch(StreamCore& s, StreamTask* t, std::string& err) {
 // 64 KiB pieces until it holds >= window bytes, so a window's text is the carry left by the previous
 // window plus whole 64 KiB reads (the last one partial at the end of the input); fed in larger pieces,
 // the buffer is cut the same way. Consecutive windows join the pending batch, dispatched once it holds
-// kBatchBytes of text or the input ends.
-constexpr uint64_t kRead = 64 * 1024;
+// kBatchBytes of text or the input ends. (StreamCore::read: the read size, 64 KiB.)
 
 int flush_batch(StreamCore& s, std::string& err) {
   if (!s.pending) return FAC_OK;
@@ -355,7 +365,7 @@ int pump(StreamCore& s, bool eof, std::string& err) {
   while (!s.done) {
     const uint8_t* b = s.buf.data() + at;
     const uint64_t avail = s.buf.size() - at;
-    const uint64_t want = s.carry >= s.window ? s.carry : s.carry + (s.window - s.carry + kRead - 1) / kRead * kRead;
+    const uint64_t want = s.carry >= s.window ? s.carry : s.carry + (s.window - s.carry + s.read - 1) / s.read * s.read;
     if (!eof && avail < want) break;  // the reader would block for more input
     const uint64_t len = std::min(avail, want);
     // the valid UTF-8 prefix of the window's bytes; bytes a previous window already validated (up to
@@ -412,13 +422,16 @@ int stream_feed(StreamCore& s, const uint8_t* data, uint64_t len, bool eof, std:
   return pump(s, eof, err);
 }
 
-StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table) {
+StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table, bool prefilter) {
   StreamCore* s = new StreamCore();
   s->e = &e;
   s->threshold = threshold;
   s->table = table;
+  s->prefilter = prefilter;
   if (const char* v = diag_env("FAC_STREAM_BATCH_BYTES"))  // diagnostics: task boundaries at small sizes
     s->batch_bytes = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+  if (const char* v = diag_env("FAC_STREAM_READ_BYTES"))  // diagnostics: the reader's read size, many windows of a small input
+    s->read = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
   if (window) s->window = window;
   s->overlap = e.max_match_graphemes + 1;  // stream_overlap (stream.rs:256-258)
   (void)hipSetDevice(e.device);

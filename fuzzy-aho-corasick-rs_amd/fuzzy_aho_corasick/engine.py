@@ -235,10 +235,10 @@ class FuzzyAhoCorasick:
         return self._to_matches(haystack, data, _native.take_matches(out, count))
 
     # -- stream.rs
-    def search_stream(self, reader, threshold: float, on_match, window: int = 0) -> int:
+    def search_stream(self, reader, threshold: float, on_match, window: int = 0, _prefilter: bool = False) -> int:
         """stream.rs:299-328: search a byte stream (anything with .read(n)) in overlapping windows,
         calling `on_match(StreamMatch)` with absolute offsets; returns the bytes read."""
-        st = _Stream(self, threshold, window)
+        st = _Stream(self, threshold, window, prefilter=_prefilter)
         while True:
             chunk = reader.read(READ_CHUNK)
             for m in st.feed(chunk or b"", eof=not chunk):
@@ -246,9 +246,9 @@ class FuzzyAhoCorasick:
             if not chunk:
                 return st.total()
 
-    def stream_matches(self, reader, threshold: float, window: int = 0):
+    def stream_matches(self, reader, threshold: float, window: int = 0, _prefilter: bool = False):
         """stream.rs:330-352: the same, lazily, as an iterator of StreamMatch."""
-        st = _Stream(self, threshold, window)
+        st = _Stream(self, threshold, window, prefilter=_prefilter)
         while True:
             chunk = reader.read(READ_CHUNK)
             yield from st.feed(chunk or b"", eof=not chunk)
@@ -260,7 +260,8 @@ class FuzzyAhoCorasick:
         stream each, fac_stream); `threads` is accepted for API parity."""
         return self.search_stream(reader, threshold, on_match)
 
-    def replace_stream(self, reader, writer, threshold: float, callback, window: int = 0) -> int:
+    def replace_stream(self, reader, writer, threshold: float, callback, window: int = 0,
+                       _prefilter: bool = False) -> int:
         """stream.rs:462-503 + ReplaceCursor::emit_window (:645-705): streaming find-and-replace.
         Every owned match (per window: sorted().non_overlapping(), start < commit, ordered by
         (start, end)) is replaced by `callback(m)` (a str; None keeps the matched text) unless it
@@ -271,7 +272,7 @@ class FuzzyAhoCorasick:
         callable is called per match on the host."""
         if not callable(callback):
             table = callback if isinstance(callback, ReplacementTable) else ReplacementTable(self, callback)
-            st = _ReplaceStream(self, table, threshold, window)
+            st = _ReplaceStream(self, table, threshold, window, prefilter=_prefilter)
             while True:
                 chunk = reader.read(READ_CHUNK)
                 out = st.feed(chunk or b"", eof=not chunk)
@@ -279,7 +280,7 @@ class FuzzyAhoCorasick:
                     writer.write(out)
                 if not chunk:
                     return st.written()
-        st = _Stream(self, threshold, window)
+        st = _Stream(self, threshold, window, prefilter=_prefilter)
         pending = bytearray()  # stream bytes [emitted, read) not yet written
         emitted = written = 0
 
@@ -453,6 +454,26 @@ class Prefiltered:
     def search(self, haystack: str, opts: SearchOptions = None) -> FuzzyMatches:
         opts = opts or SearchOptions()
         return self.engine._search_ranked(haystack, opts.threshold_, opts.order_, opts.overlap_, prefilter=True)
+
+    # -- stream.rs over Prefiltered::search: every window's text goes through the bitap pre-filter on
+    # the device (fac_stream_open_ex / fac_replace_stream_open_ex); signatures as the engine's
+    def search_stream(self, reader, threshold: float, on_match, window: int = 0) -> int:
+        return self.engine.search_stream(reader, threshold, on_match, window, _prefilter=True)
+
+    def stream_matches(self, reader, threshold: float, window: int = 0):
+        return self.engine.stream_matches(reader, threshold, window, _prefilter=True)
+
+    def search_stream_parallel(self, reader, threshold: float, threads: int, on_match) -> int:
+        """As the engine's: two windows are in flight on the device; `threads` is accepted for API parity."""
+        return self.search_stream(reader, threshold, on_match)
+
+    def replace_stream(self, reader, writer, threshold: float, callback, window: int = 0) -> int:
+        """A table or list `callback` is spliced on the device; a callable runs over the pre-filtered
+        search stream on the host."""
+        return self.engine.replace_stream(reader, writer, threshold, callback, window, _prefilter=True)
+
+    def replace_stream_parallel(self, reader, writer, threads: int, threshold: float, callback) -> int:
+        return self.replace_stream(reader, writer, threshold, callback)
 
     def _batch_parts(self, enc):
         """Indices of the documents one pre-filtered batch takes: the ASCII ones (the device filter
@@ -661,9 +682,9 @@ class StreamMatch:
 class _Stream:
     """fac_stream: WindowReader + per-window search on the GPU (stream.rs:77-297)."""
 
-    def __init__(self, engine: "FuzzyAhoCorasick", threshold: float, window: int = 0):
+    def __init__(self, engine: "FuzzyAhoCorasick", threshold: float, window: int = 0, prefilter: bool = False):
         h = ctypes.c_void_p()
-        rc = _native.lib.fac_stream_open(engine._h, f32(threshold), window, ctypes.byref(h))
+        rc = _native.lib.fac_stream_open_ex(engine._h, f32(threshold), window, int(bool(prefilter)), ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h
@@ -693,6 +714,10 @@ class _Stream:
     def committed(self) -> int:
         return int(_native.lib.fac_stream_committed(self._h))
 
+    def windows_searched(self) -> int:
+        """Start windows of the segments searched for the windows handed out so far."""
+        return int(_native.lib.fac_stream_windows_searched(self._h))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and _native.lib is not None:
@@ -704,9 +729,11 @@ class _ReplaceStream:
     """fac_replace_stream: WindowReader + per-window search + the ReplaceCursor splice on the GPU
     (stream.rs:465-517, 645-705) against a ReplacementTable."""
 
-    def __init__(self, engine: "FuzzyAhoCorasick", table: "ReplacementTable", threshold: float, window: int = 0):
+    def __init__(self, engine: "FuzzyAhoCorasick", table: "ReplacementTable", threshold: float, window: int = 0,
+                 prefilter: bool = False):
         h = ctypes.c_void_p()
-        rc = _native.lib.fac_replace_stream_open(engine._h, table._h, f32(threshold), window, ctypes.byref(h))
+        rc = _native.lib.fac_replace_stream_open_ex(engine._h, table._h, f32(threshold), window, int(bool(prefilter)),
+                                                    ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h
@@ -726,6 +753,10 @@ class _ReplaceStream:
 
     def written(self) -> int:
         return int(_native.lib.fac_replace_stream_written(self._h))
+
+    def windows_searched(self) -> int:
+        """Start windows of the segments searched for the output handed out so far."""
+        return int(_native.lib.fac_replace_stream_windows_searched(self._h))
 
     def counts(self) -> Tuple[int, int]:
         """(records replaced, records skipped by the cursor's guard) in the output handed out so far."""
@@ -869,6 +900,20 @@ class StagedHaystack:
         if rc:
             _raise(rc)
         return int(t.value)
+
+    def symbol_ids(self, stream=None):
+        """fac_haystack_symbol_ids: the bitap pre-filter's symbol id of every staged grapheme
+        (prefilter.rs:247-281), computed on the device, as a NumPy uint8 array; None when the engine
+        has no filter."""
+        import numpy as np
+        out = np.zeros(max(1, self.graphemes), dtype=np.uint8)
+        n = _native.lib.fac_haystack_symbol_ids(self.engine._h, self._h, ctypes.c_void_p(stream or 0),
+                                                ctypes.c_void_p(out.ctypes.data), self.graphemes)
+        if n == -1:
+            return None
+        if n < 0:
+            _raise(int(-n))
+        return out[: int(n)]
 
     def stream_window(self, g_begin: int, g_end: int, commit_bytes: int, base: int, threshold: float,
                       prefilter: bool, stream=None):
@@ -1478,6 +1523,7 @@ class FuzzyReplacer:
         """`[self.replace(t, opts) for t in texts]` as one device pass (fac_replace_batch)."""
         return self.engine.replace_batch(texts, opts, self._device_table())
 
-    def replace_stream(self, reader, writer, threshold: float) -> int:
-        """replacer.rs:35-44, spliced on the device (fac_replace_stream_*)."""
-        return self.engine.replace_stream(reader, writer, threshold, self._device_table())
+    def replace_stream(self, reader, writer, threshold: float, prefilter: bool = False) -> int:
+        """replacer.rs:35-44, spliced on the device (fac_replace_stream_*); `prefilter`: every window
+        is searched through the bitap pre-filter (Prefiltered::search)."""
+        return self.engine.replace_stream(reader, writer, threshold, self._device_table(), _prefilter=prefilter)

@@ -202,6 +202,14 @@ uint64_t fac_haystack_graphemes(const fac_haystack* hay);
 /* Byte start of every staged grapheme (the device segmentation's result, for tests / hosts that
  * map windows to bytes). Writes up to `cap` entries, returns the grapheme count. */
 uint64_t fac_haystack_grapheme_starts(const fac_haystack* hay, uint64_t* out, uint64_t cap);
+/* Tests and hosts: the bitap pre-filter's symbol id of every staged grapheme (prefilter.rs:247-281;
+ * ids 1..255 in first-seen order over the patterns' folded graphemes, 0 = no pattern grapheme),
+ * computed on the device: the table lookup of the folded code-point sequence for a Unicode
+ * haystack, the per-byte table for an ASCII one. Writes up to `cap` ids to the host buffer `out`;
+ * returns the grapheme count, -1 if the engine has no filter (fac_prefilter_active == 0), or minus
+ * the error code. `stream` is a hipStream_t (NULL = the engine's stream). */
+int64_t fac_haystack_symbol_ids(const fac_engine* engine, const fac_haystack* hay, void* stream, uint8_t* out,
+                                uint64_t cap);
 void fac_haystack_free(fac_haystack* hay);
 
 /* Search start windows [window_begin, window_end) of a staged haystack (window_end is clamped
@@ -368,7 +376,8 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  *
  * Limits of the pre-filtered forms: where the filter runs, the batch must be all ASCII -- one
  * non-ASCII document gives FAC_E_UNSUPPORTED with nothing written (a non-ASCII document's symbol
- * ids need the per-grapheme folded-string lookup, which exists only on the host; the same limit
+ * symbol ids come from the device lookup of fac_haystack_symbol_ids, which the batch's one scan, cut
+ * at document starts in byte coordinates, is not wired to; the same limit
  * fac_stream_windows_staged_device has) -- and it holds at most 2^32 - 1 merged windows. Staging
  * errors stay fac_batch_stage's: a document over the grapheme limit fails there, which is stricter
  * than the crate, whose Prefiltered::search only checks each merged window it searches. */
@@ -639,6 +648,17 @@ int fac_render_batch_prefiltered(const fac_engine* engine, const fac_batch* batc
  * fac_buffer_free). Pass eof = 1 (data may be empty) once the input has ended. */
 typedef struct fac_stream fac_stream;
 int fac_stream_open(const fac_engine* engine, float threshold, uint64_t window_bytes, fac_stream** out);
+/* prefilter == 0: fac_stream_open. Otherwise every window is cut exactly as before and its text is
+ * searched as engine.with_prefilter().search(text, sorted().non_overlapping()) (stream.rs:262-297
+ * with Prefiltered::search, the semantics of fac_stream_window_staged(prefilter = 1)); ownership,
+ * offsets and the output order do not change. Where the reference falls back to the full search (no
+ * filter, or an edit budget over 24 at this threshold) the stream is the unfiltered stream. */
+int fac_stream_open_ex(const fac_engine* engine, float threshold, uint64_t window_bytes, int32_t prefilter,
+                       fac_stream** out);
+/* Tests and hosts: the start windows of the segments handed to the search launcher, for the windows
+ * handed out so far: the graphemes of every window's text for a plain stream (bytes where a window's
+ * text is ASCII), the lengths of every window's merged bitap windows for a pre-filtered one. */
+uint64_t fac_stream_windows_searched(const fac_stream* stream);
 int fac_stream_feed(fac_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, fac_match** out,
                     uint64_t* n_out, uint8_t** text, uint64_t* text_len);
 uint64_t fac_stream_total(const fac_stream* stream);
@@ -664,6 +684,10 @@ void fac_buffer_free(void* p);
 typedef struct fac_replace_stream fac_replace_stream;
 int fac_replace_stream_open(const fac_engine* engine, const fac_replacements* replacements, float threshold,
                             uint64_t window_bytes, fac_replace_stream** out);
+/* fac_replace_stream_open with fac_stream_open_ex's `prefilter`; the replace cursor does not change. */
+int fac_replace_stream_open_ex(const fac_engine* engine, const fac_replacements* replacements, float threshold,
+                               uint64_t window_bytes, int32_t prefilter, fac_replace_stream** out);
+uint64_t fac_replace_stream_windows_searched(const fac_replace_stream* stream);
 int fac_replace_stream_feed(fac_replace_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, uint8_t** out,
                             uint64_t* out_len);
 /* Bytes handed out so far: replace_stream's return value (ReplaceCursor::written) after the feed with eof. */
