@@ -509,6 +509,17 @@ uint64_t fac_haystack_grapheme_starts(const fac_haystack* hay, uint64_t* out, ui
   return h.n;
 }
 
+uint64_t fac_haystack_text_chars(const fac_haystack* hay, uint32_t* out, uint64_t cap) {
+  if (!hay) return 0;
+  const fac::Haystack& h = hay->h;
+  if (h.ascii || !h.d_text32 || h.n == 0) return 0;
+  const uint64_t k = std::min(h.n, cap);
+  if (out && k &&
+      (hipSetDevice(h.device) != hipSuccess || hipMemcpy(out, h.d_text32, k * 4, hipMemcpyDeviceToHost) != hipSuccess))
+    return 0;
+  return h.n;
+}
+
 int64_t fac_haystack_symbol_ids(const fac_engine* engine, const fac_haystack* hay, void* stream, uint8_t* out,
                                 uint64_t cap) {
   if (!engine || !hay || (cap && !out)) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
@@ -1279,6 +1290,22 @@ uint64_t fac_batch_grapheme_starts(const fac_batch* batch, uint64_t d, uint64_t*
   }
   if (hipMemcpy(out, b.h.d_off + ex.u, k * 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   for (uint64_t g = 0; g < k; ++g) out[g] = (out[g] & ((1ull << fac::kDocTagShift) - 1)) - lo;
+  return n;
+}
+
+uint64_t fac_batch_text_chars(const fac_batch* batch, uint64_t d, uint32_t* out, uint64_t cap) {
+  if (!batch || d >= batch->b.n_docs) return 0;
+  const fac::Batch& b = batch->b;
+  uint32_t f = 0;
+  fac::BatchTri t{0, 0, 0}, ex{0, 0, 0};
+  if (hipSetDevice(b.h.device) != hipSuccess || hipMemcpy(&f, b.d_flags + d, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  if (!(f & 2u) || !b.h.d_text32) return 0;  // an ASCII document has no folded characters
+  if (hipMemcpy(&t, b.d_tri_in + d, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&ex, b.d_tri_ex + d, sizeof(ex), hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  const uint64_t n = t.w, k = std::min(n, cap);
+  if (out && k && hipMemcpy(out, b.h.d_text32 + ex.u, k * 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return n;
 }
 

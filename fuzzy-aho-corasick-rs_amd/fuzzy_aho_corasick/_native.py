@@ -158,6 +158,7 @@ SIGNATURES = {
     "fac_haystack_graphemes": (ctypes.c_uint64, [_hay_p]),
     "fac_haystack_free": (None, [_hay_p]),
     "fac_haystack_grapheme_starts": (ctypes.c_uint64, [_hay_p, _u64p, ctypes.c_uint64]),
+    "fac_haystack_text_chars": (ctypes.c_uint64, [_hay_p, _P(ctypes.c_uint32), ctypes.c_uint64]),
     "fac_search_staged": (ctypes.c_int, [_engine_p, _hay_p, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_float, ctypes.c_void_p, _P(_P(fac_match)), _u64p,
                                          _P(fac_stats)]),
@@ -231,6 +232,7 @@ SIGNATURES = {
     "fac_batch_docs": (ctypes.c_uint64, [ctypes.c_void_p]),
     "fac_batch_doc_graphemes": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_int32)]),
     "fac_batch_grapheme_starts": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _u64p, ctypes.c_uint64]),
+    "fac_batch_text_chars": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint32), ctypes.c_uint64]),
     "fac_search_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_batch_args), _P(_P(fac_match)), _u64p,
                                         _u64p, _P(fac_stats)]),
     "fac_search_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_batch_args), _P(_P(fac_match)),

@@ -901,6 +901,24 @@ class StagedHaystack:
             _raise(rc)
         return int(t.value)
 
+    def grapheme_starts(self):
+        """fac_haystack_grapheme_starts: the byte start of every staged grapheme (the device
+        segmentation's result), as a NumPy uint64 array."""
+        import numpy as np
+        out = np.zeros(max(1, self.graphemes), dtype=np.uint64)
+        n = _native.lib.fac_haystack_grapheme_starts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                     self.graphemes)
+        return out[: min(int(n), self.graphemes)]
+
+    def text_chars(self):
+        """fac_haystack_text_chars: the folded first code point of every staged grapheme, as the device
+        staging wrote it, as a NumPy uint32 array (empty for an ASCII haystack, which has none)."""
+        import numpy as np
+        out = np.zeros(max(1, self.graphemes), dtype=np.uint32)
+        n = _native.lib.fac_haystack_text_chars(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                self.graphemes)
+        return out[: min(int(n), self.graphemes)]
+
     def symbol_ids(self, stream=None):
         """fac_haystack_symbol_ids: the bitap pre-filter's symbol id of every staged grapheme
         (prefilter.rs:247-281), computed on the device, as a NumPy uint8 array; None when the engine
@@ -1161,6 +1179,21 @@ class StagedBatch:
         buf = (ctypes.c_uint64 * max(1, n))()
         k = _native.lib.fac_batch_grapheme_starts(self._h, d, buf, n)
         return list(buf[:min(n, k)])
+
+    def grapheme_starts_into(self, d: int, out):
+        """grapheme_starts(d) written into the NumPy uint64 buffer `out` (no Python list): the filled
+        prefix of `out`."""
+        n = _native.lib.fac_batch_grapheme_starts(self._h, d, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(out))
+        return out[: min(int(n), len(out))]
+
+    def text_chars(self, d: int, out=None):
+        """fac_batch_text_chars: the folded first code point of every grapheme of document d as a NumPy
+        uint32 array (the filled prefix of `out` when given; empty for an ASCII document)."""
+        import numpy as np
+        if out is None:
+            out = np.zeros(max(1, self.doc_graphemes(d)[0]), dtype=np.uint32)
+        n = _native.lib.fac_batch_text_chars(self._h, d, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(out))
+        return out[: min(int(n), len(out))]
 
     def _args(self, opts: SearchOptions, stream=None) -> "_native.fac_batch_args":
         a = _native.fac_batch_args()

@@ -202,6 +202,11 @@ uint64_t fac_haystack_graphemes(const fac_haystack* hay);
 /* Byte start of every staged grapheme (the device segmentation's result, for tests / hosts that
  * map windows to bytes). Writes up to `cap` entries, returns the grapheme count. */
 uint64_t fac_haystack_grapheme_starts(const fac_haystack* hay, uint64_t* out, uint64_t cap);
+/* Tests and hosts: the folded first code point of every staged grapheme (search.rs:406-412: its
+ * lowercase's first code point for a case-insensitive engine, else the code point itself), as the
+ * device staging wrote it. Writes up to `cap` entries, returns the grapheme count. An ASCII haystack
+ * has no such array (its bytes are searched as they are): nothing is written and 0 is returned. */
+uint64_t fac_haystack_text_chars(const fac_haystack* hay, uint32_t* out, uint64_t cap);
 /* Tests and hosts: the bitap pre-filter's symbol id of every staged grapheme (prefilter.rs:247-281;
  * ids 1..255 in first-seen order over the patterns' folded graphemes, 0 = no pattern grapheme),
  * computed on the device: the table lookup of the folded code-point sequence for a Unicode
@@ -408,6 +413,9 @@ uint64_t fac_batch_docs(const fac_batch* batch);
  * starts (writes up to `cap` entries, returns the count). */
 uint64_t fac_batch_doc_graphemes(const fac_batch* batch, uint64_t d, int32_t* is_ascii);
 uint64_t fac_batch_grapheme_starts(const fac_batch* batch, uint64_t d, uint64_t* out, uint64_t cap);
+/* Tests and hosts: the folded first code point of every grapheme of document d (as
+ * fac_haystack_text_chars; 0 and nothing written for an ASCII document). */
+uint64_t fac_batch_text_chars(const fac_batch* batch, uint64_t d, uint32_t* out, uint64_t cap);
 
 typedef struct fac_batch_args {
   float threshold;

@@ -9,7 +9,8 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 BATCH_NAMES = ["fac_batch_stage", "fac_batch_stage_device", "fac_batch_free", "fac_batch_docs",
-               "fac_batch_doc_graphemes", "fac_batch_grapheme_starts", "fac_search_batch"]
+               "fac_batch_doc_graphemes", "fac_batch_grapheme_starts", "fac_batch_text_chars",
+               "fac_haystack_text_chars", "fac_search_batch"]
 
 
 def test_batch_offsets_round_trips():
@@ -65,5 +66,8 @@ def test_batch_entry_points_are_bound():
         assert hasattr(lib, name), name
     import fuzzy_aho_corasick as fac
     assert hasattr(fac.FuzzyAhoCorasick, "search_batch")
-    for meth in ("from_device", "search_records", "doc_graphemes", "grapheme_starts"):
+    for meth in ("from_device", "search_records", "doc_graphemes", "grapheme_starts", "grapheme_starts_into",
+                 "text_chars"):
         assert hasattr(fac.StagedBatch, meth), meth
+    for meth in ("grapheme_starts", "text_chars"):
+        assert hasattr(fac.StagedHaystack, meth), meth
