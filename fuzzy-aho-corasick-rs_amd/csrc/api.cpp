@@ -1139,13 +1139,14 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
 // The reference falls back to the plain search when the engine has no filter or some pattern's
 // k_for exceeds 24 (prefilter.rs:151-155, 311-317): engine and threshold alone decide, so a fallback
 // call is the plain batch call for any batch. Where the filter runs, the batch must be all ASCII
-// (its one scan resets at document starts in byte coordinates; Unicode documents are not wired in).
+// (its one scan resets at document starts in byte coordinates) or opted in
+// (fac_batch_allow_unicode_prefilter: the scan runs over symbols, fac_internal.h Batch::unicode_pf).
 static int batch_prefilter(const fac::Engine& e, const fac::Batch& b, float threshold, bool prefilter, hipStream_t st,
                            fac::BatchWindows& pw, bool& filtered, fac_stats* stats, std::string& err) {
   filtered = false;
   std::vector<uint32_t> ks;
   if (!prefilter || !e.bitap_ok || !prefilter_ks(e, threshold, ks)) return FAC_OK;
-  if (!b.h.ascii) {
+  if (!b.h.ascii && !b.unicode_pf) {
     err = "pre-filtered batches need an all-ASCII batch (search the other documents one by one)";
     return FAC_E_UNSUPPORTED;
   }
@@ -1257,6 +1258,12 @@ void fac_batch_free(fac_batch* batch) {
 }
 
 uint64_t fac_batch_docs(const fac_batch* batch) { return batch ? batch->b.n_docs : 0; }
+
+int fac_batch_allow_unicode_prefilter(fac_batch* batch, int32_t on) {
+  if (!batch) return fail(FAC_E_INVALID, "NULL argument");
+  batch->b.unicode_pf = on != 0;
+  return FAC_OK;
+}
 
 uint64_t fac_batch_doc_graphemes(const fac_batch* batch, uint64_t d, int32_t* is_ascii) {
   if (is_ascii) *is_ascii = 1;
@@ -1419,9 +1426,17 @@ int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* b
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e.stream;
   std::string err;
   fac::BatchWindows pw;
+  pw.want_tri = !b.h.ascii;
   bool filtered = false;
   if (int rc = batch_prefilter(e, b, threshold, true, st, pw, filtered, nullptr, err)) return -(int64_t)fail(rc, err);
   if (!filtered) return -1;
+  if (!b.h.ascii) {  // symbol offsets: a slice's descriptor holds bytes or batch-wide graphemes
+    const uint64_t k = std::min(pw.n, cap);
+    if (k && (hipMemcpyAsync(out, pw.d_tri, k * 24, hipMemcpyDeviceToHost, st) != hipSuccess ||
+              hipStreamSynchronize(st) != hipSuccess))
+      return -(int64_t)fail(FAC_E_HIP, "copy of the batch's merged windows failed");
+    return (int64_t)pw.n;
+  }
   // (diagnostics: the descriptors and the offsets come back to the host)
   std::vector<fac::SegDesc> segs(pw.n);
   std::vector<uint64_t> off(b.n_docs + 1, 0);

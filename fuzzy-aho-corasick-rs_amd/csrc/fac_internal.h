@@ -508,7 +508,21 @@ struct Batch {
   mutable uint32_t* d_dstart = nullptr;
   mutable uint64_t dstart_cap = 0;  // words d_dstart holds
   mutable bool dstart_ready = false;
+  // fac_batch_allow_unicode_prefilter: a batch with non-ASCII documents may take the pre-filtered
+  // calls. Its scan runs in the batch's start-window space (d_prefix: a symbol is a byte of an ASCII
+  // document, a grapheme of any other); d_sstart is that space's document-start bitmap, one bit per
+  // symbol, built and kept as d_dstart is (same mutex). The flag survives a restage in place.
+  bool unicode_pf = false;
+  mutable uint32_t* d_sstart = nullptr;
+  mutable uint64_t sstart_cap = 0;  // words d_sstart holds
+  mutable bool sstart_ready = false;
 };
+// stage_kernels.hip: the pre-filter's symbol id of all b.windows symbols of a batch with non-ASCII
+// documents (ascii_id[byte] in an ASCII document, the GraphemeTable lookup of the folded grapheme in
+// any other), written to d_ids on st (asynchronous): batch_symbol_ids_kernel
+int batch_symbol_ids_device(const Engine& e, const Batch& b, uint8_t* d_ids, hipStream_t st, std::string& err);
+// stage_kernels.hip: sets bit d_prefix[k] of d_bits (zeroed by the caller) for every non-empty document k
+int batch_symbol_starts_device(const Batch& b, uint32_t* d_bits, hipStream_t st, std::string& err);
 // stage_kernels.hip: d_out[i] = d_in[0] + ... + d_in[i - 1] for i < n, on st (asynchronous)
 int exclusive_sum_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n, hipStream_t st, std::string& err);
 // stage_kernels.hip: stages the documents [d_offsets[d], d_offsets[d + 1]) of b.h.d_utf8 (b.h.len
@@ -745,7 +759,8 @@ int launch_search_sink(const Engine& e, const Haystack& h, const std::vector<Seg
 // The prefix cache is gated by the batch's own rule, not by windows per segment.
 int launch_search_batch(const Engine& e, const Batch& b, float thr, hipStream_t stream, MatchSink& sink,
                         fac_stats* stats, std::string& err);
-// Prefiltered::raw of every document of an all-ASCII batch (prefilter.rs:304-374 per document; ks:
+// Prefiltered::raw of every document of a batch, all ASCII or opted in (Batch::unicode_pf;
+// prefilter.rs:304-374 per document; ks:
 // prefilter_ks' edit budgets): one bitap pass over the concatenated bytes with the automaton reset
 // and the coverage cut at every document start (batch_prefilter_windows), then each merged window
 // searched as a haystack of its own, one segment of one launch_pass (launch_search_batch_windows).
@@ -758,9 +773,15 @@ struct BatchWindows {
   uint64_t* d_prefix = nullptr;  // n + 1 entries
   uint64_t n = 0;        // merged windows of all documents
   uint64_t windows = 0;  // their lengths summed: the start windows to search
+  // want_tri (a batch with non-ASCII documents, fac_batch_prefilter_windows): d_tri receives per
+  // window {document, start, end} in document-relative symbols (bytes of an ASCII document,
+  // graphemes of any other), which the descriptor of a slice no longer tells
+  bool want_tri = false;
+  uint64_t* d_tri = nullptr;
   ~BatchWindows() {
     if (d_segs) call_scratch_give(d_segs, s);
     if (d_prefix) call_scratch_give(d_prefix, s);
+    if (d_tri) call_scratch_give(d_tri, s);
   }
 };
 int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<uint32_t>& ks, hipStream_t stream,

@@ -4898,6 +4898,108 @@ __global__ void runs_docs_write_kernel(const uint32_t* __restrict__ cover, const
     ++idx;
   }
 }
+// The same for a batch that holds non-ASCII documents, whose runs are in the batch's start-window
+// space (Batch::d_prefix): run [s, e) lies in non-empty document k, found by bisection, at local
+// symbols [i, i + e - s). In an ASCII document that is runs_docs_write_kernel's descriptor. In any
+// other it is the slice of graphemes [gs, ge) = bytes [bs, be) (stage_kernels.hip slice_desc_kernel,
+// tagged), written here as a Unicode slice; slice_ascii_kernel then turns the all-ASCII slices into
+// byte texts (search_raw decides is_ascii per slice, prefilter.rs:349-350). tri (optional): the
+// window as {document, start, end} in document-relative symbols.
+__global__ void runs_docs_write_mixed_kernel(const uint32_t* __restrict__ cover, const uint32_t* __restrict__ ds,
+                                             uint64_t n_words, uint64_t n, const uint64_t* __restrict__ pos,
+                                             const uint64_t* __restrict__ off, const SegDesc* __restrict__ dsegs,
+                                             const uint64_t* __restrict__ dprefix, uint64_t n_segs,
+                                             SegDesc* __restrict__ segs, uint64_t* __restrict__ lens,
+                                             uint64_t* __restrict__ tri) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n_words) return;
+  uint32_t starts = run_starts(cover, ds, w, n);
+  uint64_t idx = pos[w];
+  constexpr uint64_t kByte = (1ull << kDocTagShift) - 1;
+  while (starts) {
+    const uint32_t b = __ffs(starts) - 1;
+    starts &= starts - 1;
+    const uint64_t s = w * 32 + b;
+    uint64_t e = n;  // the first clear bit or document start after s
+    for (uint64_t ww = w; ww < n_words; ++ww) {
+      uint32_t stop = ~cover[ww] | ds[ww];
+      if (ww == w) stop &= b == 31 ? 0u : (0xFFFFFFFFu << (b + 1));
+      if (stop) {
+        e = min(n, ww * 32 + (uint64_t)__builtin_ctz(stop));
+        break;
+      }
+    }
+    uint64_t lo = 0, hi = n_segs;  // the last non-empty document with dprefix[k] <= s
+    while (hi - lo > 1) {
+      const uint64_t mid = (lo + hi) / 2;
+      if (dprefix[mid] <= s) lo = mid;
+      else hi = mid;
+    }
+    const SegDesc D = dsegs[lo];
+    const uint64_t doc = D.byte_base >> kDocTagShift, i = s - dprefix[lo], cnt = e - s;
+    SegDesc S;
+    if (D.ascii) {
+      S.text_base = D.text_base + i;
+      S.n = cnt;
+      S.hay_len = cnt;
+      S.byte_base = S.text_base | (doc << kDocTagShift);
+      S.ascii = 1u;
+    } else {
+      const uint64_t gs = D.text_base + i, ge = gs + cnt;
+      const uint64_t bs = off[gs] & kByte;
+      const uint64_t be = i + cnt < D.n ? off[ge] & kByte : (D.byte_base & kByte) + D.hay_len;
+      S.text_base = gs;
+      S.n = cnt;
+      S.hay_len = be - bs;
+      S.byte_base = bs | (doc << kDocTagShift);
+      S.ascii = 0u;
+    }
+    S.avail = S.n;
+    S.w_begin = 0;
+    S.w_end = S.n;
+    S.pad = 0;
+    segs[idx] = S;
+    lens[idx] = S.n;
+    if (tri) {
+      tri[3 * idx] = doc;
+      tri[3 * idx + 1] = i;
+      tri[3 * idx + 2] = i + cnt;
+    }
+    ++idx;
+  }
+}
+// One wave per merged window: the OR of the bytes of a Unicode slice (a window can be long); a slice
+// without a high bit becomes the ASCII text of its bytes. Windows of ASCII documents return at once.
+__global__ __launch_bounds__(256) void slice_ascii_kernel(const uint8_t* __restrict__ utf8, uint64_t len,
+                                                          SegDesc* __restrict__ segs, uint64_t* __restrict__ lens,
+                                                          uint64_t n_runs) {
+  const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_runs) return;
+  if (segs[r].ascii) return;
+  constexpr uint64_t kByte = (1ull << kDocTagShift) - 1;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t bs = segs[r].byte_base & kByte, cnt = segs[r].hay_len;
+  if (bs + cnt > len) return;  // (never for a staged batch)
+  const uint8_t* p = utf8 + bs;
+  const uint64_t mis = (8u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 7u)) & 7u;
+  const uint64_t head = mis < cnt ? mis : cnt;
+  const uint64_t words = (cnt - head) / 8, tail = head + words * 8;
+  uint64_t acc = 0;
+  for (uint64_t i = lane; i < head; i += 64) acc |= p[i];
+  const uint64_t* q = reinterpret_cast<const uint64_t*>(p + head);
+  for (uint64_t i = lane; i < words; i += 64) acc |= q[i];
+  for (uint64_t i = tail + lane; i < cnt; i += 64) acc |= p[i];
+  const bool high = __ballot((acc & 0x8080808080808080ull) != 0) != 0;
+  if (high || lane != 0) return;
+  SegDesc S = segs[r];
+  S.ascii = 1u;
+  S.text_base = bs;
+  S.n = cnt;
+  S.avail = cnt;
+  S.w_end = cnt;
+  segs[r] = S;
+  lens[r] = cnt;
+}
 // The document-start bitmap: one thread per document, one bit per non-empty document
 __global__ void doc_starts_kernel(const uint64_t* __restrict__ off, uint64_t n_docs, uint32_t* __restrict__ ds) {
   const uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -7152,50 +7254,69 @@ int prefilter_windows_ex(const Engine& e, const Haystack& h, const SegDesc& view
 // (documents are disjoint, so no second bitmap and no window table). Runs are counted per bitmap
 // word, scanned and written in place as segment descriptors, so they are sorted by start -- by
 // document, then by start -- without a sort, and nothing per document or per run visits the host.
+// A batch with non-ASCII documents (Batch::unicode_pf) is scanned in its start-window space instead:
+// one symbol per byte of an ASCII document and per grapheme of any other (batch_symbol_ids_kernel),
+// the document starts of that space (Batch::d_sstart), always in ids mode; its runs become byte or
+// grapheme slices (runs_docs_write_mixed_kernel, slice_ascii_kernel). The scan, verify and count
+// kernels are the same instantiations: they see ids, a start bitmap, a coverage bitmap and a length.
 int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<uint32_t>& ks, hipStream_t stream,
                             BatchWindows& out, fac_stats* stats, std::string& err) {
   HIP_TRY(hipSetDevice(e.device));
   if (!stream) stream = e.stream;
   const Haystack& h = b.h;
-  const uint64_t n = h.len;
+  // a batch with non-ASCII documents (opted in): the scan's positions are the batch's start windows
+  const bool mixed = !h.ascii;
+  const uint64_t n = mixed ? b.windows : h.len;
   out.s = stream;
   out.n = out.windows = 0;
-  if (!h.ascii) {
+  if (mixed && !b.unicode_pf) {
     err = "pre-filtered batches need an all-ASCII batch";
     return FAC_E_UNSUPPORTED;
   }
   if (n == 0 || b.n_segs == 0) return FAC_OK;
   const uint64_t n_words = (n + 31) / 32;
-  {  // the document-start bitmap, once per staging
+  {  // the document-start bitmap of the scan's positions, once per staging
     std::lock_guard<std::mutex> lk(b.dstart_mu);
-    if (!b.dstart_ready) {
-      if (b.dstart_cap < n_words) {
-        if (b.d_dstart) HIP_TRY(hipFree(b.d_dstart));
-        b.d_dstart = nullptr;
-        b.dstart_cap = 0;
-        HIP_TRY(hipMalloc((void**)&b.d_dstart, n_words * 4));
-        b.dstart_cap = n_words;
+    uint32_t*& d_bits = mixed ? b.d_sstart : b.d_dstart;
+    uint64_t& cap = mixed ? b.sstart_cap : b.dstart_cap;
+    bool& ready = mixed ? b.sstart_ready : b.dstart_ready;
+    if (!ready) {
+      if (cap < n_words) {
+        if (d_bits) HIP_TRY(hipFree(d_bits));
+        d_bits = nullptr;
+        cap = 0;
+        HIP_TRY(hipMalloc((void**)&d_bits, n_words * 4));
+        cap = n_words;
       }
-      HIP_TRY(hipMemsetAsync(b.d_dstart, 0, n_words * 4, stream));
-      hipLaunchKernelGGL(doc_starts_kernel, dim3((uint32_t)((b.n_docs + 255) / 256)), dim3(256), 0, stream, b.d_offsets,
-                         b.n_docs, b.d_dstart);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemsetAsync(d_bits, 0, n_words * 4, stream));
+      if (mixed) {
+        if (int rc = batch_symbol_starts_device(b, d_bits, stream, err)) return rc;
+      } else {
+        hipLaunchKernelGGL(doc_starts_kernel, dim3((uint32_t)((b.n_docs + 255) / 256)), dim3(256), 0, stream, b.d_offsets,
+                           b.n_docs, d_bits);
+        HIP_TRY(hipGetLastError());
+      }
       HIP_TRY(hipStreamSynchronize(stream));  // (another stream's search may use it next)
-      b.dstart_ready = true;
+      ready = true;
     }
   }
+  const uint32_t* d_starts = mixed ? b.d_sstart : b.d_dstart;
   const uint8_t* vb = h.d_utf8;
-  const bool want_bytes = ((uintptr_t)h.d_utf8 & 15u) == 0 && !diag_env("FAC_QGRAM_IDS");
+  const bool want_bytes = !mixed && ((uintptr_t)h.d_utf8 & 15u) == 0 && !diag_env("FAC_QGRAM_IDS");
   const PfTables* T = nullptr;
   if (int rc = pf_tables(e, ks, want_bytes, T, err)) return rc;
   const uint32_t nw = T->nw;
   PoolBuf d_ids, d_cover, d_cnt, d_pos, d_lens;
-  if (!T->bytes) {  // transcode (prefilter.rs:253-258): the symbol ids of every document's bytes
+  if (!T->bytes) {  // transcode (prefilter.rs:253-280): the symbol ids of every document
     HIP_TRY(d_ids.alloc(n + 80, stream));
-    const uint64_t threads = (n + 15) / 16;
-    hipLaunchKernelGGL(transcode_ascii_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, vb, n,
-                       e.d_ascii_id, static_cast<uint8_t*>(d_ids.p));
-    HIP_TRY(hipGetLastError());
+    if (mixed) {
+      if (int rc = batch_symbol_ids_device(e, b, static_cast<uint8_t*>(d_ids.p), stream, err)) return rc;
+    } else {
+      const uint64_t threads = (n + 15) / 16;
+      hipLaunchKernelGGL(transcode_ascii_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, vb, n,
+                         e.d_ascii_id, static_cast<uint8_t*>(d_ids.p));
+      HIP_TRY(hipGetLastError());
+    }
   }
   HIP_TRY(d_cover.alloc(n_words * 4, stream));
   HIP_TRY(hipMemsetAsync(d_cover.p, 0, n_words * 4, stream));
@@ -7213,7 +7334,7 @@ int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<u
     B.n_words = nw;
     B.seg_len = 4096;
     B.cover = static_cast<uint32_t*>(d_cover.p);
-    B.dstart = b.d_dstart;
+    B.dstart = d_starts;
     const uint64_t waves = ((n + B.seg_len - 1) / B.seg_len) * ((nw + 63) / 64);
     launch_bitap<true>(*T, B, dim3((uint32_t)std::max<uint64_t>(1, (waves + 3) / 4)), stream);
     HIP_TRY(hipGetLastError());
@@ -7221,7 +7342,7 @@ int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<u
   QgramBufs qb;
   if (T->q) {
     QgramParams Q = qgram_params(e, h, *T, vb, d_ids.p, n, d_cover.p);
-    Q.dstart = b.d_dstart;
+    Q.dstart = d_starts;
     dim3 vg;
     unsigned long long nc = 0;
     if (int rc = qgram_candidates(e, *T, Q, n, stream, qb, vg, nc, err)) return rc;
@@ -7233,7 +7354,7 @@ int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<u
   HIP_TRY(d_cnt.alloc((n_words + 1) * 8, stream));
   HIP_TRY(d_pos.alloc((n_words + 1) * 8, stream));
   hipLaunchKernelGGL(runs_docs_count_kernel, dim3((uint32_t)((n_words + 1 + 255) / 256)), dim3(256), 0, stream, cov,
-                     b.d_dstart, n_words, n, static_cast<uint64_t*>(d_cnt.p));
+                     d_starts, n_words, n, static_cast<uint64_t*>(d_cnt.p));
   HIP_TRY(hipGetLastError());
   if (int rc = exclusive_sum_u64(static_cast<const uint64_t*>(d_cnt.p), static_cast<uint64_t*>(d_pos.p), n_words + 1, stream, err))
     return rc;
@@ -7253,9 +7374,22 @@ int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<u
     HIP_TRY(he);
     HIP_TRY(d_lens.alloc((n_runs + 1) * 8, stream));
     HIP_TRY(hipMemsetAsync(static_cast<uint64_t*>(d_lens.p) + n_runs, 0, 8, stream));
-    hipLaunchKernelGGL(runs_docs_write_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, stream, cov, b.d_dstart,
-                       n_words, n, static_cast<const uint64_t*>(d_pos.p), b.d_offsets, b.n_docs, out.d_segs,
-                       static_cast<uint64_t*>(d_lens.p));
+    if (mixed) {
+      if (out.want_tri) {
+        out.d_tri = static_cast<uint64_t*>(call_scratch_take(n_runs * 24, stream, &he));
+        HIP_TRY(he);
+      }
+      hipLaunchKernelGGL(runs_docs_write_mixed_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, stream, cov,
+                         d_starts, n_words, n, static_cast<const uint64_t*>(d_pos.p), h.d_off, b.d_segs, b.d_prefix, b.n_segs,
+                         out.d_segs, static_cast<uint64_t*>(d_lens.p), out.d_tri);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(slice_ascii_kernel, dim3((uint32_t)((n_runs + 3) / 4)), dim3(256), 0, stream, h.d_utf8, h.len,
+                         out.d_segs, static_cast<uint64_t*>(d_lens.p), n_runs);
+    } else {
+      hipLaunchKernelGGL(runs_docs_write_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, stream, cov, d_starts,
+                         n_words, n, static_cast<const uint64_t*>(d_pos.p), b.d_offsets, b.n_docs, out.d_segs,
+                         static_cast<uint64_t*>(d_lens.p));
+    }
     HIP_TRY(hipGetLastError());
     if (int rc = exclusive_sum_u64(static_cast<const uint64_t*>(d_lens.p), out.d_prefix, n_runs + 1, stream, err)) return rc;
     HIP_TRY(hipMemcpyAsync(&total, out.d_prefix + n_runs, 8, hipMemcpyDeviceToHost, stream));
@@ -7265,9 +7399,9 @@ int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<u
   out.n = n_runs;
   out.windows = total;
   if (diag_env("FAC_RC_DEBUG"))
-    std::fprintf(stderr, "FAC_BATCH_PF docs=%llu bytes=%llu full-scan words=%u qgram patterns=%zu/%zu bytes-mode=%d merged windows=%llu start windows=%llu\n",
-                 (unsigned long long)b.n_docs, (unsigned long long)n, nw, T->n_qpat, e.bp_m.size(), (int)T->bytes,
-                 (unsigned long long)n_runs, (unsigned long long)total);
+    std::fprintf(stderr, "FAC_BATCH_PF docs=%llu bytes=%llu full-scan words=%u qgram patterns=%zu/%zu bytes-mode=%d merged windows=%llu start windows=%llu unicode=%d symbols=%llu\n",
+                 (unsigned long long)b.n_docs, (unsigned long long)h.len, nw, T->n_qpat, e.bp_m.size(), (int)T->bytes,
+                 (unsigned long long)n_runs, (unsigned long long)total, (int)mixed, (unsigned long long)n);
   if (stats) {
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));

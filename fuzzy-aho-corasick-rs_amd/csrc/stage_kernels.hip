@@ -748,39 +748,34 @@ __global__ void grapheme_table_build_kernel(const uint32_t* __restrict__ pool, c
     if (atomicCAS(&slots[s], 0u, k + 1) == 0u) return;
 }
 
-// One thread per grapheme g of [g0, g1): bytes [off[g], off[g + 1]) (the last grapheme ends at len)
-// are decoded and folded twice -- once for the hash and the length, once per probed entry of equal
-// hash and length to compare its key -- so a grapheme of any length needs no buffer. The table
-// (<= 255 symbols) is copied to LDS when it fits (lds != 0); the loads of off are coalesced and a
-// wave's graphemes are contiguous bytes. ids[g - g0] = the id, 0 = no pattern grapheme.
-__global__ __launch_bounds__(256) void symbol_ids_kernel(const uint8_t* __restrict__ utf8, uint64_t len,
-                                                         const uint64_t* __restrict__ off, uint64_t n, uint64_t g0,
-                                                         uint64_t g1, const uint16_t* __restrict__ ltab, int ci,
-                                                         const uint32_t* __restrict__ g_slots, const uint4* __restrict__ g_ents,
-                                                         const uint32_t* __restrict__ g_pool, uint32_t mask, uint32_t n_keys,
-                                                         uint32_t n_pool, int lds, uint8_t* __restrict__ ids) {
+// The engine's table as a lookup reads it: from LDS when it fits (lds != 0: mask + 1 <= kGtSlotsLds,
+// n_keys <= kGtKeysLds, n_pool <= kGtPoolLds, checked by the host), else from global memory.
+struct GtView {
+  const uint32_t* slots;
+  const uint4* ents;
+  const uint32_t* pool;
+  uint32_t mask;
+};
+// Called by every thread of the workgroup (it synchronises when it copies).
+__device__ __forceinline__ GtView gt_view(const uint32_t* __restrict__ g_slots, const uint4* __restrict__ g_ents,
+                                          const uint32_t* __restrict__ g_pool, uint32_t mask, uint32_t n_keys,
+                                          uint32_t n_pool, int lds) {
   __shared__ uint32_t s_slots[kGtSlotsLds];
   __shared__ uint4 s_ents[kGtKeysLds];
   __shared__ uint32_t s_pool[kGtPoolLds];
-  const uint32_t* slots = g_slots;
-  const uint4* ents = g_ents;
-  const uint32_t* pool = g_pool;
-  if (lds) {  // (mask + 1 <= kGtSlotsLds, n_keys <= kGtKeysLds, n_pool <= kGtPoolLds: checked by the host)
-    for (uint32_t i = threadIdx.x; i <= mask; i += blockDim.x) s_slots[i] = g_slots[i];
-    for (uint32_t i = threadIdx.x; i < n_keys; i += blockDim.x) s_ents[i] = g_ents[i];
-    for (uint32_t i = threadIdx.x; i < n_pool; i += blockDim.x) s_pool[i] = g_pool[i];
-    __syncthreads();
-    slots = s_slots;
-    ents = s_ents;
-    pool = s_pool;
-  }
-  const uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= g1 || g >= n) return;
-  const uint64_t b = off[g], e = g + 1 < n ? off[g + 1] : len;
-  if (b >= e || e > len) {  // (never for a staged haystack)
-    ids[g - g0] = 0;
-    return;
-  }
+  if (!lds) return GtView{g_slots, g_ents, g_pool, mask};
+  for (uint32_t i = threadIdx.x; i <= mask; i += blockDim.x) s_slots[i] = g_slots[i];
+  for (uint32_t i = threadIdx.x; i < n_keys; i += blockDim.x) s_ents[i] = g_ents[i];
+  for (uint32_t i = threadIdx.x; i < n_pool; i += blockDim.x) s_pool[i] = g_pool[i];
+  __syncthreads();
+  return GtView{s_slots, s_ents, s_pool, mask};
+}
+
+// The id of the grapheme at bytes [b, e), 0 = no pattern grapheme: the bytes are decoded and folded
+// twice -- once for the hash and the length, once per probed entry of equal hash and length to
+// compare its key -- so a grapheme of any length needs no buffer.
+__device__ __forceinline__ uint32_t grapheme_symbol_id(const uint8_t* __restrict__ utf8, uint64_t b, uint64_t e,
+                                                       const uint16_t* __restrict__ ltab, int ci, const GtView& t) {
   uint32_t h = kGtHashInit, cnt = 0;
   for_folded(utf8, b, e, ltab, ci, [&](uint32_t cp) {
     h = gt_hash_step(h, cp);
@@ -788,25 +783,99 @@ __global__ __launch_bounds__(256) void symbol_ids_kernel(const uint8_t* __restri
     return true;
   });
   h = gt_hash_end(h);
-  uint32_t id = 0;
-  for (uint32_t s = h & mask, probes = 0; probes <= mask; s = (s + 1) & mask, ++probes) {
-    const uint32_t v = slots[s];
+  for (uint32_t s = h & t.mask, probes = 0; probes <= t.mask; s = (s + 1) & t.mask, ++probes) {
+    const uint32_t v = t.slots[s];
     if (v == 0u) break;
-    const uint4 en = ents[v - 1];
+    const uint4 en = t.ents[v - 1];
     if (en.x != h || en.z != cnt) continue;
     uint32_t at = 0;
     bool same = true;
     for_folded(utf8, b, e, ltab, ci, [&](uint32_t cp) {
-      same = pool[en.y + at] == cp;
+      same = t.pool[en.y + at] == cp;
       ++at;
       return same;
     });
-    if (same) {
-      id = en.w;
-      break;
-    }
+    if (same) return en.w;
   }
-  ids[g - g0] = (uint8_t)id;
+  return 0;
+}
+
+// One thread per grapheme g of [g0, g1): bytes [off[g], off[g + 1]) (the last grapheme ends at len).
+// The table (<= 255 symbols) is copied to LDS when it fits; the loads of off are coalesced and a
+// wave's graphemes are contiguous bytes. ids[g - g0] = the id, 0 = no pattern grapheme.
+__global__ __launch_bounds__(256) void symbol_ids_kernel(const uint8_t* __restrict__ utf8, uint64_t len,
+                                                         const uint64_t* __restrict__ off, uint64_t n, uint64_t g0,
+                                                         uint64_t g1, const uint16_t* __restrict__ ltab, int ci,
+                                                         const uint32_t* __restrict__ g_slots, const uint4* __restrict__ g_ents,
+                                                         const uint32_t* __restrict__ g_pool, uint32_t mask, uint32_t n_keys,
+                                                         uint32_t n_pool, int lds, uint8_t* __restrict__ ids) {
+  const GtView t = gt_view(g_slots, g_ents, g_pool, mask, n_keys, n_pool, lds);
+  const uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= g1 || g >= n) return;
+  const uint64_t b = off[g], e = g + 1 < n ? off[g + 1] : len;
+  if (b >= e || e > len) {  // (never for a staged haystack)
+    ids[g - g0] = 0;
+    return;
+  }
+  ids[g - g0] = (uint8_t)grapheme_symbol_id(utf8, b, e, ltab, ci, t);
+}
+
+// The last k of [lo, hi] with prefix[k] <= p (prefix ascends strictly: the non-empty documents)
+__device__ __forceinline__ uint64_t doc_of(const uint64_t* __restrict__ prefix, uint64_t lo, uint64_t hi, uint64_t p) {
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) / 2;
+    if (prefix[mid] <= p) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The same for every symbol of a batch that holds non-ASCII documents, in the batch's start-window
+// space: symbol p is local symbol i = p - prefix[k] of non-empty document k -- byte text_base + i of
+// an ASCII document, grapheme text_base + i of h.d_off (tagged) of any other. A document's last
+// grapheme ends at the document's end byte: off[g + 1] there belongs to the next non-ASCII document,
+// or lies past the array. One thread per symbol; the tile's first and last document are bisected
+// once per workgroup, a thread bisects only between them (piece_copy_kernel's idiom).
+__global__ __launch_bounds__(256) void batch_symbol_ids_kernel(
+    const uint8_t* __restrict__ utf8, uint64_t len, const uint64_t* __restrict__ off, const SegDesc* __restrict__ segs,
+    const uint64_t* __restrict__ prefix, uint64_t n_segs, uint64_t S, const uint8_t* __restrict__ ascii_id,
+    const uint16_t* __restrict__ ltab, int ci, const uint32_t* __restrict__ g_slots, const uint4* __restrict__ g_ents,
+    const uint32_t* __restrict__ g_pool, uint32_t mask, uint32_t n_keys, uint32_t n_pool, int lds,
+    uint8_t* __restrict__ ids) {
+  __shared__ uint64_t s_doc[2];
+  const uint64_t tile0 = (uint64_t)blockIdx.x * blockDim.x;
+  if (tile0 >= S) return;
+  if (threadIdx.x == 0) {
+    const uint64_t tile_last = (S - tile0 < blockDim.x ? S : tile0 + blockDim.x) - 1;
+    const uint64_t d0 = doc_of(prefix, 0, n_segs - 1, tile0);
+    s_doc[0] = d0;
+    s_doc[1] = doc_of(prefix, d0, n_segs - 1, tile_last);
+  }
+  __syncthreads();
+  const GtView t = gt_view(g_slots, g_ents, g_pool, mask, n_keys, n_pool, lds);
+  const uint64_t p = tile0 + threadIdx.x;
+  if (p >= S) return;
+  const uint64_t k = doc_of(prefix, s_doc[0], s_doc[1], p);
+  const uint64_t i = p - prefix[k];
+  const SegDesc* D = segs + k;
+  const uint64_t base = D->text_base;
+  if (D->ascii) {
+    ids[p] = base + i < len ? ascii_id[utf8[base + i] & 0x7Fu] : (uint8_t)0;
+    return;
+  }
+  constexpr uint64_t kByte = (1ull << kDocTagShift) - 1;
+  const uint64_t g = base + i;
+  const uint64_t b = off[g] & kByte;
+  const uint64_t e = i + 1 < D->n ? off[g + 1] & kByte : (D->byte_base & kByte) + D->hay_len;
+  ids[p] = (b < e && e <= len) ? (uint8_t)grapheme_symbol_id(utf8, b, e, ltab, ci, t) : (uint8_t)0;
+}
+
+// The document-start bitmap of that space: one thread per non-empty document
+__global__ void batch_symbol_starts_kernel(const uint64_t* __restrict__ prefix, uint64_t n_segs, uint32_t* __restrict__ bits) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_segs) return;
+  const uint64_t p = prefix[k];
+  atomicOr(bits + (p >> 5), 1u << (uint32_t)(p & 31));
 }
 
 // One workgroup per merged window w = graphemes [gs, ge) of a staged Unicode haystack: its SegDesc
@@ -915,6 +984,38 @@ int symbol_ids_device(const Engine& e, const Haystack& h, uint64_t g0, uint64_t 
   const uint64_t blocks = (g1 - g0 + 255) / 256;  // (h.n <= u32::MAX graphemes: the grid fits)
   hipLaunchKernelGGL(symbol_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n, g0, g1,
                      tabs.l, e.case_insensitive ? 1 : 0, t.d_slots, t.d_ents, t.d_pool, t.mask, t.n_keys, t.n_pool, lds, d_ids);
+  ST_TRY(hipGetLastError());
+  return FAC_OK;
+}
+
+int batch_symbol_ids_device(const Engine& e, const Batch& b, uint8_t* d_ids, hipStream_t st, std::string& err) {
+  const Haystack& h = b.h;
+  const uint64_t S = b.windows;
+  if (S == 0 || b.n_segs == 0) return FAC_OK;
+  const GraphemeTable& t = e.sym_tab;
+  if (h.ascii || !t.d_slots || !h.d_off || !b.d_segs || !b.d_prefix) {
+    err = "internal: batch_symbol_ids_device needs a staged batch with non-ASCII documents and an engine with a pre-filter";
+    return FAC_E_INTERNAL;
+  }
+  const uint64_t blocks = (S + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) {
+    err = "a pre-filtered batch with non-ASCII documents holds fewer than 2^39 symbols";
+    return FAC_E_UNSUPPORTED;
+  }
+  BmpTabs tabs;
+  if (int trc = bmp_tables(h.device, st, tabs, err)) return trc;
+  const int lds = (t.mask < kGtSlotsLds && t.n_keys <= kGtKeysLds && t.n_pool <= kGtPoolLds) ? 1 : 0;
+  hipLaunchKernelGGL(batch_symbol_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, b.d_segs,
+                     b.d_prefix, b.n_segs, S, e.d_ascii_id, tabs.l, e.case_insensitive ? 1 : 0, t.d_slots, t.d_ents, t.d_pool,
+                     t.mask, t.n_keys, t.n_pool, lds, d_ids);
+  ST_TRY(hipGetLastError());
+  return FAC_OK;
+}
+
+int batch_symbol_starts_device(const Batch& b, uint32_t* d_bits, hipStream_t st, std::string& err) {
+  if (b.n_segs == 0) return FAC_OK;
+  hipLaunchKernelGGL(batch_symbol_starts_kernel, dim3((uint32_t)((b.n_segs + 255) / 256)), dim3(256), 0, st, b.d_prefix,
+                     b.n_segs, d_bits);
   ST_TRY(hipGetLastError());
   return FAC_OK;
 }
@@ -1134,6 +1235,10 @@ void free_batch(Batch& b) {
   b.d_dstart = nullptr;
   b.dstart_cap = 0;
   b.dstart_ready = false;
+  if (b.d_sstart) (void)hipFree(b.d_sstart);
+  b.d_sstart = nullptr;
+  b.sstart_cap = 0;
+  b.sstart_ready = false;
   if (b.own_offsets && b.d_offsets) (void)hipFree(b.d_offsets);
   b.d_offsets = nullptr;
   if (b.d_meta) (void)hipFree(b.d_meta);
@@ -1151,7 +1256,8 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   b.n_segs = 0;
   b.windows = 0;
   b.err_doc = b.err_graphemes = 0;
-  b.dstart_ready = false;  // the pre-filter's document-start bitmap is rebuilt for the new offsets
+  b.dstart_ready = false;  // the pre-filter's document-start bitmaps are rebuilt for the new offsets
+  b.sstart_ready = false;
   h.ascii = true;
   h.n = 0;
   {

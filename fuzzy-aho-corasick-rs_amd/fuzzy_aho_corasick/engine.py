@@ -476,13 +476,17 @@ class Prefiltered:
         return self.replace_stream(reader, writer, threshold, callback)
 
     def _batch_parts(self, enc):
-        """Indices of the documents one pre-filtered batch takes: the ASCII ones (the device filter
-        is for all-ASCII batches; the others go through `search` one by one)."""
+        """Indices of the documents one pre-filtered batch takes: all of them where the filter is
+        active and the engine has no mappings (the batch is opted in, allow_unicode_prefilter), else
+        the ASCII ones (the others go through `search` one by one)."""
+        if self.is_active() and not self.engine.builder._mappings:
+            return list(range(len(enc)))
         return [d for d, raw in enumerate(enc) if raw.isascii()]
 
     def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None) -> List[FuzzyMatches]:
-        """`[self.search(h, opts) for h in haystacks]`: the ASCII haystacks as one pre-filtered batch
-        (fac_search_batch_prefiltered), the others one by one, results in input order."""
+        """`[self.search(h, opts) for h in haystacks]`: the haystacks as one pre-filtered batch
+        (fac_search_batch_prefiltered; `_batch_parts`: all of them, or the ASCII ones and the others
+        one by one), results in input order."""
         opts = opts or SearchOptions()
         haystacks = list(haystacks)
         enc = [h.encode("utf-8") for h in haystacks]
@@ -490,7 +494,8 @@ class Prefiltered:
         idx = self._batch_parts(enc)
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
-            recs, doc_off = StagedBatch(self.engine, data, offsets).search_records(opts, prefilter=True)
+            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True)
+            recs, doc_off = sb.search_records(opts, prefilter=True)
             for k, d in enumerate(idx):
                 rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
                          int(r["insertions"]), int(r["deletions"]), int(r["substitutions"]), int(r["swaps"]),
@@ -517,7 +522,8 @@ class Prefiltered:
             table = ReplacementTable(self.engine, reps) if idx else None
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
-            buf, off = StagedBatch(self.engine, data, offsets).replace_bytes(table, opts, prefilter=True)
+            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True)
+            buf, off = sb.replace_bytes(table, opts, prefilter=True)
             for k, d in enumerate(idx):
                 out[d] = buf[int(off[k]):int(off[k + 1])].decode("utf-8")
         order = Order.Default if opts.order_ == Order.Unsorted else opts.order_
@@ -616,7 +622,8 @@ def _item_text(reps, m) -> str:
 
 def _extract_batch(engine: "FuzzyAhoCorasick", enc, opts: SearchOptions, table, prefilter: bool) -> List[List[str]]:
     data, offsets = batch_offsets(enc)
-    _, doc_off, text, item_off = StagedBatch(engine, data, offsets).extract(table, opts, prefilter=prefilter)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter)
+    _, doc_off, text, item_off = sb.extract(table, opts, prefilter=prefilter)
     return [[text[int(item_off[i]):int(item_off[i + 1])].decode("utf-8")
              for i in range(int(doc_off[d]), int(doc_off[d + 1]))] for d in range(len(enc))]
 
@@ -624,14 +631,16 @@ def _extract_batch(engine: "FuzzyAhoCorasick", enc, opts: SearchOptions, table, 
 def _render_batch(engine: "FuzzyAhoCorasick", texts, mode: int, opts: SearchOptions, prefilter: bool) -> List[str]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
-    out, off = StagedBatch(engine, data, offsets).render_bytes(mode, opts, prefilter=prefilter)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter)
+    out, off = sb.render_bytes(mode, opts, prefilter=prefilter)
     return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
 
 def _segment_batch(engine: "FuzzyAhoCorasick", texts, opts: SearchOptions, prefilter: bool) -> List[List[Segment]]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
-    recs, doc_off = StagedBatch(engine, data, offsets).segment_records(opts, prefilter=prefilter)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter)
+    recs, doc_off = sb.segment_records(opts, prefilter=prefilter)
     out = []
     for d, raw in enumerate(enc):
         segs = []
@@ -1118,7 +1127,7 @@ class StagedBatch:
     times: document d is data[offsets[d]:offsets[d + 1]], staged as if it were staged alone (UTF-8
     validity, is_ascii and grapheme segmentation per document)."""
 
-    def __init__(self, engine: FuzzyAhoCorasick, data: bytes, offsets):
+    def __init__(self, engine: FuzzyAhoCorasick, data: bytes, offsets, unicode_prefilter: bool = False):
         import numpy as np
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
         if off.ndim != 1 or len(off) < 1:
@@ -1136,13 +1145,16 @@ class StagedBatch:
             _raise_batch(rc, None if ed.value == 0xFFFFFFFFFFFFFFFF else ed.value, eg.value)
         self._h = h
         self._dev_out = self._dev_doc = None
+        if unicode_prefilter:
+            self.allow_unicode_prefilter()
 
     @classmethod
     def from_device(cls, engine: FuzzyAhoCorasick, d_utf8: int, d_offsets: int, n_docs: int, total_len: int,
-                    stream=None, reuse: "StagedBatch" = None) -> "StagedBatch":
+                    stream=None, reuse: "StagedBatch" = None, unicode_prefilter: bool = False) -> "StagedBatch":
         """fac_batch_stage_device: the bytes (`d_utf8`, total_len of them) and the n_docs + 1 uint64
         offsets (`d_offsets`) are device addresses, e.g. torch tensors' data_ptr() (borrowed: keep both
-        alive). `reuse`: a batch staged this way before, restaged in place and returned."""
+        alive). `reuse`: a batch staged this way before, restaged in place and returned (it keeps its
+        opt-in). `unicode_prefilter`: opt the batch in (allow_unicode_prefilter)."""
         h = ctypes.c_void_p(reuse._h.value if reuse is not None else None)
         ed = ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
         eg = ctypes.c_uint64()
@@ -1159,6 +1171,8 @@ class StagedBatch:
             obj.engine, obj.data, obj._h = engine, None, h
             obj._dev_out = obj._dev_doc = None
         obj.n_docs = n_docs
+        if unicode_prefilter:
+            obj.allow_unicode_prefilter()
         return obj
 
     def __del__(self):
@@ -1166,6 +1180,15 @@ class StagedBatch:
         if h and _native.lib is not None:
             _native.lib.fac_batch_free(h)
             self._h = None
+
+    def allow_unicode_prefilter(self, on: bool = True) -> "StagedBatch":
+        """fac_batch_allow_unicode_prefilter: the `prefilter=True` calls take this batch even if it
+        holds non-ASCII documents (default off: they raise UnsupportedConfiguration for such a batch).
+        An all-ASCII batch is handled the same either way. Returns self."""
+        rc = _native.lib.fac_batch_allow_unicode_prefilter(self._h, 1 if on else 0)
+        if rc:
+            _raise(rc)
+        return self
 
     def doc_graphemes(self, d: int) -> Tuple[int, bool]:
         """(grapheme count, is_ascii) of document d."""
@@ -1207,7 +1230,8 @@ class StagedBatch:
     def search_records(self, opts: SearchOptions = None, out=None, stream=None, stats=None, doc_offsets_out=None,
                        prefilter: bool = False):
         """fac_search_batch (`prefilter`: fac_search_batch_prefiltered, every document searched as
-        engine.with_prefilter().search would; all-ASCII batches only where the filter runs):
+        engine.with_prefilter().search would; where the filter runs the batch must be all ASCII or
+        opted in, allow_unicode_prefilter):
         (records, doc_offsets). Records (MATCH_DTYPE) are grouped by document,
         offsets relative to the record's own document, each document in FuzzyMatches::apply's order;
         doc_offsets (n_docs + 1) indexes them. `out`: a uint8 CUDA tensor to leave the records in HBM
@@ -1317,8 +1341,9 @@ class StagedBatch:
 
     def prefilter_windows(self, threshold: float, stream=None):
         """Diagnostics (fac_batch_prefilter_windows): the merged bitap windows of every document as
-        (document, start, end) triples, document-relative, ascending; None where the reference falls
-        back to the full search."""
+        (document, start, end) triples, document-relative, ascending -- bytes for an ASCII document,
+        graphemes for any other (an opted-in batch); None where the reference falls back to the full
+        search."""
         cap = 1024
         while True:
             buf = (ctypes.c_uint64 * (3 * cap))()

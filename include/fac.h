@@ -374,18 +374,22 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  * segment descriptors back and run the per-segment auto-beam loop of fac_search_staged on the host.
  * Batched replace is provided (fac_replace_batch below), and so are the other segmentation helpers:
  * segment_iter and split (fac_segment_batch), strip_prefix, strip_suffix and segment_text
- * (fac_render_batch). Every one of these calls has a pre-filtered form for all-ASCII batches
- * (fac_search_batch_prefiltered, fac_replace_batch_prefiltered, fac_segment_batch_prefiltered,
+ * (fac_render_batch). Every one of these calls has a pre-filtered form for batches that are all
+ * ASCII or opted in (fac_search_batch_prefiltered, fac_replace_batch_prefiltered, fac_segment_batch_prefiltered,
  * fac_render_batch_prefiltered below). The matched strings of a batch, or each match's replacement,
  * come from fac_extract_batch and fac_extract_batch_prefiltered. Multi-GPU batches are not provided.
  *
- * Limits of the pre-filtered forms: where the filter runs, the batch must be all ASCII -- one
- * non-ASCII document gives FAC_E_UNSUPPORTED with nothing written (a non-ASCII document's symbol
- * symbol ids come from the device lookup of fac_haystack_symbol_ids, which the batch's one scan, cut
- * at document starts in byte coordinates, is not wired to; the same limit
- * fac_stream_windows_staged_device has) -- and it holds at most 2^32 - 1 merged windows. Staging
- * errors stay fac_batch_stage's: a document over the grapheme limit fails there, which is stricter
- * than the crate, whose Prefiltered::search only checks each merged window it searches. */
+ * Limits of the pre-filtered forms: where the filter runs, the batch must be all ASCII or opted in
+ * with fac_batch_allow_unicode_prefilter. Without the opt-in one non-ASCII document gives
+ * FAC_E_UNSUPPORTED with nothing written (callers may rely on that to route such batches elsewhere;
+ * fac_stream_windows_staged_device keeps the same limit). An opted-in batch is scanned once in symbol
+ * coordinates -- a symbol is a byte of an ASCII document and a folded grapheme of any other, "\r\n"
+ * being one -- cut at document starts; each merged window of a non-ASCII document becomes the byte
+ * slice of its graphemes and is searched as a haystack of its own, byte-wise when the slice is all
+ * ASCII (prefilter.rs:346-350, search.rs:196). An all-ASCII batch takes the same path whether opted
+ * in or not. A batch holds at most 2^32 - 1 merged windows. Staging errors stay fac_batch_stage's:
+ * a document over the grapheme limit fails there, which is stricter than the crate, whose
+ * Prefiltered::search only checks each merged window it searches. */
 typedef struct fac_batch fac_batch;
 
 /* Documents d = 0..n_docs-1 are bytes [offsets[d], offsets[d+1]) of utf8.
@@ -408,6 +412,12 @@ int fac_batch_stage_device(const fac_engine* engine, const uint8_t* d_utf8, cons
 
 void fac_batch_free(fac_batch* batch);
 uint64_t fac_batch_docs(const fac_batch* batch);
+
+/* Opt-in (on != 0) or back out (0, the default): the pre-filtered calls below take this batch even
+ * if it holds non-ASCII documents (see "Limits of the pre-filtered forms" above). Sets a flag and
+ * does no work; the flag survives a restage in place (fac_batch_stage_device with *batch set). Not
+ * to be called concurrently with a search of the same batch. FAC_E_INVALID for NULL. */
+int fac_batch_allow_unicode_prefilter(fac_batch* batch, int32_t on);
 
 /* Tests and hosts: document d's grapheme count, is_ascii, and document-relative grapheme byte
  * starts (writes up to `cap` entries, returns the count). */
@@ -452,14 +462,15 @@ int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac
  * Where the reference falls back to the full search -- no filter (fac_prefilter_active == 0, which
  * covers engines with mappings), or k_for above 24 for some pattern at this threshold -- the call is
  * fac_search_batch exactly, for any batch. Otherwise arguments, contract, errors and limits are
- * fac_search_batch's plus the all-ASCII limit above. stats: prefilter_ms = device time of the scan,
+ * fac_search_batch's plus the "all ASCII, or opted in" limit above. stats: prefilter_ms = device time of the scan,
  * verify and runs; windows = the start windows searched, the merged windows' lengths summed. */
 int fac_search_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args,
                                  fac_match** out, uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats);
 
 /* Tests and diagnostics: the merged windows fac_search_batch_prefiltered searches, as
- * (document, start, end) triples with document-relative offsets, ascending by document, then by
- * start. Writes up to `cap` triples to `out` and returns their count, -1 where the reference falls
+ * (document, start, end) triples with document-relative symbol offsets -- bytes for an ASCII
+ * document, graphemes for any other (an opted-in batch), the coordinates of Prefiltered's merged
+ * windows, ends clamped to the document -- ascending by document, then by start. Writes up to `cap` triples to `out` and returns their count, -1 where the reference falls
  * back to the full search, or minus the error code (every FAC_E_* that can occur here is >= 100). */
 int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* batch, float threshold, void* stream,
                                     uint64_t* out, uint64_t cap);

@@ -33,6 +33,13 @@ c5's engine on fresh filler words with no planted match):
 
   The legs alternate; "records_equal" compares (p)'s records of the sample with (b)'s.
 
+With --prefilter-unicode the same legs run on batches that hold non-ASCII documents, opted in with
+fac_batch_allow_unicode_prefilter (DESIGN.md §6a "Pre-filtered batches of non-ASCII documents"):
+"u3" = c5's shape over the C3 script mix (1 000 patterns of 10-16 characters, edits 1, threshold
+0.85, case-insensitive, one planted hit per MiB), "u3a" = the same text with every fourth document
+replaced by ASCII filler of its length. (a), the plain batch, is the only one-call path such a batch
+had before; (b) is what the Python conveniences did.
+
 With --segment the legs are (DESIGN.md §6a "Batched segmentation"):
 
   (s)  one fac_render_batch call per mode (strip_prefix, strip_suffix, segment_text) and one
@@ -467,8 +474,35 @@ def run_template_extract(name, nbytes, L, rounds, leg, profile_only):
             "dtod_copy_ms": dtod_copy_ms(stream, sh, bufs["out"], out_bytes, rounds)}
 
 
+def unicode_workload(nbytes):
+    """c5's shape over the C3 scripts (profiles/bench_prefilter_stream.py's text)."""
+    if ("u3", nbytes) not in _CACHE:
+        from fuzzy_aho_corasick import FuzzyAhoCorasickBuilder, FuzzyLimits
+        pats = workloads._words(workloads.XorShift(5).numpy(), workloads.SCRIPTS_C3, 1000, 10, 16, True)
+        hay = workloads._haystack(workloads.XorShift(1005).numpy(), workloads.SCRIPTS_C3, pats, nbytes, 1, 1 << 20)
+        w = workloads.Workload("u3", pats, hay, 1, 0, True, 0.85, True)
+        engine = FuzzyAhoCorasickBuilder().fuzzy(FuzzyLimits().edits(1)).case_insensitive(True).build(pats)
+        assert engine.with_prefilter().is_active() and not hay.isascii()
+        _CACHE[("u3", nbytes)] = (w, engine)
+    return _CACHE[("u3", nbytes)]
+
+
+def ascii_quarter(data: bytes, off: np.ndarray) -> bytes:
+    """`data` with every fourth document replaced by fresh ASCII filler words of its byte length."""
+    rng = workloads.XorShift(0xA5C1).numpy()
+    filler = np.frombuffer(workloads._fresh_filler(rng, [workloads.ASCII_LOWER], len(data), 2, 12)[:len(data)], np.uint8)
+    lens = np.diff(off.astype(np.int64))
+    take = np.repeat(np.arange(len(lens)) % 4 == 0, lens)
+    out = np.frombuffer(data, np.uint8).copy()
+    out[take] = filler[take]
+    return out.tobytes()
+
+
 def prefilter_workload(name, nbytes):
-    """c2 / c5 as workloads.config; c5n: c5's patterns and threshold over fresh filler words alone."""
+    """c2 / c5 as workloads.config; c5n: c5's patterns and threshold over fresh filler words alone;
+    u3 / u3a: unicode_workload (u3a's documents are replaced once they are cut, run_prefilter)."""
+    if name in ("u3", "u3a"):
+        return unicode_workload(nbytes)
     if name != "c5n":
         return workload(name, nbytes)
     if (name, nbytes) not in _CACHE:
@@ -483,7 +517,9 @@ def prefilter_workload(name, nbytes):
 def run_prefilter(name, nbytes, L, sample, rounds, rules, profile_only):
     w, engine = prefilter_workload(name, nbytes)
     data = w.haystack
-    off = cut_documents(data, L)
+    off = cut_documents(data, L)  # (after a space: a grapheme boundary, the texts hold no combining marks)
+    if name == "u3a":
+        data = ascii_quarter(data, off)
     nd = len(off) - 1
     dev = torch.device("cuda", engine.device)
     t_data = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(dev)
@@ -492,7 +528,8 @@ def run_prefilter(name, nbytes, L, sample, rounds, rules, profile_only):
     sh = stream.cuda_stream
     opts = SearchOptions().threshold(w.threshold)
     bufs = {"out": torch.empty(max(1 << 16, len(data) // 16) * 32, dtype=torch.uint8, device=dev)}
-    sb = StagedBatch.from_device(engine, t_data.data_ptr(), t_off.data_ptr(), nd, len(data), stream=sh)
+    sb = StagedBatch.from_device(engine, t_data.data_ptr(), t_off.data_ptr(), nd, len(data), stream=sh,
+                                 unicode_prefilter=name in ("u3", "u3a"))
     stats = _native.fac_stats()
 
     def batch_search(prefilter):
@@ -569,7 +606,8 @@ def run_prefilter(name, nbytes, L, sample, rounds, rules, profile_only):
             "p_spread_ms": round(max(p_ms[best_rule]) - min(p_ms[best_rule]), 3),
             "a_spread_ms": round(max(a_ms) - min(a_ms), 3), "c_spread_ms": round(max(c_ms) - min(c_ms), 3),
             "records_equal": bool(same),
-            "faster_than_a": bool(same and min(a_ms) - max(p_ms[best_rule]) > 0)}
+            "faster_than_a": bool(same and min(a_ms) - max(p_ms[best_rule]) > 0),
+            "faster_than_b": bool(same and min(b_doc) - max(p_ms[best_rule]) / nd > 0)}
 
 
 def main():
@@ -589,6 +627,8 @@ def main():
     ap.add_argument("--prefilter", action="store_true",
                     help="time fac_search_batch_prefiltered against the plain batch, the one-haystack pre-filtered "
                          "search and the per-document Prefiltered loop (configs c2, c5, c5n; --pf-bytes each)")
+    ap.add_argument("--prefilter-unicode", action="store_true",
+                    help="the --prefilter legs on opted-in batches of the C3 script mix (configs u3, u3a)")
     ap.add_argument("--pf-bytes", type=int, default=64 << 20)
     ap.add_argument("--segment", action="store_true",
                     help="time fac_render_batch (each mode) and fac_segment_batch against fac_search_batch, the "
@@ -598,8 +638,9 @@ def main():
     ap.add_argument("--extract", action="store_true",
                     help="time fac_extract_batch (NULL table) against fac_search_batch with the same options")
     args = ap.parse_args()
-    if args.prefilter:
-        for name in (args.configs if args.configs != ["c2", "c3"] else ["c2", "c5", "c5n"]):
+    if args.prefilter or args.prefilter_unicode:
+        default = ["u3", "u3a"] if args.prefilter_unicode else ["c2", "c5", "c5n"]
+        for name in (args.configs if args.configs != ["c2", "c3"] else default):
             for L in args.lengths:
                 res = run_prefilter(name, args.pf_bytes, L, args.sample, args.rounds, args.rules, args.profile_only)
                 if res is not None:
