@@ -21,6 +21,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "fac_internal.h"
+#include "host_util.h"
 
 namespace fac {
 namespace {
@@ -130,24 +131,13 @@ __global__ __launch_bounds__(kThreads) void extract_copy_kernel(
   chunk_store(c, out + g, wide);
 }
 
-#define EX_TRY(x)                                              \
-  do {                                                         \
-    hipError_t e_ = (x);                                       \
-    if (e_ != hipSuccess) {                                    \
-      err = std::string(#x ": ") + hipGetErrorString(e_);      \
-      return FAC_E_HIP;                                        \
-    }                                                          \
-  } while (0)
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 int extract_plan_device(const Batch& b, const ReplaceTable* t, const fac_match* d_recs, uint64_t n_recs,
                         const uint64_t* d_doc_off, hipStream_t s, ExtractPlan& plan, std::string& err) {
   const uint64_t ni = n_recs;
   size_t scan_bytes = 0;
-  EX_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, ni + 1,
+  HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, ni + 1,
                                  rocprim::plus<uint64_t>(), s));
   // one block of call scratch: lengths, offsets, source words, the scan's own
   const size_t o_len = 0, o_off = o_len + up256((ni + 1) * 8), o_src = o_off + up256((ni + 1) * 8);
@@ -168,12 +158,12 @@ int extract_plan_device(const Batch& b, const ReplaceTable* t, const fac_match* 
   hipLaunchKernelGGL(extract_len_kernel, dim3((uint32_t)((ni + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
                      d_recs, ni, d_doc_off, b.d_offsets, b.n_docs, t ? t->d_tab : nullptr, t ? t->d_ins : nullptr, d_len,
                      plan.d_src);
-  EX_TRY(hipGetLastError());
-  EX_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_len, plan.d_item_off, (uint64_t)0, ni + 1,
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_len, plan.d_item_off, (uint64_t)0, ni + 1,
                                  rocprim::plus<uint64_t>(), s));
   unsigned long long total = 0;
-  EX_TRY(hipMemcpyAsync(&total, plan.d_item_off + ni, 8, hipMemcpyDeviceToHost, s));
-  EX_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(&total, plan.d_item_off + ni, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   plan.total = total;
   return FAC_OK;
 }
@@ -186,7 +176,7 @@ int extract_copy_device(const Batch& b, const ReplaceTable* t, const fac_match* 
   hipLaunchKernelGGL(extract_copy_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, plan.s, b.h.d_utf8, d_recs,
                      plan.n_items, plan.d_item_off, plan.d_src, t ? t->d_tab : nullptr, t ? t->d_ins : nullptr,
                      t ? t->d_bytes : nullptr, d_out, plan.total, wide);
-  EX_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 

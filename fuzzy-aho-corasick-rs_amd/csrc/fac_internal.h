@@ -308,7 +308,7 @@ struct SearchParams {
 constexpr unsigned ERR_QUEUE = 1u, ERR_VISITED = 2u, ERR_EMIT = 4u, ERR_HALO = 8u, ERR_OUT = 16u, ERR_SPILL = 32u;
 
 // ---------------------------------------------------------------- engine
-// The pre-filter's device tables for one set of edit budgets (search_kernels.hip prefilter_windows):
+// The pre-filter's device tables for one set of edit budgets (prefilter_kernels.hip prefilter_windows):
 // the packed full-scan words and the q-gram path's gram table, screening bitmap and pattern masks.
 // Built on a call's first use and kept by the engine (they depend on the engine and ks alone).
 struct PfTables {
@@ -501,7 +501,7 @@ struct Batch {
   uint64_t n_segs = 0;   // non-empty documents
   uint64_t windows = 0;  // start windows of all documents
   uint64_t err_doc = 0, err_graphemes = 0;  // of a failed staging
-  // the pre-filter's document-start bitmap (search_kernels.hip batch_prefilter_windows): one
+  // the pre-filter's document-start bitmap (prefilter_kernels.hip batch_prefilter_windows): one
   // bit per byte of h.d_utf8, set at the first byte of every non-empty document; built by the first
   // pre-filtered search after a staging and kept until the batch is staged again
   mutable std::mutex dstart_mu;
@@ -796,6 +796,8 @@ int auto_beam_total(const Engine& e, const Haystack& h, const std::vector<SegDes
 const char* diag_env(const char* name);
 // the host copies of a staged haystack (Haystack::utf8, ::starts), fetched once from the device
 int ensure_host(const Haystack& h, std::string& err);
+// the grapheme ids of a Unicode haystack for an engine with mappings, computed and uploaded on first use
+int ensure_gids(const Engine& e, const Haystack& h, std::string& err);
 // largest grapheme count a haystack may have (u32::MAX, search.rs:198-201; lowered only by the
 // diagnostics knob FAC_GRAPHEME_LIMIT so tests can reach SearchError::HaystackTooLarge)
 uint64_t grapheme_limit();
@@ -811,6 +813,7 @@ struct ScratchSet {
 };
 void scratch_bind(ScratchSet* s);  // this thread's searches use `s` (nullptr: the engine's)
 void scratch_free(ScratchSet& s);
+int aux_priority();  // the stream priority of a set's (and the engine's) aux stream
 // Short-lived call scratch (rank kernels, stream-window record buffers), one process-wide pool: a
 // block given back on stream s is handed out again only for work on s (same device), whose order
 // makes the reuse safe without the device-wide synchronisation a hipFree implies (a per-call
@@ -884,7 +887,7 @@ void grapheme_table_free(GraphemeTable& t);
 // Unicode haystack, written to d_ids[0, g1 - g0) on st (asynchronous): symbol_ids_kernel
 int symbol_ids_device(const Engine& e, const Haystack& h, uint64_t g0, uint64_t g1, uint8_t* d_ids, hipStream_t st,
                       std::string& err);
-// search_kernels.hip: the same for ASCII text (prefilter.rs:253-258): d_ids[i] = ascii_id[d_utf8[i]], i < n
+// prefilter_kernels.hip: the same for ASCII text (prefilter.rs:253-258): d_ids[i] = ascii_id[d_utf8[i]], i < n
 int transcode_ascii_device(const Engine& e, const uint8_t* d_utf8, uint64_t n, uint8_t* d_ids, hipStream_t st,
                            std::string& err);
 // The descriptors of graphemes [gs, ge) x n of a staged Unicode haystack, each searched as a text of
@@ -917,7 +920,7 @@ void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
                          bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
                          std::vector<uint64_t>* win_off = nullptr, uint64_t* searched = nullptr);
-// merged bitap windows (prefilter.rs:319-342) of a text view of a staged haystack (view.ascii:
+// prefilter_kernels.hip: merged bitap windows (prefilter.rs:319-342) of a text view of a staged haystack (view.ascii:
 // bytes [text_base, text_base + n) of h.d_utf8; else graphemes [text_base, text_base + n)); windows
 // in the view's local grapheme coordinates
 // diagnostics: beam_select(_lds) alone on key arrays (tests; fac_diag_beam_select)
@@ -939,7 +942,7 @@ int prefilter_windows_ex(const Engine& e, const Haystack& h, const SegDesc& view
 // the segments handed to the search launcher
 int prefiltered_view(const Engine& e, const Haystack& h, const SegDesc& view, float threshold, hipStream_t stream,
                      std::vector<fac_match>& merged, fac_stats* stats, std::string& err, uint64_t* searched = nullptr);
-// force_ascii: -1 decide from the bytes (search.rs:196), 0 Unicode graphemes, 1 ASCII bytes (a
+// device_state.cpp. force_ascii: -1 decide from the bytes (search.rs:196), 0 Unicode graphemes, 1 ASCII bytes (a
 // shard of a haystack whose global is_ascii is already known)
 int stage_haystack(const Engine& e, const uint8_t* utf8, uint64_t len, Haystack& h, std::string& err,
                    int force_ascii = -1, hipStream_t stream = nullptr);

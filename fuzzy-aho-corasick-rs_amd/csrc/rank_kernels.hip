@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "fac_internal.h"
+#include "host_util.h"
 
 namespace fac {
 namespace {
@@ -196,15 +197,6 @@ __global__ void gather_kernel(const fac_match* m, const Span* order, uint64_t n,
   if (i < n) out[i] = m[order[i].rank];
 }
 
-#define RK_TRY(x)                                                   \
-  do {                                                              \
-    hipError_t _e = (x);                                            \
-    if (_e != hipSuccess) {                                         \
-      err = std::string(#x ": ") + hipGetErrorString(_e);           \
-      return FAC_E_HIP;                                             \
-    }                                                               \
-  } while (0)
-
 // stream-ordered call scratch (call_scratch_take): every use below is on the stream it was taken for
 thread_local hipStream_t t_buf_stream = nullptr;
 struct Buf {
@@ -277,16 +269,16 @@ int apply_matches_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64
   const uint32_t G = (uint32_t)((n + T - 1) / T);
   fac_match* ranked = d_a;
   if (order != 0) {
-    RK_TRY(dev_sort(d_a, d_b, n, RankCmp{e.d_pat_bytes, order}, s));
+    HIP_TRY(dev_sort(d_a, d_b, n, RankCmp{e.d_pat_bytes, order}, s));
     ranked = d_b;
   }
   auto host_walk = [&](bool unique) -> int {
     std::vector<fac_match> v(n);
-    RK_TRY(hipMemcpyAsync(v.data(), ranked, n * sizeof(fac_match), hipMemcpyDeviceToHost, s));
-    RK_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(v.data(), ranked, n * sizeof(fac_match), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     walk_host(v, unique_ids, unique);
-    if (!v.empty()) RK_TRY(hipMemcpyAsync(d_a, v.data(), v.size() * sizeof(fac_match), hipMemcpyHostToDevice, s));
-    RK_TRY(hipStreamSynchronize(s));
+    if (!v.empty()) HIP_TRY(hipMemcpyAsync(d_a, v.data(), v.size() * sizeof(fac_match), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
     *res = d_a;
     *n_res = v.size();
     return FAC_OK;
@@ -298,81 +290,81 @@ int apply_matches_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64
   if (overlap == 2) return host_walk(true);  // the unique walk on the host
   // ---- non_overlapping: clusters in start order, resolved one thread per cluster
   Buf d_sp, d_sp2, d_ends, d_maxe, d_flag, d_cid, d_head, d_lo, d_hi, d_keep, d_pos, d_kept;
-  RK_TRY(d_sp.alloc(n * sizeof(Span)));
-  RK_TRY(d_sp2.alloc(n * sizeof(Span)));
+  HIP_TRY(d_sp.alloc(n * sizeof(Span)));
+  HIP_TRY(d_sp2.alloc(n * sizeof(Span)));
   hipLaunchKernelGGL(spans_kernel, dim3(G), dim3(T), 0, s, ranked, n, d_sp.as<Span>());
-  RK_TRY(dev_sort(d_sp.as<Span>(), d_sp2.as<Span>(), n, SpanByStart{}, s));
-  RK_TRY(d_ends.alloc(n * 8));
-  RK_TRY(d_maxe.alloc(n * 8));
+  HIP_TRY(dev_sort(d_sp.as<Span>(), d_sp2.as<Span>(), n, SpanByStart{}, s));
+  HIP_TRY(d_ends.alloc(n * 8));
+  HIP_TRY(d_maxe.alloc(n * 8));
   hipLaunchKernelGGL(ends_kernel, dim3(G), dim3(T), 0, s, d_sp2.as<Span>(), n, d_ends.as<uint64_t>());
   {
     size_t bytes = 0;
-    RK_TRY(rocprim::inclusive_scan(nullptr, bytes, d_ends.as<uint64_t>(), d_maxe.as<uint64_t>(), n,
+    HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, d_ends.as<uint64_t>(), d_maxe.as<uint64_t>(), n,
                                    rocprim::maximum<uint64_t>(), s));
     Buf tmp;
-    RK_TRY(tmp.alloc(bytes));
-    RK_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_ends.as<uint64_t>(), d_maxe.as<uint64_t>(), n,
+    HIP_TRY(tmp.alloc(bytes));
+    HIP_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_ends.as<uint64_t>(), d_maxe.as<uint64_t>(), n,
                                    rocprim::maximum<uint64_t>(), s));
   }
-  RK_TRY(d_flag.alloc(n * 4));
-  RK_TRY(d_cid.alloc(n * 4));
+  HIP_TRY(d_flag.alloc(n * 4));
+  HIP_TRY(d_cid.alloc(n * 4));
   hipLaunchKernelGGL(cluster_flags_kernel, dim3(G), dim3(T), 0, s, d_sp2.as<Span>(), d_maxe.as<uint64_t>(), n,
                      d_flag.as<uint32_t>());
   {
     size_t bytes = 0;
-    RK_TRY(rocprim::inclusive_scan(nullptr, bytes, d_flag.as<uint32_t>(), d_cid.as<uint32_t>(), n,
+    HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, d_flag.as<uint32_t>(), d_cid.as<uint32_t>(), n,
                                    rocprim::plus<uint32_t>(), s));
     Buf tmp;
-    RK_TRY(tmp.alloc(bytes));
-    RK_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_flag.as<uint32_t>(), d_cid.as<uint32_t>(), n,
+    HIP_TRY(tmp.alloc(bytes));
+    HIP_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_flag.as<uint32_t>(), d_cid.as<uint32_t>(), n,
                                    rocprim::plus<uint32_t>(), s));
   }
   hipLaunchKernelGGL(assign_cluster_kernel, dim3(G), dim3(T), 0, s, d_sp2.as<Span>(), d_cid.as<uint32_t>(), n);
-  RK_TRY(dev_sort(d_sp2.as<Span>(), d_sp.as<Span>(), n, SpanByClusterRank{}, s));
+  HIP_TRY(dev_sort(d_sp2.as<Span>(), d_sp.as<Span>(), n, SpanByClusterRank{}, s));
   uint32_t last_cid = 0;
-  RK_TRY(hipMemcpyAsync(&last_cid, d_cid.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
-  RK_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(&last_cid, d_cid.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   const uint64_t n_clusters = (uint64_t)last_cid + 1;
-  RK_TRY(d_head.alloc(n_clusters * 8));
+  HIP_TRY(d_head.alloc(n_clusters * 8));
   hipLaunchKernelGGL(cluster_heads_kernel, dim3(G), dim3(T), 0, s, d_sp.as<Span>(), n, d_head.as<uint64_t>());
   {  // largest cluster: a thread's walk is quadratic in its cluster, keep it bounded
     std::vector<uint64_t> heads(n_clusters);
-    RK_TRY(hipMemcpyAsync(heads.data(), d_head.p, n_clusters * 8, hipMemcpyDeviceToHost, s));
-    RK_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(heads.data(), d_head.p, n_clusters * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     uint64_t biggest = 0;
     for (uint64_t c = 0; c < n_clusters; ++c) biggest = std::max(biggest, (c + 1 < n_clusters ? heads[c + 1] : n) - heads[c]);
     if (biggest > kMaxCluster) return host_walk(false);
   }
-  RK_TRY(d_lo.alloc(n * sizeof(uint2)));
-  RK_TRY(d_hi.alloc(n * sizeof(uint2)));
-  RK_TRY(d_keep.alloc(n));
-  RK_TRY(hipMemsetAsync(d_keep.p, 0, n, s));
+  HIP_TRY(d_lo.alloc(n * sizeof(uint2)));
+  HIP_TRY(d_hi.alloc(n * sizeof(uint2)));
+  HIP_TRY(d_keep.alloc(n));
+  HIP_TRY(hipMemsetAsync(d_keep.p, 0, n, s));
   hipLaunchKernelGGL(resolve_kernel, dim3((uint32_t)((n_clusters + T - 1) / T)), dim3(T), 0, s, d_sp.as<Span>(),
                      d_head.as<uint64_t>(), n_clusters, n, d_lo.as<uint2>(), d_hi.as<uint2>(), d_keep.as<uint8_t>());
   // compact the kept matches (rank order), then order them by start
-  RK_TRY(d_pos.alloc(n * 4));
+  HIP_TRY(d_pos.alloc(n * 4));
   {
     size_t bytes = 0;
-    RK_TRY(rocprim::inclusive_scan(nullptr, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
+    HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
                                    rocprim::plus<uint32_t>(), s));
     Buf tmp;
-    RK_TRY(tmp.alloc(bytes));
-    RK_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
+    HIP_TRY(tmp.alloc(bytes));
+    HIP_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
                                    rocprim::plus<uint32_t>(), s));
   }
   uint32_t kept = 0;
-  RK_TRY(hipMemcpyAsync(&kept, d_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
-  RK_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(&kept, d_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   *n_res = kept;
   if (kept == 0) return FAC_OK;
-  RK_TRY(d_kept.alloc((uint64_t)kept * sizeof(Span)));
+  HIP_TRY(d_kept.alloc((uint64_t)kept * sizeof(Span)));
   hipLaunchKernelGGL(kept_spans_kernel, dim3(G), dim3(T), 0, s, ranked, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
                      d_kept.as<Span>());
-  RK_TRY(dev_sort(d_kept.as<Span>(), d_sp2.as<Span>(), kept, KeptByStart{}, s));
+  HIP_TRY(dev_sort(d_kept.as<Span>(), d_sp2.as<Span>(), kept, KeptByStart{}, s));
   fac_match* out = (ranked == d_a) ? d_b : d_a;
   hipLaunchKernelGGL(gather_kernel, dim3((kept + T - 1) / T), dim3(T), 0, s, ranked, d_sp2.as<Span>(), (uint64_t)kept,
                      out);
-  RK_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   *res = out;
   return FAC_OK;
 }
@@ -381,21 +373,21 @@ int apply_matches(const Engine& e, std::vector<fac_match>& v, int order, int ove
                   std::string& err) {
   const uint64_t n = v.size();
   if (n == 0 || (order == 0 && overlap == 0)) return FAC_OK;
-  RK_TRY(hipSetDevice(e.device));
+  HIP_TRY(hipSetDevice(e.device));
   hipStream_t s = e.stream;
   t_buf_stream = s;
   Buf d_a, d_b;
-  RK_TRY(d_a.alloc(n * sizeof(fac_match)));
-  RK_TRY(d_b.alloc(n * sizeof(fac_match)));
-  RK_TRY(hipMemcpyAsync(d_a.p, v.data(), n * sizeof(fac_match), hipMemcpyHostToDevice, s));
+  HIP_TRY(d_a.alloc(n * sizeof(fac_match)));
+  HIP_TRY(d_b.alloc(n * sizeof(fac_match)));
+  HIP_TRY(hipMemcpyAsync(d_a.p, v.data(), n * sizeof(fac_match), hipMemcpyHostToDevice, s));
   fac_match* res = nullptr;
   uint64_t nres = 0;
   if (int rc = apply_matches_device(e, d_a.as<fac_match>(), d_b.as<fac_match>(), n, order, overlap, unique_ids, s, &res,
                                     &nres, err))
     return rc;
   v.resize(nres);
-  if (nres) RK_TRY(hipMemcpyAsync(v.data(), res, nres * sizeof(fac_match), hipMemcpyDeviceToHost, s));
-  RK_TRY(hipStreamSynchronize(s));
+  if (nres) HIP_TRY(hipMemcpyAsync(v.data(), res, nres * sizeof(fac_match), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return FAC_OK;
 }
 
@@ -424,8 +416,8 @@ int window_owned_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_
   if (n == 0) return FAC_OK;
   if (n <= kHostRank) {  // few records (C5: ~1 000 per 1 GiB window): ranked on the host, not by ~20 launches
     std::vector<fac_match> v(n);
-    RK_TRY(hipMemcpyAsync(v.data(), d_a, n * sizeof(fac_match), hipMemcpyDeviceToHost, s));
-    RK_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(v.data(), d_a, n * sizeof(fac_match), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     std::sort(v.begin(), v.end(), RankCmpHost{e.pat_bytes.data(), 1});
     walk_host(v, nullptr, false);  // non_overlapping, start order
     uint64_t owned = 0;
@@ -439,8 +431,8 @@ int window_owned_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_
     }
     *n_owned = owned;
     if (owned > cap) return FAC_E_OUTPUT_CAPACITY;
-    if (owned) RK_TRY(hipMemcpyAsync(d_out, v.data(), owned * sizeof(fac_match), hipMemcpyHostToDevice, s));
-    RK_TRY(hipStreamSynchronize(s));
+    if (owned) HIP_TRY(hipMemcpyAsync(d_out, v.data(), owned * sizeof(fac_match), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return FAC_OK;
   }
   fac_match* res = nullptr;
@@ -450,20 +442,20 @@ int window_owned_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_
   t_buf_stream = s;
   // the owned count first (a prefix of the start-ordered list), then the copy if it fits
   Buf d_cnt, d_tmp;
-  RK_TRY(d_cnt.alloc(8));
-  RK_TRY(d_tmp.alloc(nres * sizeof(fac_match)));
-  RK_TRY(hipMemsetAsync(d_cnt.p, 0, 8, s));
+  HIP_TRY(d_cnt.alloc(8));
+  HIP_TRY(d_tmp.alloc(nres * sizeof(fac_match)));
+  HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 8, s));
   const uint32_t T = 256;
   hipLaunchKernelGGL(owned_kernel, dim3((uint32_t)((nres + T - 1) / T)), dim3(T), 0, s, res, nres, byte_base, commit, base,
                      d_tmp.as<fac_match>(), d_cnt.as<unsigned long long>());
-  RK_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   unsigned long long owned = 0;
-  RK_TRY(hipMemcpyAsync(&owned, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
-  RK_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(&owned, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   *n_owned = owned;
   if (owned > cap) return FAC_E_OUTPUT_CAPACITY;
-  if (owned) RK_TRY(hipMemcpyAsync(d_out, d_tmp.p, owned * sizeof(fac_match), hipMemcpyDeviceToDevice, s));
-  RK_TRY(hipStreamSynchronize(s));
+  if (owned) HIP_TRY(hipMemcpyAsync(d_out, d_tmp.p, owned * sizeof(fac_match), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return FAC_OK;
 }
 
@@ -570,7 +562,7 @@ int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t
   *res = d_a;
   *n_res = 0;
   if (n == 0) {
-    RK_TRY(hipMemsetAsync(d_doc_off, 0, (n_docs + 1) * 8, s));
+    HIP_TRY(hipMemsetAsync(d_doc_off, 0, (n_docs + 1) * 8, s));
     return FAC_OK;
   }
   if (n >= (1ull << 32)) {
@@ -580,66 +572,66 @@ int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t
   t_buf_stream = s;
   const uint32_t T = 256;
   const uint32_t G = (uint32_t)((n + T - 1) / T), GD = (uint32_t)((n_docs + 1 + T - 1) / T);
-  RK_TRY(dev_sort(d_a, d_b, n, BatchCmp{e.d_pat_bytes, order}, s));
+  HIP_TRY(dev_sort(d_a, d_b, n, BatchCmp{e.d_pat_bytes, order}, s));
   fac_match* ranked = d_b;
   if (overlap == 0) {
     hipLaunchKernelGGL(batch_doc_index_kernel, dim3(GD), dim3(T), 0, s, reinterpret_cast<const char*>(ranked),
                        sizeof(fac_match), n, n_docs, d_doc_off);
     hipLaunchKernelGGL(batch_rebase_kernel, dim3(G), dim3(T), 0, s, ranked, n, d_offsets);
-    RK_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     *res = ranked;
     *n_res = n;
     return FAC_OK;
   }
   Buf d_idx, d_occ, d_used, d_uid, d_keep, d_pos, d_kept, d_kept2;
-  RK_TRY(d_idx.alloc((n_docs + 1) * 8));
+  HIP_TRY(d_idx.alloc((n_docs + 1) * 8));
   hipLaunchKernelGGL(batch_doc_index_kernel, dim3(GD), dim3(T), 0, s, reinterpret_cast<const char*>(ranked),
                      sizeof(fac_match), n, n_docs, d_idx.as<uint64_t>());
-  RK_TRY(d_occ.alloc(n * sizeof(ulonglong2)));
-  RK_TRY(d_keep.alloc(n));
-  RK_TRY(hipMemsetAsync(d_keep.p, 0, n, s));
+  HIP_TRY(d_occ.alloc(n * sizeof(ulonglong2)));
+  HIP_TRY(d_keep.alloc(n));
+  HIP_TRY(hipMemsetAsync(d_keep.p, 0, n, s));
   const bool unique = overlap == 2;
   if (unique) {
-    RK_TRY(d_used.alloc(n * 8));
+    HIP_TRY(d_used.alloc(n * 8));
     if (unique_ids) {
-      RK_TRY(d_uid.alloc(std::max<size_t>(e.pats.size(), 1) * 8));
-      RK_TRY(hipMemcpyAsync(d_uid.p, unique_ids, e.pats.size() * 8, hipMemcpyHostToDevice, s));
+      HIP_TRY(d_uid.alloc(std::max<size_t>(e.pats.size(), 1) * 8));
+      HIP_TRY(hipMemcpyAsync(d_uid.p, unique_ids, e.pats.size() * 8, hipMemcpyHostToDevice, s));
     }
   }
   hipLaunchKernelGGL(batch_walk_kernel, dim3((uint32_t)((n_docs + T - 1) / T)), dim3(T), 0, s, ranked,
                      d_idx.as<uint64_t>(), n_docs, unique && unique_ids ? d_uid.as<uint64_t>() : (const uint64_t*)nullptr,
                      unique ? 1 : 0, d_occ.as<ulonglong2>(), d_used.as<uint64_t>(), d_keep.as<uint8_t>());
-  RK_TRY(hipGetLastError());
-  RK_TRY(d_pos.alloc(n * 4));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(d_pos.alloc(n * 4));
   {
     size_t bytes = 0;
-    RK_TRY(rocprim::inclusive_scan(nullptr, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
+    HIP_TRY(rocprim::inclusive_scan(nullptr, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
                                    rocprim::plus<uint32_t>(), s));
     Buf tmp;
-    RK_TRY(tmp.alloc(bytes));
-    RK_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
+    HIP_TRY(tmp.alloc(bytes));
+    HIP_TRY(rocprim::inclusive_scan(tmp.p, bytes, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
                                    rocprim::plus<uint32_t>(), s));
   }
   uint32_t kept = 0;
-  RK_TRY(hipMemcpyAsync(&kept, d_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
-  RK_TRY(hipStreamSynchronize(s));  // (also: the pageable unique_ids were read)
+  HIP_TRY(hipMemcpyAsync(&kept, d_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (also: the pageable unique_ids were read)
   *n_res = kept;
   if (kept == 0) {
-    RK_TRY(hipMemsetAsync(d_doc_off, 0, (n_docs + 1) * 8, s));
+    HIP_TRY(hipMemsetAsync(d_doc_off, 0, (n_docs + 1) * 8, s));
     return FAC_OK;
   }
   // the kept matches in (document, start) order, ties in acceptance (rank) order: the tagged start
   // sorts by document first
-  RK_TRY(d_kept.alloc((uint64_t)kept * sizeof(Span)));
-  RK_TRY(d_kept2.alloc((uint64_t)kept * sizeof(Span)));
+  HIP_TRY(d_kept.alloc((uint64_t)kept * sizeof(Span)));
+  HIP_TRY(d_kept2.alloc((uint64_t)kept * sizeof(Span)));
   hipLaunchKernelGGL(kept_spans_kernel, dim3(G), dim3(T), 0, s, ranked, d_keep.as<uint8_t>(), d_pos.as<uint32_t>(), n,
                      d_kept.as<Span>());
-  RK_TRY(dev_sort(d_kept.as<Span>(), d_kept2.as<Span>(), kept, KeptByStart{}, s));
+  HIP_TRY(dev_sort(d_kept.as<Span>(), d_kept2.as<Span>(), kept, KeptByStart{}, s));
   hipLaunchKernelGGL(batch_doc_index_kernel, dim3(GD), dim3(T), 0, s, reinterpret_cast<const char*>(d_kept2.p), sizeof(Span),
                      (uint64_t)kept, n_docs, d_doc_off);
   hipLaunchKernelGGL(batch_gather_kernel, dim3((kept + T - 1) / T), dim3(T), 0, s, ranked, d_kept2.as<Span>(), (uint64_t)kept,
                      d_offsets, d_a);
-  RK_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   // the scratch above goes back to the pool for this stream only: its later users are ordered after these kernels
   *res = d_a;
   return FAC_OK;

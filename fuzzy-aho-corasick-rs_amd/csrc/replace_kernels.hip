@@ -33,6 +33,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "fac_internal.h"
+#include "host_util.h"
 
 namespace fac {
 namespace {
@@ -349,24 +350,13 @@ __global__ void stream_plan_kernel(const fac_match* __restrict__ m, uint64_t n, 
   if ((threadIdx.x & 63u) == 0 && applied) atomicAdd(scal, (unsigned long long)applied);
 }
 
-#define RP_TRY(x)                                              \
-  do {                                                         \
-    hipError_t e_ = (x);                                       \
-    if (e_ != hipSuccess) {                                    \
-      err = std::string(#x ": ") + hipGetErrorString(e_);      \
-      return FAC_E_HIP;                                        \
-    }                                                          \
-  } while (0)
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 int replace_plan_device(const Batch& b, const ReplaceTable& t, const fac_match* d_recs, uint64_t n_recs,
                         const uint64_t* d_doc_off, hipStream_t s, ReplacePlan& plan, std::string& err) {
   const uint64_t nd = b.n_docs;
   size_t scan_bytes = 0;
-  RP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, nd + 1,
+  HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, nd + 1,
                                  rocprim::plus<uint64_t>(), s));
   // one block of call scratch: plan records, lengths, offsets, {n_applied, total}, the scan's own
   const size_t o_plan = 0, o_len = o_plan + up256(std::max<uint64_t>(n_recs, 1) * sizeof(ulonglong2));
@@ -385,17 +375,17 @@ int replace_plan_device(const Batch& b, const ReplaceTable& t, const fac_match* 
   uint64_t* d_len = reinterpret_cast<uint64_t*>(base + o_len);
   plan.d_out_off = reinterpret_cast<uint64_t*>(base + o_off);
   unsigned long long* d_scal = reinterpret_cast<unsigned long long*>(base + o_scal);
-  RP_TRY(hipMemsetAsync(d_scal, 0, 16, s));
+  HIP_TRY(hipMemsetAsync(d_scal, 0, 16, s));
   const auto plan_kernel = t.d_ins ? replace_plan_kernel<true> : replace_plan_kernel<false>;
   hipLaunchKernelGGL(plan_kernel, dim3((uint32_t)((nd + 1 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, d_recs,
                      d_doc_off, b.d_offsets, nd, t.d_tab, t.d_ins, plan.d_plan, d_len, d_scal);
-  RP_TRY(hipGetLastError());
-  RP_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_len, plan.d_out_off, (uint64_t)0, nd + 1,
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_len, plan.d_out_off, (uint64_t)0, nd + 1,
                                  rocprim::plus<uint64_t>(), s));
-  RP_TRY(hipMemcpyAsync(d_scal + 1, plan.d_out_off + nd, 8, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_scal + 1, plan.d_out_off + nd, 8, hipMemcpyDeviceToDevice, s));
   unsigned long long scal[2] = {0, 0};
-  RP_TRY(hipMemcpyAsync(scal, d_scal, 16, hipMemcpyDeviceToHost, s));
-  RP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpyAsync(scal, d_scal, 16, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   plan.n_replaced = scal[0];
   plan.total = scal[1];
   return FAC_OK;
@@ -412,7 +402,7 @@ int launch_copy(const uint8_t* d_utf8, const uint64_t* d_offsets, uint64_t n_doc
   const auto copy_kernel = t.d_ins ? replace_copy_kernel<true> : replace_copy_kernel<false>;
   hipLaunchKernelGGL(copy_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, plan.s, d_utf8, d_offsets, plan.d_out_off,
                      n_docs, d_recs, d_doc_off, plan.d_plan, t.d_tab, t.d_ins, t.d_bytes, d_out, plan.total, wide);
-  RP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 }  // namespace
@@ -460,23 +450,23 @@ int replace_stream_plan_device(const ReplaceTable& t, std::vector<fac_match>& re
   plan.d_view = reinterpret_cast<uint64_t*>(base + o_view);
   plan.d_out_off = plan.d_view + 4;
   unsigned long long* d_scal = reinterpret_cast<unsigned long long*>(base + o_scal);
-  RP_TRY(hipMemsetAsync(d_scal, 0, 24, s));
-  if (n) RP_TRY(hipMemcpyAsync(d_in, recs.data(), n * sizeof(fac_match), hipMemcpyHostToDevice, s));
-  RP_TRY(hipMemcpyAsync(d_woff, win_off.data(), (nw + 1) * 8, hipMemcpyHostToDevice, s));
-  if (nw) RP_TRY(hipMemcpyAsync(d_commit, commit.data(), nw * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(d_scal, 0, 24, s));
+  if (n) HIP_TRY(hipMemcpyAsync(d_in, recs.data(), n * sizeof(fac_match), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_woff, win_off.data(), (nw + 1) * 8, hipMemcpyHostToDevice, s));
+  if (nw) HIP_TRY(hipMemcpyAsync(d_commit, commit.data(), nw * 8, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(stream_carry_kernel, dim3(1), dim3(kCarryThreads), 0, s, d_in, d_woff, d_commit, nw, e_in, d_cur,
                      d_prev);
   const dim3 grid((uint32_t)((n + 1 + kThreads - 1) / kThreads));
   const auto delta_kernel = t.d_ins ? stream_delta_kernel<true> : stream_delta_kernel<false>;
   hipLaunchKernelGGL(delta_kernel, grid, dim3(kThreads), 0, s, d_in, n, d_woff, nw, d_cur, t.d_tab, t.d_ins, d_delta);
-  RP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   if (int rc = exclusive_sum_u64(d_delta, d_sum, n + 1, s, err)) return rc;
   hipLaunchKernelGGL(stream_plan_kernel, grid, dim3(kThreads), 0, s, d_in, n, d_woff, nw, d_cur, d_prev, d_sum, e_in,
                      plan.d_plan, plan.d_recs, plan.d_view, d_scal);
-  RP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   unsigned long long scal[3] = {0, 0, 0};
-  RP_TRY(hipMemcpyAsync(scal, d_scal, 24, hipMemcpyDeviceToHost, s));
-  RP_TRY(hipStreamSynchronize(s));  // (also: the pageable uploads above were read)
+  HIP_TRY(hipMemcpyAsync(scal, d_scal, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (also: the pageable uploads above were read)
   plan.n_replaced = scal[0];
   plan.n_skipped = n - scal[0];
   plan.total = scal[1];

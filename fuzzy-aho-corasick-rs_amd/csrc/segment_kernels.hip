@@ -26,6 +26,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "fac_internal.h"
+#include "host_util.h"
 
 namespace fac {
 namespace {
@@ -295,17 +296,6 @@ __global__ __launch_bounds__(kThreads) void piece_copy_kernel(const uint8_t* __r
   chunk_store(c, out + g, wide);
 }
 
-#define SG_TRY(x)                                              \
-  do {                                                         \
-    hipError_t e_ = (x);                                       \
-    if (e_ != hipSuccess) {                                    \
-      err = std::string(#x ": ") + hipGetErrorString(e_);      \
-      return FAC_E_HIP;                                        \
-    }                                                          \
-  } while (0)
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline dim3 doc_grid(uint64_t nd) { return dim3((uint32_t)((nd + 1 + kThreads - 1) / kThreads)); }
 
 }  // namespace
@@ -315,7 +305,7 @@ int segment_plan_device(const Batch& b, int mode, const fac_match* d_recs, const
   const uint64_t nd = b.n_docs;
   const bool want_cnt = mode >= kRenderSegmentText, want_len = mode <= kRenderSegmentText;
   size_t scan_bytes = 0;
-  SG_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, nd + 1,
+  HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, nd + 1,
                                  rocprim::plus<uint64_t>(), s));
   // one block of call scratch: counts, segment offsets, lengths, output offsets, sources, the scan's own
   const size_t col = up256((nd + 1) * 8);
@@ -346,19 +336,19 @@ int segment_plan_device(const Batch& b, int mode, const fac_match* d_recs, const
     default: SG_PLAN(kSegmentRecords); break;
   }
 #undef SG_PLAN
-  SG_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   unsigned long long scal[2] = {0, 0};  // {segments, output bytes}
   if (want_cnt) {
-    SG_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_cnt, plan.d_seg_off, (uint64_t)0, nd + 1,
+    HIP_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_cnt, plan.d_seg_off, (uint64_t)0, nd + 1,
                                    rocprim::plus<uint64_t>(), s));
-    SG_TRY(hipMemcpyAsync(&scal[0], plan.d_seg_off + nd, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&scal[0], plan.d_seg_off + nd, 8, hipMemcpyDeviceToHost, s));
   }
   if (want_len) {
-    SG_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_len, plan.d_out_off, (uint64_t)0, nd + 1,
+    HIP_TRY(rocprim::exclusive_scan(base + o_tmp, scan_bytes, d_len, plan.d_out_off, (uint64_t)0, nd + 1,
                                    rocprim::plus<uint64_t>(), s));
-    SG_TRY(hipMemcpyAsync(&scal[1], plan.d_out_off + nd, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&scal[1], plan.d_out_off + nd, 8, hipMemcpyDeviceToHost, s));
   }
-  SG_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(s));
   plan.n_segs = scal[0];
   plan.total = scal[1];
   return FAC_OK;
@@ -369,7 +359,7 @@ int segment_write_device(const Batch& b, const fac_match* d_recs, const uint64_t
   if (!plan.n_segs) return FAC_OK;
   hipLaunchKernelGGL(segment_write_kernel, doc_grid(b.n_docs), dim3(kThreads), 0, plan.s, d_recs, d_doc_off, b.d_offsets,
                      b.n_docs, plan.d_seg_off, d_out);
-  SG_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 
@@ -393,7 +383,7 @@ int render_copy_device(const Batch& b, const fac_match* d_recs, const uint64_t* 
     uint64_t* ps = reinterpret_cast<uint64_t*>(static_cast<char*>(plan.mem_pieces) + o_src);
     hipLaunchKernelGGL(segment_pieces_kernel, doc_grid(nd), dim3(kThreads), 0, plan.s, d_recs, d_doc_off, b.h.d_utf8,
                        b.d_offsets, nd, plan.d_seg_off, plan.d_out_off, po, ps);
-    SG_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     piece_out = po;
     piece_src = ps;
     n_pieces = plan.n_segs;
@@ -402,7 +392,7 @@ int render_copy_device(const Batch& b, const fac_match* d_recs, const uint64_t* 
   const int wide = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0 ? 1 : 0;
   hipLaunchKernelGGL(piece_copy_kernel, dim3((uint32_t)tiles), dim3(kThreads), 0, plan.s, b.h.d_utf8, piece_out,
                      piece_src, n_pieces, d_out, plan.total, wide);
-  SG_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "fac_internal.h"
+#include "host_util.h"
 
 namespace fac {
 namespace {
@@ -518,15 +519,6 @@ __global__ __launch_bounds__(256) void write_tile_kernel(const uint8_t* __restri
 
 }  // namespace
 
-#define ST_TRY(x)                                         \
-  do {                                                    \
-    hipError_t _e = (x);                                  \
-    if (_e != hipSuccess) {                               \
-      err = std::string(#x ": ") + hipGetErrorString(_e); \
-      return FAC_E_HIP;                                   \
-    }                                                     \
-  } while (0)
-
 namespace {
 struct BmpTabs {
   uint8_t* p = nullptr;
@@ -543,11 +535,11 @@ int bmp_tables(int device, hipStream_t st, BmpTabs& out, std::string& err) {
   std::lock_guard<std::mutex> lk(mu);
   BmpTabs& t = tabs[device];
   if (!t.p) {
-    ST_TRY(hipMalloc((void**)&t.p, 0x10000));
-    ST_TRY(hipMalloc((void**)&t.l, 0x10000 * sizeof(uint16_t)));
+    HIP_TRY(hipMalloc((void**)&t.p, 0x10000));
+    HIP_TRY(hipMalloc((void**)&t.l, 0x10000 * sizeof(uint16_t)));
     hipLaunchKernelGGL(bmp_tables_kernel, dim3(256), dim3(256), 0, st, t.p, t.l);
-    ST_TRY(hipGetLastError());
-    ST_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
   }
   out = t;
   return FAC_OK;
@@ -566,15 +558,15 @@ int stage_device(const Engine& e, Haystack& h, hipStream_t st, std::string& err,
     h.n = h.ascii ? len : 0;
     if (!h.ascii) {
       if (h.off_cap < 1) {
-        if (h.d_off) ST_TRY(hipFree(h.d_off));
+        if (h.d_off) HIP_TRY(hipFree(h.d_off));
         h.d_off = nullptr;
-        ST_TRY(hipMalloc((void**)&h.d_off, 16));
-        if (h.d_text32) ST_TRY(hipFree(h.d_text32));
+        HIP_TRY(hipMalloc((void**)&h.d_off, 16));
+        if (h.d_text32) HIP_TRY(hipFree(h.d_text32));
         h.d_text32 = nullptr;
-        ST_TRY(hipMalloc((void**)&h.d_text32, 16));
+        HIP_TRY(hipMalloc((void**)&h.d_text32, 16));
         h.off_cap = 1;
       }
-      ST_TRY(hipMemcpyAsync(h.d_off, &h.len, 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(h.d_off, &h.len, 8, hipMemcpyHostToDevice, st));
     }
     return FAC_OK;
   }
@@ -584,10 +576,10 @@ int stage_device(const Engine& e, Haystack& h, hipStream_t st, std::string& err,
   // scratch: scal[4] | bits[ranges] | ubase[n_units] | ucnt[n_units] | hard[ranges]
   const size_t need = 32 + ranges * 8 + n_units * 8 + n_units * 4 + ranges + 16;
   if (h.stage_cap < need) {
-    if (h.d_stage) ST_TRY(hipFree(h.d_stage));
+    if (h.d_stage) HIP_TRY(hipFree(h.d_stage));
     h.d_stage = nullptr;
     h.stage_cap = 0;
-    ST_TRY(hipMalloc(&h.d_stage, need));
+    HIP_TRY(hipMalloc(&h.d_stage, need));
     h.stage_cap = need;
   }
   unsigned long long* scal = static_cast<unsigned long long*>(h.d_stage);
@@ -596,14 +588,14 @@ int stage_device(const Engine& e, Haystack& h, hipStream_t st, std::string& err,
   uint32_t* ucnt = reinterpret_cast<uint32_t*>(ubase + n_units);
   uint8_t* hard = reinterpret_cast<uint8_t*>(ucnt + n_units);
   const int aligned = (reinterpret_cast<uintptr_t>(h.d_utf8) & 15u) == 0 ? 1 : 0;
-  ST_TRY(hipMemsetAsync(scal, 0, 32, st));
+  HIP_TRY(hipMemsetAsync(scal, 0, 32, st));
   if (mode == -2) {
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h.device);
     const uint64_t want = (len / 16 + 255) / 256;
     hipLaunchKernelGGL(ascii_or_kernel, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)cus * 8))),
                        dim3(256), 0, st, h.d_utf8, len, aligned, scal);
-    ST_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(seg_tile_kernel, dim3((uint32_t)n_units), dim3(256), 0, st, h.d_utf8, len, aligned, tabs.p, bits,
                      ucnt, hard, scal, mode == -2 ? 1 : 0);
@@ -611,10 +603,10 @@ int stage_device(const Engine& e, Haystack& h, hipStream_t st, std::string& err,
   hipLaunchKernelGGL(recount_kernel, dim3((uint32_t)((n_units + 3) / 4)), dim3(256), 0, st, bits, ranges, ucnt, n_units,
                      scal);
   hipLaunchKernelGGL(unit_scan_kernel, dim3(1), dim3(1024), 0, st, ucnt, ubase, n_units, scal + 2);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   unsigned long long sc[4] = {0, 0, 0, 0};
-  ST_TRY(hipMemcpyAsync(sc, scal, sizeof(sc), hipMemcpyDeviceToHost, st));
-  ST_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(sc, scal, sizeof(sc), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (sc[0] & 1ull) {  // seg_tile_kernel checks every code point (modes -2 and 0)
     err = "haystack is not valid UTF-8";
     return FAC_E_INVALID;
@@ -630,19 +622,19 @@ int stage_device(const Engine& e, Haystack& h, hipStream_t st, std::string& err,
   h.n = sc[2];
   if (h.n > grapheme_limit()) return FAC_E_HAYSTACK_TOO_LARGE;
   if (h.off_cap < h.n + 1) {  // grapheme starts + off[n] = len (a shard's halo end), folded first chars
-    if (h.d_off) ST_TRY(hipFree(h.d_off));
-    if (h.d_text32) ST_TRY(hipFree(h.d_text32));
+    if (h.d_off) HIP_TRY(hipFree(h.d_off));
+    if (h.d_text32) HIP_TRY(hipFree(h.d_text32));
     h.d_off = nullptr;
     h.d_text32 = nullptr;
     h.off_cap = 0;
-    ST_TRY(hipMalloc((void**)&h.d_off, (h.n + 1) * 8));
-    ST_TRY(hipMalloc((void**)&h.d_text32, std::max<uint64_t>(h.n * 4, 16)));
+    HIP_TRY(hipMalloc((void**)&h.d_off, (h.n + 1) * 8));
+    HIP_TRY(hipMalloc((void**)&h.d_text32, std::max<uint64_t>(h.n * 4, 16)));
     h.off_cap = h.n + 1;
   }
-  ST_TRY(hipMemcpyAsync(h.d_off + h.n, &h.len, 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h.d_off + h.n, &h.len, 8, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(write_tile_kernel, dim3((uint32_t)((n_units + 3) / 4)), dim3(256), 0, st, h.d_utf8, len, aligned, bits, ubase,
                      n_units, tabs.l, e.case_insensitive ? 1 : 0, h.d_off, h.d_text32);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 
@@ -667,10 +659,10 @@ int graphemes_before(const Haystack& h, uint64_t b, hipStream_t st, uint64_t& ou
   }
   unsigned long long* d = static_cast<unsigned long long*>(h.d_stage);  // scal[3]: free after staging
   hipLaunchKernelGGL(starts_before_kernel, dim3(1), dim3(1), 0, st, h.d_off, h.n, b, d + 3);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   unsigned long long v = 0;
-  ST_TRY(hipMemcpyAsync(&v, d + 3, 8, hipMemcpyDeviceToHost, st));
-  ST_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(&v, d + 3, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   out = v;
   return FAC_OK;
 }
@@ -938,14 +930,14 @@ int grapheme_table_build(const std::vector<std::pair<std::u32string, uint32_t>>&
   t.mask = slots - 1;
   t.n_keys = (uint32_t)keys.size();
   t.n_pool = (uint32_t)pool.size();
-  ST_TRY(hipMalloc((void**)&t.d_slots, (size_t)slots * 4));
-  ST_TRY(hipMalloc((void**)&t.d_ents, std::max<size_t>(keys.size() * sizeof(uint4), 16)));
-  ST_TRY(hipMalloc((void**)&t.d_pool, std::max<size_t>(pool.size() * 4, 16)));
-  ST_TRY(hipMemsetAsync(t.d_slots, 0, (size_t)slots * 4, st));
+  HIP_TRY(hipMalloc((void**)&t.d_slots, (size_t)slots * 4));
+  HIP_TRY(hipMalloc((void**)&t.d_ents, std::max<size_t>(keys.size() * sizeof(uint4), 16)));
+  HIP_TRY(hipMalloc((void**)&t.d_pool, std::max<size_t>(pool.size() * 4, 16)));
+  HIP_TRY(hipMemsetAsync(t.d_slots, 0, (size_t)slots * 4, st));
   if (keys.empty()) return FAC_OK;
   uint2* d_keys = nullptr;
   uint32_t* d_ids = nullptr;
-  ST_TRY(hipMalloc((void**)&d_keys, ks.size() * sizeof(uint2)));
+  HIP_TRY(hipMalloc((void**)&d_keys, ks.size() * sizeof(uint2)));
   hipError_t he = hipMalloc((void**)&d_ids, ids.size() * 4);
   if (he == hipSuccess && !pool.empty()) he = hipMemcpyAsync(t.d_pool, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, st);
   if (he == hipSuccess) he = hipMemcpyAsync(d_keys, ks.data(), ks.size() * sizeof(uint2), hipMemcpyHostToDevice, st);
@@ -958,7 +950,7 @@ int grapheme_table_build(const std::vector<std::pair<std::u32string, uint32_t>>&
   if (he == hipSuccess) he = hipStreamSynchronize(st);  // (the host vectors and the two temporaries go away)
   (void)hipFree(d_keys);
   if (d_ids) (void)hipFree(d_ids);
-  ST_TRY(he);
+  HIP_TRY(he);
   return FAC_OK;
 }
 
@@ -984,7 +976,7 @@ int symbol_ids_device(const Engine& e, const Haystack& h, uint64_t g0, uint64_t 
   const uint64_t blocks = (g1 - g0 + 255) / 256;  // (h.n <= u32::MAX graphemes: the grid fits)
   hipLaunchKernelGGL(symbol_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n, g0, g1,
                      tabs.l, e.case_insensitive ? 1 : 0, t.d_slots, t.d_ents, t.d_pool, t.mask, t.n_keys, t.n_pool, lds, d_ids);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 
@@ -1008,7 +1000,7 @@ int batch_symbol_ids_device(const Engine& e, const Batch& b, uint8_t* d_ids, hip
   hipLaunchKernelGGL(batch_symbol_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, b.d_segs,
                      b.d_prefix, b.n_segs, S, e.d_ascii_id, tabs.l, e.case_insensitive ? 1 : 0, t.d_slots, t.d_ents, t.d_pool,
                      t.mask, t.n_keys, t.n_pool, lds, d_ids);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 
@@ -1016,7 +1008,7 @@ int batch_symbol_starts_device(const Batch& b, uint32_t* d_bits, hipStream_t st,
   if (b.n_segs == 0) return FAC_OK;
   hipLaunchKernelGGL(batch_symbol_starts_kernel, dim3((uint32_t)((b.n_segs + 255) / 256)), dim3(256), 0, st, b.d_prefix,
                      b.n_segs, d_bits);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 
@@ -1036,7 +1028,7 @@ int slice_descs_device(const Haystack& h, const std::vector<std::pair<uint64_t, 
   hipError_t he = hipSuccess;
   const size_t in_b = flat.size() * 8, out_b = spans.size() * sizeof(SegDesc);
   uint8_t* mem = static_cast<uint8_t*>(call_scratch_take(in_b + out_b, st, &he));
-  ST_TRY(he);
+  HIP_TRY(he);
   uint64_t* d_spans = reinterpret_cast<uint64_t*>(mem);
   SegDesc* d_out = reinterpret_cast<SegDesc*>(mem + in_b);  // (in_b is a multiple of 16)
   he = hipMemcpyAsync(d_spans, flat.data(), in_b, hipMemcpyHostToDevice, st);
@@ -1049,7 +1041,7 @@ int slice_descs_device(const Haystack& h, const std::vector<std::pair<uint64_t, 
   if (he == hipSuccess) he = hipStreamSynchronize(st);
   else (void)hipStreamSynchronize(st);  // (the upload may be in flight: flat goes away)
   call_scratch_give(mem, st);
-  ST_TRY(he);
+  HIP_TRY(he);
   return FAC_OK;
 }
 
@@ -1219,13 +1211,13 @@ __global__ void batch_desc_kernel(const uint64_t* __restrict__ off, uint64_t n_d
 
 int exclusive_sum_u64(const uint64_t* d_in, uint64_t* d_out, uint64_t n, hipStream_t st, std::string& err) {
   size_t bytes = 0;
-  ST_TRY(rocprim::exclusive_scan(nullptr, bytes, d_in, d_out, uint64_t(0), n, rocprim::plus<uint64_t>(), st));
+  HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, d_in, d_out, uint64_t(0), n, rocprim::plus<uint64_t>(), st));
   hipError_t he = hipSuccess;
   void* tmp = call_scratch_take(std::max<size_t>(bytes, 16), st, &he);
-  ST_TRY(he);
+  HIP_TRY(he);
   he = rocprim::exclusive_scan(tmp, bytes, d_in, d_out, uint64_t(0), n, rocprim::plus<uint64_t>(), st);
   call_scratch_give(tmp, st);
-  ST_TRY(he);
+  HIP_TRY(he);
   return FAC_OK;
 }
 
@@ -1271,10 +1263,10 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   const size_t tri_b = (nd + 1) * sizeof(BatchTri), flag_b = (nd * 4 + 15) & ~size_t(15);
   const size_t need = flag_b + 2 * tri_b + 64;
   if (b.meta_cap < need) {
-    if (b.d_meta) ST_TRY(hipFree(b.d_meta));
+    if (b.d_meta) HIP_TRY(hipFree(b.d_meta));
     b.d_meta = nullptr;
     b.meta_cap = 0;
-    ST_TRY(hipMalloc(&b.d_meta, need));
+    HIP_TRY(hipMalloc(&b.d_meta, need));
     b.meta_cap = need;
   }
   uint8_t* m = static_cast<uint8_t*>(b.d_meta);
@@ -1283,15 +1275,15 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   b.d_tri_ex = reinterpret_cast<BatchTri*>(m + flag_b + tri_b);
   b.d_scal = reinterpret_cast<unsigned long long*>(m + flag_b + 2 * tri_b);
   const unsigned long long scal0[4] = {0ull, ~0ull, ~0ull, 0ull};
-  ST_TRY(hipMemcpyAsync(b.d_scal, scal0, sizeof(scal0), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b.d_scal, scal0, sizeof(scal0), hipMemcpyHostToDevice, st));
   const uint32_t T = 256;
   const uint32_t G1 = (uint32_t)((nd + 1 + T - 1) / T);
   // the offsets are checked before anything is read through them
   hipLaunchKernelGGL(batch_offsets_kernel, dim3(G1), dim3(T), 0, st, b.d_offsets, nd, len, b.d_scal);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   unsigned long long sc[4] = {0, 0, 0, 0};
-  ST_TRY(hipMemcpyAsync(sc, b.d_scal, sizeof(sc), hipMemcpyDeviceToHost, st));
-  ST_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(sc, b.d_scal, sizeof(sc), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (sc[0] & 1ull) {
     err = "batch offsets must start at 0, not decrease, and end at the byte count";
     b.err_doc = ~0ull;
@@ -1307,21 +1299,21 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
                      (uint32_t*)nullptr);
   hipLaunchKernelGGL(batch_tri_kernel, dim3(G1), dim3(T), 0, st, b.d_offsets, nd, b.d_flags, b.d_tri_in, grapheme_limit(),
                      b.d_scal);
-  ST_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   {
     size_t bytes = 0;
-    ST_TRY(rocprim::exclusive_scan(nullptr, bytes, b.d_tri_in, b.d_tri_ex, BatchTri{0, 0, 0}, nd + 1, TriPlus{}, st));
+    HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, b.d_tri_in, b.d_tri_ex, BatchTri{0, 0, 0}, nd + 1, TriPlus{}, st));
     hipError_t he = hipSuccess;
     void* tmp = call_scratch_take(std::max<size_t>(bytes, 16), st, &he);
-    ST_TRY(he);
+    HIP_TRY(he);
     he = rocprim::exclusive_scan(tmp, bytes, b.d_tri_in, b.d_tri_ex, BatchTri{0, 0, 0}, nd + 1, TriPlus{}, st);
     call_scratch_give(tmp, st);
-    ST_TRY(he);
+    HIP_TRY(he);
   }
   BatchTri tot{0, 0, 0};
-  ST_TRY(hipMemcpyAsync(sc, b.d_scal, sizeof(sc), hipMemcpyDeviceToHost, st));
-  ST_TRY(hipMemcpyAsync(&tot, b.d_tri_ex + nd, sizeof(tot), hipMemcpyDeviceToHost, st));
-  ST_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(sc, b.d_scal, sizeof(sc), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&tot, b.d_tri_ex + nd, sizeof(tot), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   // search_raw applied to the documents in order: the first document that fails decides the error
   // (an invalid document has no grapheme count, so only the valid ones can be too large)
   if (sc[1] != ~0ull || sc[2] != ~0ull) {
@@ -1332,8 +1324,8 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
     }
     b.err_doc = sc[2];
     BatchTri t{0, 0, 0};
-    ST_TRY(hipMemcpyAsync(&t, b.d_tri_in + sc[2], sizeof(t), hipMemcpyDeviceToHost, st));
-    ST_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&t, b.d_tri_in + sc[2], sizeof(t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     b.err_graphemes = t.w;
     return FAC_E_HAYSTACK_TOO_LARGE;
   }
@@ -1341,32 +1333,32 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   h.n = tot.u;
   if (!h.ascii) {
     if (h.off_cap < h.n + 1) {
-      if (h.d_off) ST_TRY(hipFree(h.d_off));
-      if (h.d_text32) ST_TRY(hipFree(h.d_text32));
+      if (h.d_off) HIP_TRY(hipFree(h.d_off));
+      if (h.d_text32) HIP_TRY(hipFree(h.d_text32));
       h.d_off = nullptr;
       h.d_text32 = nullptr;
       h.off_cap = 0;
-      ST_TRY(hipMalloc((void**)&h.d_off, (h.n + 1) * 8));
-      ST_TRY(hipMalloc((void**)&h.d_text32, std::max<uint64_t>(h.n * 4, 16)));
+      HIP_TRY(hipMalloc((void**)&h.d_off, (h.n + 1) * 8));
+      HIP_TRY(hipMalloc((void**)&h.d_text32, std::max<uint64_t>(h.n * 4, 16)));
       h.off_cap = h.n + 1;
     }
     hipLaunchKernelGGL(batch_seg_kernel<true>, dim3((uint32_t)((nd + 63) / 64)), dim3(64), 0, st, h.d_utf8, b.d_offsets, nd,
                        b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, b.d_tri_ex, h.d_off, h.d_text32);
   }
   if (b.seg_cap < tot.s + 1) {
-    if (b.d_segs) ST_TRY(hipFree(b.d_segs));
-    if (b.d_prefix) ST_TRY(hipFree(b.d_prefix));
+    if (b.d_segs) HIP_TRY(hipFree(b.d_segs));
+    if (b.d_prefix) HIP_TRY(hipFree(b.d_prefix));
     b.d_segs = nullptr;
     b.d_prefix = nullptr;
     b.seg_cap = 0;
-    ST_TRY(hipMalloc((void**)&b.d_segs, (tot.s + 1) * sizeof(SegDesc)));
-    ST_TRY(hipMalloc((void**)&b.d_prefix, (tot.s + 1) * 8));
+    HIP_TRY(hipMalloc((void**)&b.d_segs, (tot.s + 1) * sizeof(SegDesc)));
+    HIP_TRY(hipMalloc((void**)&b.d_prefix, (tot.s + 1) * 8));
     b.seg_cap = tot.s + 1;
   }
   hipLaunchKernelGGL(batch_desc_kernel, dim3((uint32_t)((nd + T - 1) / T)), dim3(T), 0, st, b.d_offsets, nd, b.d_flags,
                      b.d_tri_in, b.d_tri_ex, b.d_segs, b.d_prefix);
-  ST_TRY(hipGetLastError());
-  ST_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
   b.n_segs = tot.s;
   b.windows = tot.w;
   return FAC_OK;
