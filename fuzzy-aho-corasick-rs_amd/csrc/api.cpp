@@ -549,6 +549,37 @@ int64_t fac_haystack_symbol_ids(const fac_engine* engine, const fac_haystack* ha
   return (int64_t)h.n;
 }
 
+// fac_haystack_grapheme_ids / fac_batch_grapheme_ids: the search path's own ids (ensure_gids), copied out
+static int64_t grapheme_ids_out(const fac::Engine& e, const fac::Haystack& h, void* stream, uint32_t* out, uint64_t cap) {
+  if (cap && !out) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
+  if (!e.has_map) return -1;
+  if (h.device != e.device) return -(int64_t)fail(FAC_E_INVALID, "haystack was staged for another device");
+  if (h.ascii || h.n == 0) return 0;
+  if (hipSetDevice(e.device) != hipSuccess) return -(int64_t)fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : e.stream;
+  std::string err;
+  if (int rc = fac::ensure_gids(e, h, st, err)) return -(int64_t)fail(rc, err);
+  const uint64_t take = std::min(cap, h.n);
+  if ((take && hipMemcpyAsync(out, h.d_gid, take * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return -(int64_t)fail(FAC_E_HIP, "copy of the grapheme ids failed");
+  return (int64_t)h.n;
+}
+
+int64_t fac_haystack_grapheme_ids(const fac_engine* engine, const fac_haystack* hay, void* stream, uint32_t* out,
+                                  uint64_t cap) {
+  if (!engine || !hay) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
+  return grapheme_ids_out(engine->e, hay->h, stream, out, cap);
+}
+
+uint32_t fac_engine_grapheme_id(const fac_engine* engine, const uint8_t* utf8, uint64_t len) {
+  if (!engine || !engine->e.has_map || !utf8 || len == 0) return 0;
+  std::u32string g;
+  fac::fold_grapheme(utf8, 0, len, engine->e.case_insensitive, g);
+  const auto it = engine->e.gid_of.find(g);
+  return it == engine->e.gid_of.end() ? 0u : it->second;
+}
+
 void fac_haystack_free(fac_haystack* hay) {
   if (!hay) return;
   fac::free_haystack(hay->h);
@@ -1265,6 +1296,17 @@ int fac_batch_allow_unicode_prefilter(fac_batch* batch, int32_t on) {
   return FAC_OK;
 }
 
+int fac_batch_allow_unicode_mappings(fac_batch* batch, int32_t on) {
+  if (!batch) return fail(FAC_E_INVALID, "NULL argument");
+  batch->b.unicode_map = on != 0;
+  return FAC_OK;
+}
+
+int64_t fac_batch_grapheme_ids(const fac_engine* engine, const fac_batch* batch, void* stream, uint32_t* out, uint64_t cap) {
+  if (!engine || !batch) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
+  return grapheme_ids_out(engine->e, batch->b.h, stream, out, cap);
+}
+
 uint64_t fac_batch_doc_graphemes(const fac_batch* batch, uint64_t d, int32_t* is_ascii) {
   if (is_ascii) *is_ascii = 1;
   if (!batch || d >= batch->b.n_docs) return 0;
@@ -1390,7 +1432,7 @@ static int search_batch_impl(const fac_engine* engine, const fac_batch* batch, c
   const fac::Engine& e = engine->e;
   const fac::Batch& b = batch->b;
   if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
-  if (e.has_map && !b.h.ascii)
+  if (e.has_map && !b.h.ascii && !b.unicode_map)
     return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
   hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
@@ -1563,7 +1605,7 @@ static int replace_batch_impl(const fac_engine* engine, const fac_batch* batch, 
   if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
   if (t.device != e.device || t.n_patterns != e.pats.size())
     return fail(FAC_E_INVALID, "the replacement table was built for another engine");
-  if (e.has_map && !b.h.ascii)
+  if (e.has_map && !b.h.ascii && !b.unicode_map)
     return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
   hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
@@ -1630,7 +1672,7 @@ static int extract_batch_impl(const fac_engine* engine, const fac_batch* batch, 
   if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
   if (t && (t->device != e.device || t->n_patterns != e.pats.size()))
     return fail(FAC_E_INVALID, "the replacement table was built for another engine");
-  if (e.has_map && !b.h.ascii)
+  if (e.has_map && !b.h.ascii && !b.unicode_map)
     return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
   hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
@@ -1723,7 +1765,7 @@ static int segment_batch_impl(const fac_engine* engine, const fac_batch* batch, 
   const fac::Engine& e = engine->e;
   const fac::Batch& b = batch->b;
   if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
-  if (e.has_map && !b.h.ascii)
+  if (e.has_map && !b.h.ascii && !b.unicode_map)
     return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
   hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
@@ -1774,7 +1816,7 @@ static int render_batch_impl(const fac_engine* engine, const fac_batch* batch, i
   const fac::Engine& e = engine->e;
   const fac::Batch& b = batch->b;
   if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
-  if (e.has_map && !b.h.ascii)
+  if (e.has_map && !b.h.ascii && !b.unicode_map)
     return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
   if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
   hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;

@@ -49,6 +49,11 @@ int upload_engine(Engine& e, std::string& err) {
     if ((rc = upload(e.map_range, &e.d_map_range, err))) return rc;
     if ((rc = upload(e.map_ent, &e.d_map_ent, err))) return rc;
     if ((rc = upload(e.map_hay, &e.d_map_hay, err))) return rc;
+    // folded grapheme -> dictionary id, for the ids of Unicode text (grapheme_ids_kernel); sorted, so
+    // the table does not depend on the hash map's iteration order
+    std::vector<std::pair<std::u32string, uint32_t>> keys(e.gid_of.begin(), e.gid_of.end());
+    std::sort(keys.begin(), keys.end());
+    if ((rc = grapheme_table_build(keys, e.gid_tab, e.stream, err))) return rc;
   }
   if (e.bitap_ok) {
     // the packed masks depend on the per-call edit budgets: prefilter_windows builds them
@@ -72,6 +77,7 @@ void free_engine_device(Engine& e) {
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   grapheme_table_free(e.sym_tab);
+  grapheme_table_free(e.gid_tab);
   e.pf_cache.clear();
   for (int i = 0; i < Engine::kScratch; ++i)
     if (e.scratch_p[i]) {
@@ -132,9 +138,10 @@ int stage_haystack_device(const Engine& e, const uint8_t* d_utf8, uint64_t len, 
     h.utf8.clear();
     h.starts.clear();
   }
-  if (h.d_gid) HIP_TRY(hipFree(h.d_gid));
-  h.d_gid = nullptr;
-  h.gid_engine = nullptr;
+  {  // the grapheme ids follow the text: the contents are stale, the array stays (ensure_gids)
+    std::lock_guard<std::mutex> lk(h.gid_mu);
+    h.gid_engine = nullptr;
+  }
   hipStream_t st = stream ? stream : e.stream;
   int rc = stage_device(e, h, st, err, mode);
   if (!rc) {
@@ -180,29 +187,33 @@ void free_haystack(Haystack& h) {
   h.d_off = nullptr;
   h.d_gid = nullptr;
   h.d_stage = nullptr;
+  h.gid_cap = 0;
+  h.gid_engine = nullptr;
   h.off_cap = 0;
   h.stage_cap = 0;
 }
 
-// Grapheme ids of a Unicode haystack for an engine with mappings (gs_text compared as whole
-// folded graphemes, grapheme.rs:61-63): computed on the host on first use and uploaded.
-int ensure_gids(const Engine& e, const Haystack& h, std::string& err) {
-  if (h.ascii || (h.d_gid && h.gid_engine == &e)) return FAC_OK;
-  if (int hrc = ensure_host(h, err)) return hrc;
-  std::vector<uint32_t> gid(h.n, 0);
-  std::u32string g;
-  const uint8_t* utf8 = h.utf8.data();
-  for (uint64_t i = 0; i < h.n; ++i) {
-    const uint64_t b = h.starts[i], en = i + 1 < h.n ? h.starts[i + 1] : h.len;
-    fold_grapheme(utf8, b, en, e.case_insensitive, g);
-    auto it = e.gid_of.find(g);
-    if (it != e.gid_of.end()) gid[i] = it->second;
-  }
+// Grapheme ids of a Unicode haystack, or of a batch's non-ASCII documents, for an engine with
+// mappings (gs_text compared as whole folded graphemes, grapheme.rs:61-63): looked up on the device
+// by the first search after a staging (grapheme_ids_device) and kept for that engine. The build is
+// ordered on the call's stream and synchronised once, so a search on any other stream that finds the
+// cache valid reads complete ids.
+int ensure_gids(const Engine& e, const Haystack& h, hipStream_t st, std::string& err) {
+  if (h.ascii) return FAC_OK;
+  std::lock_guard<std::mutex> lk(h.gid_mu);
+  if (h.d_gid && h.gid_engine == &e) return FAC_OK;
   HIP_TRY(hipSetDevice(h.device));
-  if (h.d_gid) HIP_TRY(hipFree(h.d_gid));
-  h.d_gid = nullptr;
-  HIP_TRY(hipMalloc((void**)&h.d_gid, std::max<size_t>(gid.size() * sizeof(uint32_t), 16)));
-  if (!gid.empty()) HIP_TRY(hipMemcpy(h.d_gid, gid.data(), gid.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  h.gid_engine = nullptr;
+  if (!h.d_gid || h.gid_cap < h.n) {
+    if (h.d_gid) HIP_TRY(hipFree(h.d_gid));
+    h.d_gid = nullptr;
+    h.gid_cap = 0;
+    HIP_TRY(hipMalloc((void**)&h.d_gid, std::max<uint64_t>(h.n * sizeof(uint32_t), 16)));
+    h.gid_cap = h.n;
+  }
+  if (!st) st = e.stream;
+  if (int rc = grapheme_ids_device(e, h, h.d_gid, st, err)) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
   h.gid_engine = &e;
   return FAC_OK;
 }

@@ -334,7 +334,8 @@ struct PfTables {
 // A device lookup "folded grapheme -> id" (stage_kernels.hip): an open-addressing table over a hash
 // of the grapheme's folded code points. A slot holds an entry's index + 1 (0: empty), an entry
 // {hash, offset of its key in the pool, key length in code points, id}; the pool holds every key's
-// code points. Keys have any length and ids are 32 bits, so the same structure can hold Engine::gid_of.
+// code points. Keys have any length and ids are 32 bits: Engine::sym_tab holds the pre-filter's
+// symbols, Engine::gid_tab the grapheme dictionary of an engine with mappings (Engine::gid_of).
 struct GraphemeTable {
   uint32_t* d_slots = nullptr;
   uint4* d_ents = nullptr;
@@ -420,6 +421,7 @@ struct Engine {
   float* d_sim_vals = nullptr;
   uint8_t* d_ascii_id = nullptr;
   GraphemeTable sym_tab;  // symbol_ids on the device (bitap_ok engines; symbol_ids_device)
+  GraphemeTable gid_tab;  // gid_of on the device (has_map engines; grapheme_ids_device)
   uint32_t* d_edge_gid = nullptr;
   uint32_t* d_ascii_gid = nullptr;
   uint2* d_map_range = nullptr;
@@ -457,14 +459,23 @@ struct Haystack {
   uint64_t off_cap = 0;          // entries d_off / d_text32 hold (kept when staged again)
   void* d_stage = nullptr;       // staging scratch (stage_device), kept when staged again
   size_t stage_cap = 0;
-  // host copies, fetched from the device on first use (ensure_host): the UTF-8 bytes (the mapping
-  // engines' host transcode, shard planning) and the grapheme byte starts (Unicode only)
+  // host copies, fetched from the device on first use (ensure_host): the UTF-8 bytes (shard
+  // planning) and the grapheme byte starts (Unicode only)
   mutable std::vector<uint8_t> utf8;
   mutable std::vector<uint64_t> starts;
   mutable bool host_ready = false;
   mutable std::mutex host_mu;
-  mutable uint32_t* d_gid = nullptr;  // grapheme ids (Unicode, engines with mappings; lazy)
+  // grapheme ids (Unicode, engines with mappings): written by the device on the first search after
+  // a staging (ensure_gids) for the engine gid_engine (nullptr: the contents are stale); the array
+  // is kept when the haystack is staged again
+  mutable std::mutex gid_mu;
+  mutable uint32_t* d_gid = nullptr;
+  mutable uint64_t gid_cap = 0;  // entries d_gid holds
   mutable const void* gid_engine = nullptr;
+  // a batch's haystack (Batch::h): the batch's n_docs + 1 document byte offsets, which end the last
+  // grapheme of every document (d_off is tagged and has no closing entry per document); else nullptr
+  const uint64_t* d_doc_off = nullptr;
+  uint64_t n_docs = 0;
   int device = 0;
   uint64_t failed_n = 0;  // graphemes counted by a failed restage (stage_haystack_device), for the error
 };
@@ -513,6 +524,10 @@ struct Batch {
   // document, a grapheme of any other); d_sstart is that space's document-start bitmap, one bit per
   // symbol, built and kept as d_dstart is (same mutex). The flag survives a restage in place.
   bool unicode_pf = false;
+  // fac_batch_allow_unicode_mappings: an engine with multi-character mappings may take this batch
+  // even if it holds non-ASCII documents (their grapheme ids: batch_grapheme_ids_kernel). Kept
+  // across a restage like unicode_pf, and independent of it.
+  bool unicode_map = false;
   mutable uint32_t* d_sstart = nullptr;
   mutable uint64_t sstart_cap = 0;  // words d_sstart holds
   mutable bool sstart_ready = false;
@@ -796,8 +811,13 @@ int auto_beam_total(const Engine& e, const Haystack& h, const std::vector<SegDes
 const char* diag_env(const char* name);
 // the host copies of a staged haystack (Haystack::utf8, ::starts), fetched once from the device
 int ensure_host(const Haystack& h, std::string& err);
-// the grapheme ids of a Unicode haystack for an engine with mappings, computed and uploaded on first use
-int ensure_gids(const Engine& e, const Haystack& h, std::string& err);
+// the grapheme ids of a Unicode haystack (or of a batch's non-ASCII documents) for an engine with
+// mappings: h.d_gid, written by the device on st on first use and complete on return
+int ensure_gids(const Engine& e, const Haystack& h, hipStream_t st, std::string& err);
+// stage_kernels.hip: Engine::gid_of's id (0 = not in the dictionary) of every grapheme of h, looked
+// up in e.gid_tab and written to d_ids[0, h.n) on st (asynchronous): grapheme_ids_kernel, or
+// batch_grapheme_ids_kernel for a batch's haystack
+int grapheme_ids_device(const Engine& e, const Haystack& h, uint32_t* d_ids, hipStream_t st, std::string& err);
 // largest grapheme count a haystack may have (u32::MAX, search.rs:198-201; lowered only by the
 // diagnostics knob FAC_GRAPHEME_LIMIT so tests can reach SearchError::HaystackTooLarge)
 uint64_t grapheme_limit();

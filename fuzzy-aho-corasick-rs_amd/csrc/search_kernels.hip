@@ -4142,7 +4142,7 @@ namespace {
 // The fields of a pass's SearchParams that come from the engine, the haystack and the call and stay
 // as they are through launch_pass's re-runs; with mappings, the haystack's grapheme ids (ensure_gids).
 int base_params(const Engine& e, const Haystack& h, float thr, uint32_t beam, bool exact_dedup, uint64_t n_segs,
-                uint64_t windows, SearchParams& P, std::string& err) {
+                uint64_t windows, hipStream_t stream, SearchParams& P, std::string& err) {
   P.nodes = e.d_nodes;
   P.edges = e.d_edges;
   P.out_pat = e.d_out_pat;
@@ -4189,7 +4189,7 @@ int base_params(const Engine& e, const Haystack& h, float thr, uint32_t beam, bo
   P.window_skip = e.window_skip;
   P.has_map = e.has_map ? 1 : 0;
   if (e.has_map) {  // multi-character mappings: whole-grapheme ids (ensure_gids for Unicode text)
-    const int grc = ensure_gids(e, h, err);
+    const int grc = ensure_gids(e, h, stream, err);
     if (grc) return grc;
     P.edge_gid = e.d_edge_gid;
     P.gid32 = h.d_gid;
@@ -4326,7 +4326,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   const uint64_t rc_seg_windows = dsegs ? dsegs->rc_seg_windows : 1024ull;
 
   SearchParams P{};
-  if (int brc = base_params(e, h, thr, beam, exact_dedup, n_segs, windows, P, err)) return brc;
+  if (int brc = base_params(e, h, thr, beam, exact_dedup, n_segs, windows, stream, P, err)) return brc;
 
   int cus = 256;
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e.device));

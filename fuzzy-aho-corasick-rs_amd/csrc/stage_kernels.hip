@@ -793,14 +793,19 @@ __device__ __forceinline__ uint32_t grapheme_symbol_id(const uint8_t* __restrict
 }
 
 // One thread per grapheme g of [g0, g1): bytes [off[g], off[g + 1]) (the last grapheme ends at len).
-// The table (<= 255 symbols) is copied to LDS when it fits; the loads of off are coalesced and a
-// wave's graphemes are contiguous bytes. ids[g - g0] = the id, 0 = no pattern grapheme.
+// The table is copied to LDS when it fits; the loads of off are coalesced and a wave's graphemes are
+// contiguous bytes. ids[g - g0] = the id, 0 = not a key. Id = uint8_t: the pre-filter's symbols
+// (<= 255, ascii_ids null); uint32_t: the grapheme dictionary of an engine with mappings
+// (grapheme_ids_kernel below), where a one-byte grapheme takes its id from ascii_ids
+// (Engine::ascii_gid, indexed by the byte as it stands) without a lookup.
+template <typename Id>
 __global__ __launch_bounds__(256) void symbol_ids_kernel(const uint8_t* __restrict__ utf8, uint64_t len,
                                                          const uint64_t* __restrict__ off, uint64_t n, uint64_t g0,
                                                          uint64_t g1, const uint16_t* __restrict__ ltab, int ci,
                                                          const uint32_t* __restrict__ g_slots, const uint4* __restrict__ g_ents,
                                                          const uint32_t* __restrict__ g_pool, uint32_t mask, uint32_t n_keys,
-                                                         uint32_t n_pool, int lds, uint8_t* __restrict__ ids) {
+                                                         uint32_t n_pool, int lds, const uint32_t* __restrict__ ascii_ids,
+                                                         Id* __restrict__ ids) {
   const GtView t = gt_view(g_slots, g_ents, g_pool, mask, n_keys, n_pool, lds);
   const uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= g1 || g >= n) return;
@@ -809,7 +814,42 @@ __global__ __launch_bounds__(256) void symbol_ids_kernel(const uint8_t* __restri
     ids[g - g0] = 0;
     return;
   }
-  ids[g - g0] = (uint8_t)grapheme_symbol_id(utf8, b, e, ltab, ci, t);
+  if (ascii_ids && e - b == 1) {
+    ids[g - g0] = (Id)ascii_ids[utf8[b] & 0x7Fu];
+    return;
+  }
+  ids[g - g0] = (Id)grapheme_symbol_id(utf8, b, e, ltab, ci, t);
+}
+constexpr auto grapheme_ids_kernel = symbol_ids_kernel<uint32_t>;
+
+// The same for the graphemes of a batch's non-ASCII documents (h.d_off of Batch::h: document order,
+// the index space of d_text32 and of SegDesc::text_base), one thread per grapheme g of n: it begins
+// at byte off[g] & kByte of document off[g] >> kDocTagShift and ends where the next grapheme begins
+// if that one carries the same tag, else at its document's end doc_off[doc + 1] -- off[g + 1] then
+// belongs to the next non-ASCII document, whatever lies between them, or is past the last grapheme.
+__global__ __launch_bounds__(256) void batch_grapheme_ids_kernel(
+    const uint8_t* __restrict__ utf8, uint64_t len, const uint64_t* __restrict__ off, uint64_t n,
+    const uint64_t* __restrict__ doc_off, uint64_t n_docs, const uint16_t* __restrict__ ltab, int ci,
+    const uint32_t* __restrict__ g_slots, const uint4* __restrict__ g_ents, const uint32_t* __restrict__ g_pool,
+    uint32_t mask, uint32_t n_keys, uint32_t n_pool, int lds, const uint32_t* __restrict__ ascii_ids,
+    uint32_t* __restrict__ ids) {
+  const GtView t = gt_view(g_slots, g_ents, g_pool, mask, n_keys, n_pool, lds);
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  constexpr uint64_t kByte = (1ull << kDocTagShift) - 1;
+  const uint64_t w = off[g], b = w & kByte, doc = w >> kDocTagShift;
+  uint64_t e = 0;
+  if (g + 1 < n && (off[g + 1] >> kDocTagShift) == doc) e = off[g + 1] & kByte;
+  else if (doc < n_docs) e = doc_off[doc + 1];
+  if (b >= e || e > len) {  // (never for a staged batch)
+    ids[g] = 0;
+    return;
+  }
+  if (e - b == 1) {
+    ids[g] = ascii_ids[utf8[b] & 0x7Fu];
+    return;
+  }
+  ids[g] = grapheme_symbol_id(utf8, b, e, ltab, ci, t);
 }
 
 // The last k of [lo, hi] with prefix[k] <= p (prefix ascends strictly: the non-empty documents)
@@ -974,8 +1014,37 @@ int symbol_ids_device(const Engine& e, const Haystack& h, uint64_t g0, uint64_t 
   if (int trc = bmp_tables(h.device, st, tabs, err)) return trc;
   const int lds = (t.mask < kGtSlotsLds && t.n_keys <= kGtKeysLds && t.n_pool <= kGtPoolLds) ? 1 : 0;
   const uint64_t blocks = (g1 - g0 + 255) / 256;  // (h.n <= u32::MAX graphemes: the grid fits)
-  hipLaunchKernelGGL(symbol_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n, g0, g1,
-                     tabs.l, e.case_insensitive ? 1 : 0, t.d_slots, t.d_ents, t.d_pool, t.mask, t.n_keys, t.n_pool, lds, d_ids);
+  hipLaunchKernelGGL(symbol_ids_kernel<uint8_t>, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n, g0,
+                     g1, tabs.l, e.case_insensitive ? 1 : 0, t.d_slots, t.d_ents, t.d_pool, t.mask, t.n_keys, t.n_pool, lds,
+                     (const uint32_t*)nullptr, d_ids);
+  HIP_TRY(hipGetLastError());
+  return FAC_OK;
+}
+
+int grapheme_ids_device(const Engine& e, const Haystack& h, uint32_t* d_ids, hipStream_t st, std::string& err) {
+  if (h.n == 0) return FAC_OK;
+  const GraphemeTable& t = e.gid_tab;
+  if (h.ascii || !t.d_slots || !e.d_ascii_gid || !h.d_off || !d_ids) {
+    err = "internal: grapheme_ids_device needs staged Unicode text and an engine with mappings";
+    return FAC_E_INTERNAL;
+  }
+  const uint64_t blocks = (h.n + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) {
+    err = "a batch's non-ASCII documents hold fewer than 2^39 graphemes";
+    return FAC_E_UNSUPPORTED;
+  }
+  BmpTabs tabs;
+  if (int trc = bmp_tables(h.device, st, tabs, err)) return trc;
+  const int lds = (t.mask < kGtSlotsLds && t.n_keys <= kGtKeysLds && t.n_pool <= kGtPoolLds) ? 1 : 0;
+  const int ci = e.case_insensitive ? 1 : 0;
+  if (h.d_doc_off)
+    hipLaunchKernelGGL(batch_grapheme_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n,
+                       h.d_doc_off, h.n_docs, tabs.l, ci, t.d_slots, t.d_ents, t.d_pool, t.mask, t.n_keys, t.n_pool, lds,
+                       e.d_ascii_gid, d_ids);
+  else
+    hipLaunchKernelGGL(grapheme_ids_kernel, dim3((uint32_t)blocks), dim3(256), 0, st, h.d_utf8, h.len, h.d_off, h.n,
+                       (uint64_t)0, h.n, tabs.l, ci, t.d_slots, t.d_ents, t.d_pool, t.mask, t.n_keys, t.n_pool, lds,
+                       e.d_ascii_gid, d_ids);
   HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
@@ -1258,6 +1327,12 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
     h.utf8.clear();
     h.starts.clear();
   }
+  {  // the grapheme ids of the text staged before are stale (the array is kept: ensure_gids)
+    std::lock_guard<std::mutex> lk(h.gid_mu);
+    h.gid_engine = nullptr;
+  }
+  h.d_doc_off = nullptr;
+  h.n_docs = 0;
   if (nd == 0) return FAC_OK;
   // flags | tri_in | tri_ex | scal
   const size_t tri_b = (nd + 1) * sizeof(BatchTri), flag_b = (nd * 4 + 15) & ~size_t(15);
@@ -1331,6 +1406,8 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   }
   h.ascii = !(sc[0] & 2ull);
   h.n = tot.u;
+  h.d_doc_off = b.d_offsets;
+  h.n_docs = nd;
   if (!h.ascii) {
     if (h.off_cap < h.n + 1) {
       if (h.d_off) HIP_TRY(hipFree(h.d_off));

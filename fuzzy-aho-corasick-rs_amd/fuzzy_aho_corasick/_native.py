@@ -231,6 +231,12 @@ SIGNATURES = {
     "fac_batch_free": (None, [ctypes.c_void_p]),
     "fac_batch_docs": (ctypes.c_uint64, [ctypes.c_void_p]),
     "fac_batch_allow_unicode_prefilter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "fac_batch_allow_unicode_mappings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "fac_batch_grapheme_ids": (ctypes.c_int64, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint64]),
+    "fac_haystack_grapheme_ids": (ctypes.c_int64, [_engine_p, _hay_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint64]),
+    "fac_engine_grapheme_id": (ctypes.c_uint32, [_engine_p, ctypes.c_char_p, ctypes.c_uint64]),
     "fac_batch_doc_graphemes": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_int32)]),
     "fac_batch_grapheme_starts": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _u64p, ctypes.c_uint64]),
     "fac_batch_text_chars": (ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint64, _P(ctypes.c_uint32), ctypes.c_uint64]),

@@ -179,6 +179,12 @@ class FuzzyAhoCorasick:
     def max_edits_fast(self) -> int:
         return int(_native.lib.fac_engine_max_edits_fast(self._h))
 
+    def grapheme_id(self, grapheme: str) -> int:
+        """fac_engine_grapheme_id: the id of one grapheme in the dictionary of an engine with
+        multi-character mappings, folded and looked up on the host; 0 = not in it (or no mappings)."""
+        raw = grapheme.encode("utf-8")
+        return int(_native.lib.fac_engine_grapheme_id(self._h, raw, len(raw)))
+
     def max_match_graphemes(self) -> int:
         """stream.rs:213-253"""
         return int(_native.lib.fac_max_match_graphemes(self._h))
@@ -373,16 +379,19 @@ class FuzzyAhoCorasick:
         return StagedHaystack(self, haystack)
 
     # -- many independent haystacks in one device pass (fac_search_batch)
-    def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None) -> List[FuzzyMatches]:
+    def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None,
+                     unicode_mappings: bool = False) -> List[FuzzyMatches]:
         """`[self.search(h, opts) for h in haystacks]` as one call: every haystack is staged, searched
         and ranked as a text of its own (the crate has no such entry point; its answer to many
         documents is one engine shared by threads). Errors name the first offending document
-        (`.doc` of the exception)."""
+        (`.doc` of the exception). `unicode_mappings` (here and in the other batch calls): an engine
+        with multi-character mappings takes non-ASCII haystacks too (StagedBatch.allow_unicode_mappings;
+        default off: such a batch raises UnsupportedConfiguration)."""
         opts = opts or SearchOptions()
         haystacks = list(haystacks)
         enc = [h.encode("utf-8") for h in haystacks]
         data, offsets = batch_offsets(enc)
-        recs, doc_off = StagedBatch(self, data, offsets).search_records(opts)
+        recs, doc_off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings).search_records(opts)
         out = []
         for d, (hay, raw) in enumerate(zip(haystacks, enc)):
             rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
@@ -391,7 +400,8 @@ class FuzzyAhoCorasick:
             out.append(self._to_matches(hay, raw, rows))
         return out
 
-    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements) -> List[str]:
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements,
+                      unicode_mappings: bool = False) -> List[str]:
         """`[self.replace(t, opts, lambda m: replacements[m.pattern_index]) for t in texts]` as one
         call (fac_replace_batch): searched, ranked and spliced on the device. `replacements` has one
         entry per pattern, `None` = keep the matched text (the callback's None, matches.rs:180-183).
@@ -401,10 +411,11 @@ class FuzzyAhoCorasick:
         enc = [t.encode("utf-8") for t in texts]
         data, offsets = batch_offsets(enc)
         table = replacements if isinstance(replacements, ReplacementTable) else ReplacementTable(self, replacements)
-        out, off = StagedBatch(self, data, offsets).replace_bytes(table, opts)
+        out, off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings).replace_bytes(table, opts)
         return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
-    def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None) -> List[List[str]]:
+    def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None,
+                      unicode_mappings: bool = False) -> List[List[str]]:
         """Per text, one string per match of `self.search(t, opts)`, in its order, as one call
         (fac_extract_batch): the matched text, or with `replacements` (one entry per pattern, or a
         ReplacementTable) what replace would put in its place -- the entry, `Wrap` rendered around
@@ -412,34 +423,37 @@ class FuzzyAhoCorasick:
         table = replacements
         if replacements is not None and not isinstance(replacements, ReplacementTable):
             table = ReplacementTable(self, replacements)
-        return _extract_batch(self, [t.encode("utf-8") for t in texts], opts or SearchOptions(), table, False)
+        return _extract_batch(self, [t.encode("utf-8") for t in texts], opts or SearchOptions(), table, False,
+                              unicode_mappings)
 
-    def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None) -> List[List[str]]:
+    def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None,
+                              unicode_mappings: bool = False) -> List[List[str]]:
         """`[self.search(t, opts).matched_strings() for t in texts]` as one call (matches.rs:513-515)."""
-        return self.extract_batch(texts, opts)
+        return self.extract_batch(texts, opts, unicode_mappings=unicode_mappings)
 
     # -- the other segmentation helpers of a whole batch (fac_render_batch, fac_segment_batch): each is
     # one device call; whitespace is Rust's char::is_whitespace (DESIGN.md 6a "Batched segmentation")
-    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[str]:
         """`[self.strip_prefix(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_PREFIX, opts, False)
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_PREFIX, opts, False, unicode_mappings)
 
-    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[str]:
         """`[self.strip_suffix(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, False)
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, False, unicode_mappings)
 
-    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[str]:
         """`[self.segment_text(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, False)
+        return _render_batch(self, texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, False, unicode_mappings)
 
-    def segment_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[Segment]]:
+    def segment_batch(self, texts: Sequence[str], opts: SearchOptions,
+                      unicode_mappings: bool = False) -> List[List[Segment]]:
         """`[list(self.segment_iter(t, opts)) for t in texts]` as one call."""
-        return _segment_batch(self, texts, opts, False)
+        return _segment_batch(self, texts, opts, False, unicode_mappings)
 
-    def split_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[str]]:
+    def split_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[List[str]]:
         """`[list(self.split(t, opts)) for t in texts]` as one call."""
         return [[s.unmatched().text for s in segs if s.unmatched() is not None]
-                for segs in _segment_batch(self, texts, opts, False)]
+                for segs in _segment_batch(self, texts, opts, False, unicode_mappings)]
 
 
 class Prefiltered:
@@ -477,9 +491,10 @@ class Prefiltered:
 
     def _batch_parts(self, enc):
         """Indices of the documents one pre-filtered batch takes: all of them where the filter is
-        active and the engine has no mappings (the batch is opted in, allow_unicode_prefilter), else
-        the ASCII ones (the others go through `search` one by one)."""
-        if self.is_active() and not self.engine.builder._mappings:
+        active or the engine has mappings (the batch is opted in, allow_unicode_prefilter and
+        allow_unicode_mappings; an engine with mappings has no filter and takes the plain batch call),
+        else the ASCII ones (the others go through `search` one by one)."""
+        if self.is_active() or self.engine.builder._mappings:
             return list(range(len(enc)))
         return [d for d, raw in enumerate(enc) if raw.isascii()]
 
@@ -494,7 +509,7 @@ class Prefiltered:
         idx = self._batch_parts(enc)
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
-            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True)
+            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True)
             recs, doc_off = sb.search_records(opts, prefilter=True)
             for k, d in enumerate(idx):
                 rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
@@ -522,7 +537,7 @@ class Prefiltered:
             table = ReplacementTable(self.engine, reps) if idx else None
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
-            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True)
+            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True)
             buf, off = sb.replace_bytes(table, opts, prefilter=True)
             for k, d in enumerate(idx):
                 out[d] = buf[int(off[k]):int(off[k + 1])].decode("utf-8")
@@ -548,7 +563,7 @@ class Prefiltered:
             reps = None if replacements is None else list(replacements)
             table = ReplacementTable(self.engine, reps) if idx and reps is not None else None
         if idx:
-            for d, items in zip(idx, _extract_batch(self.engine, [enc[d] for d in idx], opts, table, True)):
+            for d, items in zip(idx, _extract_batch(self.engine, [enc[d] for d in idx], opts, table, True, True)):
                 out[d] = items
         for d, t in enumerate(texts):
             if out[d] is None:
@@ -573,7 +588,7 @@ class Prefiltered:
         out = [None] * len(texts)
         idx = self._batch_parts(enc)
         if idx:
-            for d, r in zip(idx, _render_batch(self.engine, [texts[d] for d in idx], mode, opts, True)):
+            for d, r in zip(idx, _render_batch(self.engine, [texts[d] for d in idx], mode, opts, True, True)):
                 out[d] = r
         for d, t in enumerate(texts):
             if out[d] is None:
@@ -597,7 +612,7 @@ class Prefiltered:
         out = [None] * len(texts)
         idx = self._batch_parts(enc)
         if idx:
-            for d, segs in zip(idx, _segment_batch(self.engine, [texts[d] for d in idx], opts, True)):
+            for d, segs in zip(idx, _segment_batch(self.engine, [texts[d] for d in idx], opts, True, True)):
                 out[d] = segs
         for d, t in enumerate(texts):
             if out[d] is None:
@@ -620,26 +635,29 @@ def _item_text(reps, m) -> str:
     return m.text if r is None else r
 
 
-def _extract_batch(engine: "FuzzyAhoCorasick", enc, opts: SearchOptions, table, prefilter: bool) -> List[List[str]]:
+def _extract_batch(engine: "FuzzyAhoCorasick", enc, opts: SearchOptions, table, prefilter: bool,
+                   unicode_mappings: bool = False) -> List[List[str]]:
     data, offsets = batch_offsets(enc)
-    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings)
     _, doc_off, text, item_off = sb.extract(table, opts, prefilter=prefilter)
     return [[text[int(item_off[i]):int(item_off[i + 1])].decode("utf-8")
              for i in range(int(doc_off[d]), int(doc_off[d + 1]))] for d in range(len(enc))]
 
 
-def _render_batch(engine: "FuzzyAhoCorasick", texts, mode: int, opts: SearchOptions, prefilter: bool) -> List[str]:
+def _render_batch(engine: "FuzzyAhoCorasick", texts, mode: int, opts: SearchOptions, prefilter: bool,
+                  unicode_mappings: bool = False) -> List[str]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
-    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings)
     out, off = sb.render_bytes(mode, opts, prefilter=prefilter)
     return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
 
-def _segment_batch(engine: "FuzzyAhoCorasick", texts, opts: SearchOptions, prefilter: bool) -> List[List[Segment]]:
+def _segment_batch(engine: "FuzzyAhoCorasick", texts, opts: SearchOptions, prefilter: bool,
+                   unicode_mappings: bool = False) -> List[List[Segment]]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
-    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings)
     recs, doc_off = sb.segment_records(opts, prefilter=prefilter)
     out = []
     for d, raw in enumerate(enc):
@@ -942,6 +960,21 @@ class StagedHaystack:
             _raise(int(-n))
         return out[: int(n)]
 
+    def grapheme_ids(self, stream=None, engine=None):
+        """fac_haystack_grapheme_ids: the id in the grapheme dictionary of `engine` (default: the
+        haystack's; 0 = not in it) of every staged grapheme of a Unicode haystack, looked up on the
+        device, as a NumPy uint32 array (empty for an ASCII haystack); None when the engine has no
+        mappings."""
+        import numpy as np
+        out = np.zeros(max(1, self.graphemes), dtype=np.uint32)
+        n = _native.lib.fac_haystack_grapheme_ids((engine or self.engine)._h, self._h, ctypes.c_void_p(stream or 0),
+                                                  ctypes.c_void_p(out.ctypes.data), self.graphemes)
+        if n == -1:
+            return None
+        if n < 0:
+            _raise(int(-n))
+        return out[: int(n)]
+
     def stream_window(self, g_begin: int, g_end: int, commit_bytes: int, base: int, threshold: float,
                       prefilter: bool, stream=None):
         """fac_stream_window_staged (stream.rs:262-297 window_matches on a device-resident window):
@@ -1127,7 +1160,8 @@ class StagedBatch:
     times: document d is data[offsets[d]:offsets[d + 1]], staged as if it were staged alone (UTF-8
     validity, is_ascii and grapheme segmentation per document)."""
 
-    def __init__(self, engine: FuzzyAhoCorasick, data: bytes, offsets, unicode_prefilter: bool = False):
+    def __init__(self, engine: FuzzyAhoCorasick, data: bytes, offsets, unicode_prefilter: bool = False,
+                 unicode_mappings: bool = False):
         import numpy as np
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
         if off.ndim != 1 or len(off) < 1:
@@ -1147,14 +1181,18 @@ class StagedBatch:
         self._dev_out = self._dev_doc = None
         if unicode_prefilter:
             self.allow_unicode_prefilter()
+        if unicode_mappings:
+            self.allow_unicode_mappings()
 
     @classmethod
     def from_device(cls, engine: FuzzyAhoCorasick, d_utf8: int, d_offsets: int, n_docs: int, total_len: int,
-                    stream=None, reuse: "StagedBatch" = None, unicode_prefilter: bool = False) -> "StagedBatch":
+                    stream=None, reuse: "StagedBatch" = None, unicode_prefilter: bool = False,
+                    unicode_mappings: bool = False) -> "StagedBatch":
         """fac_batch_stage_device: the bytes (`d_utf8`, total_len of them) and the n_docs + 1 uint64
         offsets (`d_offsets`) are device addresses, e.g. torch tensors' data_ptr() (borrowed: keep both
         alive). `reuse`: a batch staged this way before, restaged in place and returned (it keeps its
-        opt-in). `unicode_prefilter`: opt the batch in (allow_unicode_prefilter)."""
+        opt-ins). `unicode_prefilter`, `unicode_mappings`: opt the batch in (allow_unicode_prefilter,
+        allow_unicode_mappings)."""
         h = ctypes.c_void_p(reuse._h.value if reuse is not None else None)
         ed = ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
         eg = ctypes.c_uint64()
@@ -1173,6 +1211,8 @@ class StagedBatch:
         obj.n_docs = n_docs
         if unicode_prefilter:
             obj.allow_unicode_prefilter()
+        if unicode_mappings:
+            obj.allow_unicode_mappings()
         return obj
 
     def __del__(self):
@@ -1189,6 +1229,33 @@ class StagedBatch:
         if rc:
             _raise(rc)
         return self
+
+    def allow_unicode_mappings(self, on: bool = True) -> "StagedBatch":
+        """fac_batch_allow_unicode_mappings: an engine with multi-character mappings takes this batch
+        even if it holds non-ASCII documents (default off: every batch call raises
+        UnsupportedConfiguration for such a batch). Returns self."""
+        rc = _native.lib.fac_batch_allow_unicode_mappings(self._h, 1 if on else 0)
+        if rc:
+            _raise(rc)
+        return self
+
+    def grapheme_ids(self, stream=None, engine=None):
+        """fac_batch_grapheme_ids: the id in the grapheme dictionary of `engine` (default: the batch's;
+        0 = not in it) of every grapheme of the non-ASCII documents, in document order, looked up on the
+        device, as a NumPy uint32 array; None when the engine has no mappings."""
+        import numpy as np
+        eh = (engine or self.engine)._h
+        n = _native.lib.fac_batch_grapheme_ids(eh, self._h, ctypes.c_void_p(stream or 0), None, 0)
+        if n == -1:
+            return None
+        if n < 0:
+            _raise(int(-n))
+        out = np.zeros(max(1, int(n)), dtype=np.uint32)
+        n = _native.lib.fac_batch_grapheme_ids(eh, self._h, ctypes.c_void_p(stream or 0),
+                                               ctypes.c_void_p(out.ctypes.data), int(n))
+        if n < 0:
+            _raise(int(-n))
+        return out[: int(n)]
 
     def doc_graphemes(self, d: int) -> Tuple[int, bool]:
         """(grapheme count, is_ascii) of document d."""

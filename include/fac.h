@@ -215,6 +215,20 @@ uint64_t fac_haystack_text_chars(const fac_haystack* hay, uint32_t* out, uint64_
  * the error code. `stream` is a hipStream_t (NULL = the engine's stream). */
 int64_t fac_haystack_symbol_ids(const fac_engine* engine, const fac_haystack* hay, void* stream, uint8_t* out,
                                 uint64_t cap);
+/* Tests and hosts, engines with multi-character mappings: the id of one grapheme (its UTF-8 bytes)
+ * in the engine's dictionary of folded graphemes -- the patterns' and the mappings' haystack sides,
+ * 1-based in first-seen order; 0 = not in the dictionary, or the engine has no mappings. Computed on
+ * the host (the fold of grapheme.rs:61-63 and a hash-map lookup): the reference the device ids below
+ * are tested against. */
+uint32_t fac_engine_grapheme_id(const fac_engine* engine, const uint8_t* utf8, uint64_t len);
+/* Tests and hosts: that id for every grapheme of a staged Unicode haystack, as the search of an
+ * engine with mappings reads it: looked up on the device by the first search (or this call) after a
+ * staging and kept with the haystack for that engine. Writes up to `cap` ids to the host buffer `out`;
+ * returns the grapheme count, -1 if the engine has no mappings, or minus the error code. An ASCII
+ * haystack has no such array (its bytes index a 128-entry table): nothing is written and 0 is
+ * returned. `stream` is a hipStream_t (NULL = the engine's stream). */
+int64_t fac_haystack_grapheme_ids(const fac_engine* engine, const fac_haystack* hay, void* stream, uint32_t* out,
+                                  uint64_t cap);
 void fac_haystack_free(fac_haystack* hay);
 
 /* Search start windows [window_begin, window_end) of a staged haystack (window_end is clamped
@@ -369,8 +383,11 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  *
  * Limits of the implementation (FAC_E_UNSUPPORTED, never a partial result): at most 2^24
  * documents and fewer than 2^40 bytes in all (a record carries its document in bits 40..63 of
- * start / end while it is inside the library; the tag is cleared before records leave it), and no
- * engine with multi-character mappings when some document is not ASCII. Auto-beam engines read the
+ * start / end while it is inside the library; the tag is cleared before records leave it). An
+ * engine with multi-character mappings takes a batch that holds a non-ASCII document only when the
+ * batch is opted in with fac_batch_allow_unicode_mappings (the grapheme ids of those documents are
+ * then looked up on the device, each document's last grapheme ending at its document's end); without
+ * the opt-in such a call gives FAC_E_UNSUPPORTED with nothing written. Auto-beam engines read the
  * segment descriptors back and run the per-segment auto-beam loop of fac_search_staged on the host.
  * Batched replace is provided (fac_replace_batch below), and so are the other segmentation helpers:
  * segment_iter and split (fac_segment_batch), strip_prefix, strip_suffix and segment_text
@@ -418,6 +435,18 @@ uint64_t fac_batch_docs(const fac_batch* batch);
  * does no work; the flag survives a restage in place (fac_batch_stage_device with *batch set). Not
  * to be called concurrently with a search of the same batch. FAC_E_INVALID for NULL. */
 int fac_batch_allow_unicode_prefilter(fac_batch* batch, int32_t on);
+
+/* Opt-in (on != 0) or back out (0, the default): every batch call, plain or pre-filtered, of an
+ * engine with multi-character mappings takes this batch even if it holds non-ASCII documents (see
+ * "Limits of the implementation" above). Independent of fac_batch_allow_unicode_prefilter (an engine
+ * with mappings has no filter: its pre-filtered calls are the plain ones). Sets a flag and does no
+ * work; the flag survives a restage in place. Not to be called concurrently with a search of the
+ * same batch. FAC_E_INVALID for NULL. */
+int fac_batch_allow_unicode_mappings(fac_batch* batch, int32_t on);
+/* Tests and hosts: as fac_haystack_grapheme_ids for the graphemes of the batch's non-ASCII documents,
+ * in document order (fac_batch_doc_graphemes of those documents, concatenated). An all-ASCII batch
+ * writes nothing and returns 0. Needs no opt-in. */
+int64_t fac_batch_grapheme_ids(const fac_engine* engine, const fac_batch* batch, void* stream, uint32_t* out, uint64_t cap);
 
 /* Tests and hosts: document d's grapheme count, is_ascii, and document-relative grapheme byte
  * starts (writes up to `cap` entries, returns the count). */
