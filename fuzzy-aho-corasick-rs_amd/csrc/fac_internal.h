@@ -223,8 +223,8 @@ struct SearchParams {
   unsigned int* slot_ring;
   unsigned int* slot_ctr;
   uint32_t n_slots;
-  uint4* bsel;              // beamed engines: the beam selection's scratch (bsel_stride per slot)
-  uint32_t bsel_stride;
+  uint4* bsel;              // beamed engines: the beam selection's scratch (bsel_stride per slot). An HBM rung
+  uint32_t bsel_stride;     // (bfs_window_kernel_hbm): each slot's dedup table, ring, then that scratch
   uint32_t sel_limit;       // select.rs partition rounds before median_of_medians (16; tests lower it)
   int32_t beam_canonical;   // diagnostics (FAC_BEAM_CANONICAL): rounds 1-2's canonical tie rule
   fac_match* out;

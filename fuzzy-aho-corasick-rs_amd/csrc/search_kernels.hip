@@ -261,8 +261,13 @@ __device__ void emit_update(EmitList& L, uint32_t me_rel, uint32_t p, float sim,
 // writes the first bw states back to the ring. oracle/oracle.cpp (rsel) is the CPU restatement.
 //
 // Scratch per wave (uint4 units): A[QCAP], T[QCAP], W[48] (per 64 partition positions: the "is less"
-// mask as two words, then the exclusive prefix counts).
-__host__ __device__ constexpr uint32_t bsel_stride(uint32_t qcap) { return 2u * qcap + 48u; }
+// mask as two words, then the exclusive prefix counts). Rings past 4096 states (the HBM rungs) need
+// more than 64 such groups: W holds 2 * QCAP / 64 mask words, then QCAP / 64 counts.
+__host__ __device__ constexpr uint32_t bsel_stride(uint32_t qcap) {
+  return 2u * qcap + (qcap <= 4096u ? 48u : 3u * (qcap / 256u));
+}
+// word offset of the prefix counts inside W
+__host__ __device__ constexpr uint32_t bsel_woff(uint32_t qcap) { return qcap <= 4096u ? 128u : qcap / 32u; }
 
 __device__ __forceinline__ uint32_t sel_key(const uint4& s) { return total_order_key(__uint_as_float(s.z)); }
 
@@ -315,6 +320,64 @@ __device__ uint32_t sel_pivot(const uint4* v, uint32_t len) {
   return shfl_u32(p, 0);
 }
 
+// choose_pivot for slices past 32767 elements (the HBM rungs' rings): median3_rec is 4 or 5 levels
+// deep there (81 or 243 leaf triples). The tree's lower three levels are evaluated as in sel_pivot, one
+// 27-leaf subtree per turn; subtree t leaves its median with lane t, and the upper levels reduce those.
+__device__ uint32_t sel_pivot_big(const uint4* v, uint32_t len) {
+  const uint32_t lane = lane_id();
+  uint32_t s[7] = {len / 8, 0u, 0u, 0u, 0u, 0u, 0u};
+  uint32_t D = 0;
+  if (len >= 64)
+    while (D < 6 && s[D] >= 8) {  // median3_rec recurses while n * 8 >= 64 (len < 2^24: D <= 6)
+      s[D + 1] = s[D] / 8;
+      ++D;
+    }
+  const uint32_t Dl = min(D, 3u), Du = D - Dl;  // levels inside a subtree, above the subtrees
+  uint32_t nsub = 1, nleaf = 1;
+  for (uint32_t d = 0; d < Du; ++d) nsub *= 3;  // <= 27
+  for (uint32_t d = 0; d < Dl; ++d) nleaf *= 3;
+  auto reduce3 = [&](uint32_t n, uint32_t& p, uint32_t& k) {  // lane g takes lanes 3g, 3g + 1, 3g + 2
+    for (; n > 1; n /= 3) {
+      const int b = (int)(3u * lane) & 63;
+      const uint32_t pa = (uint32_t)__shfl((int)p, b), ka = (uint32_t)__shfl((int)k, b);
+      const uint32_t pb = (uint32_t)__shfl((int)p, (b + 1) & 63), kb = (uint32_t)__shfl((int)k, (b + 1) & 63);
+      const uint32_t pc = (uint32_t)__shfl((int)p, (b + 2) & 63), kc = (uint32_t)__shfl((int)k, (b + 2) & 63);
+      if (lane < n / 3) sel_median3(pa, ka, pb, kb, pc, kc, p, k);
+    }
+  };
+  uint32_t P = 0, K = 0;  // lane t: subtree t's median
+  for (uint32_t t = 0; t < nsub; ++t) {
+    uint32_t base = 0, rem = t, div = nsub;
+    for (uint32_t d = 0; d < Du; ++d) {  // the subtree's digits, most significant first
+      div /= 3;
+      const uint32_t dig = rem / div;
+      rem -= dig * div;
+      base += (dig == 0 ? 0u : dig == 1 ? 4u : 7u) * s[d];
+    }
+    uint32_t p = 0, k = 0;
+    if (lane < nleaf) {
+      rem = lane;
+      div = nleaf;
+      for (uint32_t d = Du; d < D; ++d) {
+        div /= 3;
+        const uint32_t dig = rem / div;
+        rem -= dig * div;
+        base += (dig == 0 ? 0u : dig == 1 ? 4u : 7u) * s[d];
+      }
+      const uint32_t pa = base, pb = base + 4u * s[D], pc = base + 7u * s[D];
+      sel_median3(pa, sel_key(v[pa]), pb, sel_key(v[pb]), pc, sel_key(v[pc]), p, k);
+    }
+    reduce3(nleaf, p, k);
+    const uint32_t p0 = shfl_u32(p, 0), k0 = shfl_u32(k, 0);
+    if (lane == t) {
+      P = p0;
+      K = k0;
+    }
+  }
+  reduce3(nsub, P, K);
+  return shfl_u32(P, 0);
+}
+
 // partition (quicksort.rs) of v[0..len) around v[pp] with is_less (le: a <= pivot), through T;
 // returns num_lt. swap(v[0], v[pp]), then partition_lomuto_branchless_cyclic over w = v[1..len): it
 // takes w[1], ..., w[m-1], then w[0] (r = 1..m: e_r) and writes each to w[num_lt], moving the previous
@@ -324,6 +387,7 @@ __device__ uint32_t sel_pivot(const uint4* v, uint32_t len) {
 //   * w[p] for p >= F: e_m if p == F and e_m is not lt; else follow r = p + 1: while e_{r-1} is lt,
 //     r = L_r + 1; then e_{r-1};
 // then swap(v[0], v[F]): w[F-1] goes to v[0], the pivot to v[F], every other w[p] to v[p + 1].
+template <uint32_t WOFF = 128u>
 __device__ uint32_t sel_partition(uint4* v, uint4* T, uint32_t* W, uint32_t len, uint32_t pp, bool le) {
   const uint32_t lane = lane_id();
   const uint32_t m = len - 1;
@@ -348,7 +412,7 @@ __device__ uint32_t sel_partition(uint4* v, uint4* T, uint32_t* W, uint32_t len,
     if (lane == 0) {
       W[2u * c] = (uint32_t)mk;
       W[2u * c + 1u] = (uint32_t)(mk >> 32);
-      W[128u + c] = F;
+      W[WOFF + c] = F;
     }
     if (lt) T[F + prefix_below(mk) + 1u] = e;  // w position L_r, v position + 1 (fixed below for F - 1)
     F += (uint32_t)__popcll(mk);
@@ -362,7 +426,7 @@ __device__ uint32_t sel_partition(uint4* v, uint4* T, uint32_t* W, uint32_t len,
   auto lcount = [&](uint32_t r) -> uint32_t {  // L_r: lt elements among e_1 .. e_{r-1}
     const uint32_t b = r - 1u, c = b >> 6, o = b & 63u;
     const uint64_t mk = ((uint64_t)W[2u * c + 1u] << 32) | W[2u * c];
-    return W[128u + c] + (uint32_t)__popcll(mk & ((1ull << o) - 1ull));
+    return W[WOFF + c] + (uint32_t)__popcll(mk & ((1ull << o) - 1ull));
   };
   const bool lt_m = m ? bit(m - 1u) : false;
   for (uint32_t p = F + lane; p < m; p += 64u) {
@@ -600,10 +664,12 @@ __device__ FAC_SEL_ATTR void beam_select(KState* q, uint32_t head, uint32_t tail
       break;
     }
     --limit;
-    const uint32_t pp = sel_pivot(A + a, len);
+    uint32_t pp;
+    if constexpr (QCAP <= 4096) pp = sel_pivot(A + a, len);
+    else pp = len < 32768u ? sel_pivot(A + a, len) : sel_pivot_big(A + a, len);
     const uint32_t pk = sel_key(A[a + pp]);
     if (has_anc && !(anc < pk)) {  // pivot equal to the ancestor pivot: split off the equal run
-      const uint32_t mid = sel_partition(A + a, T + a, W, len, pp, true) + 1u;
+      const uint32_t mid = sel_partition<bsel_woff(QCAP)>(A + a, T + a, W, len, pp, true) + 1u;
       if (index < mid) break;  // core: `if mid > index { return; }`
       a += mid;
       len -= mid;
@@ -611,7 +677,7 @@ __device__ FAC_SEL_ATTR void beam_select(KState* q, uint32_t head, uint32_t tail
       has_anc = false;
       continue;
     }
-    const uint32_t mid = sel_partition(A + a, T + a, W, len, pp, false);
+    const uint32_t mid = sel_partition<bsel_woff(QCAP)>(A + a, T + a, W, len, pp, false);
     if (mid < index) {
       has_anc = true;
       anc = pk;
@@ -930,12 +996,24 @@ __device__ __forceinline__ uint32_t vis_hash(const KState& s) {
   return h;
 }
 
+// The frontier of an HBM rung (bfs_window_kernel_hbm) lives in global memory. Where the LDS rungs
+// order one lane's ring or table store against another lane's load with a wave barrier alone, a
+// frontier in global memory also needs the stores to have completed: the workgroup-scope fence that
+// EmitList and the beam selection's scratch already use. HBM = false is the wave barrier as before.
+template <bool HBM>
+__device__ __forceinline__ void frontier_sync() {
+  if constexpr (HBM) wave_mem_fence();
+  __builtin_amdgcn_wave_barrier();
+}
+
 // State dedup (search.rs:608-628). Returns true when the state must be skipped.
-template <uint32_t VCAP>
+// HBM: the previous call's (or the parallel commit's) insert is fenced before this call's probe.
+template <uint32_t VCAP, bool HBM = false>
 __device__ __forceinline__ bool visited_check(KState* vis, uint32_t& vcount, const KState& s, bool exact_needed,
                                               unsigned& err) {
   const uint32_t lane = lane_id();
   const uint32_t h = vis_hash(s);
+  if constexpr (HBM) wave_mem_fence();
   for (uint32_t probe = 0; probe < VCAP; probe += 64) {
     const uint32_t slot = (h + probe + lane) & (VCAP - 1);
     const KState e = vis[slot];
@@ -1681,6 +1759,11 @@ __device__ __forceinline__ fac_match match_record(const SearchParams& P, const S
 }
 
 constexpr uint32_t claim_slots(uint32_t vcap) { return vcap / 2 < 512 ? 512 : vcap / 2; }  // >= ExpScratch
+// HBM rungs: the table is in global memory and far larger than LDS, the claim words stay in LDS at a
+// fixed size (8 KB). A batch claims at most 64 slots, so 2048 words keep sharing rare.
+constexpr uint32_t HBM_CLAIM_WORDS = 2048;
+template <uint32_t VCAP, bool HBM>
+constexpr uint32_t claim_words() { return HBM ? HBM_CLAIM_WORDS : claim_slots(VCAP); }
 
 __device__ unsigned long long g_live_dbg[12];  // diagnostics (FAC_RC_DEBUG): live-dedup checks / hits, spills
 __device__ unsigned long long g_bad[8];       // diagnostics (FAC_RC_DEBUG): uncached keys by reason
@@ -1738,8 +1821,10 @@ __global__ void slot_init_kernel(unsigned int* ring, unsigned int* ctr, uint32_t
 // stored penalty <= its own is skipped as the reference's visited map would (search.rs:618-622): the
 // window itself runs dedup-free, which cannot change results while no beam triggers -- except against
 // states popped before the snapshot, whose subtrees a beam may have pruned (live_dup).
+// HBM (the HBM rungs): vis and q point into the wave slot's global scratch region; every exchange of
+// ring or table data between lanes is fenced (frontier_sync), claim has HBM_CLAIM_WORDS.
 constexpr uint32_t LIVE_CAP = 256;
-template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LIVE = false>
+template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LIVE = false, bool HBM = false>
 __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegDesc& S, KState* vis, KState* q, uint32_t* claim,
                            uint32_t& cseq, EmitList& EL, uint64_t start, const RcHit& rc, uint64_t& popped,
                            uint64_t& cached, unsigned& err, uint32_t& head_out, uint32_t& vcount_out,
@@ -1793,7 +1878,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
     head = rc.head;
     tail = rc.tail;
     const uint32_t nq = tail - head, nv = rc.nv_nel & 0xFFFFu, ne = rc.nv_nel >> 16, nw = nq + nv + ne;
-    if constexpr (VCAP > 0) __builtin_amdgcn_wave_barrier();  // the table clear above
+    if constexpr (VCAP > 0) frontier_sync<HBM>();  // the table clear above
     for (uint32_t b = 0; b < nw; b += 256) {  // four loads in flight per lane, then their stores
       uint4 w[4];
 #pragma unroll
@@ -1829,7 +1914,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
   } else if (lane == 0) {
     q[0] = KState{0u, 0u, 0.0f, 0u};
   }
-  __builtin_amdgcn_wave_barrier();
+  frontier_sync<HBM>();  // the table clear, the snapshot's ring and table entries, the root
   const uint32_t beam2 = 2u * P.beam;
   PROF_ACC(38, t_load);
   PROF_ACC(20, t_win);
@@ -1840,7 +1925,10 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       if (P.beam && tail - head > beam2) {
         // (tail by value: a reference into these noinline calls kept it in scratch memory for the whole
         // window loop, reloaded with a full vmcnt wait wherever it was read)
-        if (P.beam_canonical) beam_select_canonical<QCAP>(q, head, tail, P.beam);  // diagnostics
+        if constexpr (HBM) {  // (no canonical rule here: its keys are QCAP / 64 registers per lane)
+          beam_select<QCAP>(q, head, tail, P.beam, bsel, P.sel_limit);
+          wave_mem_fence();  // the survivors written back to the ring, before the next pop
+        } else if (P.beam_canonical) beam_select_canonical<QCAP>(q, head, tail, P.beam);  // diagnostics
         else if constexpr (QCAP <= 256) beam_select_lds<QCAP>(q, head, tail, P.beam, claim, P.sel_limit);  // :577-589
         else beam_select<QCAP>(q, head, tail, P.beam, bsel, P.sel_limit);
         tail = head + P.beam;  // truncate(bw) (:587)
@@ -1945,10 +2033,11 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       popped += 1;
       if (track_beam) jp1 = max(jp1, (s0.jm & 0xFFFFu) + 1u);
       if constexpr (VCAP > 0)
-        if (visited_check<VCAP>(vis, vcount, s0, P.exact_dedup != 0, err)) continue;
+        if (visited_check<VCAP, HBM>(vis, vcount, s0, P.exact_dedup != 0, err)) continue;
       const DevNode n0 = P.nodes[s0.node];
       if (node_has_out(n0)) emit_state(P, EL, s0.jm >> 16, s0.pen, s0.packed, s0.node, err);
       expand_wide<QCAP, MAP>(P, S, q, head, tail, s0, n0, start, err);
+      if constexpr (HBM) wave_mem_fence();  // its table insert and push_lanes' ring stores, before the next pop
       PROF_ACC(2, t2);
       if (any_err(err)) break;
       continue;
@@ -2058,13 +2147,16 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       const bool wr = lane < Bc && !skip;
       cseq += 1;
       if (cseq >= (1u << 26)) {  // sequence wrap: forget all claims
-        for (uint32_t i = lane; i < claim_slots(VCAP); i += 64) claim[i] = 0u;
+        for (uint32_t i = lane; i < claim_words<VCAP, HBM>(); i += 64) claim[i] = 0u;
         __builtin_amdgcn_wave_barrier();
         cseq = 2;
       }
       // claims are hashed to VCAP/2 words: lanes of different slots may share one (then they are
-      // "losers" with distinct keys and take the serial insert, which also handles found keys)
-      const uint32_t cs = vslot & (claim_slots(VCAP) - 1);
+      // "losers" with distinct keys and take the serial insert, which also handles found keys).
+      // That holds for any number of slots per word (HBM rungs: HBM_CLAIM_WORDS for the whole table):
+      // equal keys found the same slot in phase A, hence the same word, so a loser's key differs from
+      // every winner's, and the losers insert one at a time in lane order after the winners.
+      const uint32_t cs = vslot & (claim_words<VCAP, HBM>() - 1);
       if (wr && vslot != EMPTY) atomicMax(&claim[cs], (cseq << 6) | (63u - lane));
       __builtin_amdgcn_wave_barrier();
       const uint32_t w = (wr && vslot != EMPTY) ? 63u - (claim[cs] & 63u) : lane;
@@ -2119,6 +2211,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
         while (dl) {
           const int l = first_lane(dl);
           dl &= dl - 1;
+          if constexpr (HBM) wave_mem_fence();  // after the winner's (the earlier duplicate's) store to this entry
           if (lane == (uint32_t)l) vis[vslot].pen = st.pen;
           __builtin_amdgcn_wave_barrier();
         }
@@ -2131,7 +2224,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
           kt.jm = shfl_u32(st.jm, l);
           kt.pen = shfl_f32(st.pen, l);
           kt.packed = shfl_u32(st.packed, l);
-          if (visited_check<VCAP>(vis, vcount, kt, P.exact_dedup != 0, err)) nskip |= 1ull << l;  // a loser's duplicate
+          if (visited_check<VCAP, HBM>(vis, vcount, kt, P.exact_dedup != 0, err)) nskip |= 1ull << l;  // a loser's duplicate
         }
       } else {  // near-full table: the reference order, one state at a time
         nskip = 0;
@@ -2143,10 +2236,10 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
           kt.jm = shfl_u32(st.jm, t);
           kt.pen = shfl_f32(st.pen, t);
           kt.packed = shfl_u32(st.packed, t);
-          if (visited_check<VCAP>(vis, vcount, kt, P.exact_dedup != 0, err)) nskip |= 1ull << t;
+          if (visited_check<VCAP, HBM>(vis, vcount, kt, P.exact_dedup != 0, err)) nskip |= 1ull << t;
         }
       }
-      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_wave_barrier();  // (HBM: the commit's table stores are fenced with the pushes below)
     }
     PROF_ACC(4, t4);
     PROF_T(t5);
@@ -2171,7 +2264,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
     push_units<QCAP, FAC_UK, MAP>(P, reinterpret_cast<ExpScratch*>(claim), q, opq(tail + excl2), st, nd, x, opq(pr.cur_ch),
                              keep && x.count != 0);  // same entries rewritten
 #endif
-    __builtin_amdgcn_wave_barrier();
+    frontier_sync<HBM>();  // this batch's pushes and table commit, before the next batch's pops and probes
     tail += shfl_u32(incl2, Bc - 1);
     if (track_beam && lane < Bc) jp1 = max(jp1, (st.jm & 0xFFFFu) + 1u);
     head += Bc;
@@ -3667,12 +3760,17 @@ __global__ __launch_bounds__(64) void lane_window_kernel(SearchParams P) {
 
 // LK: the window prologue looks snapshots up itself (cache builds); otherwise a main pass with the
 // prefix cache reads the hits rc_lookup_kernel stored.
-template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LK, bool LIVE = false>
+// HBM (the HBM rungs, bfs_window_kernel_hbm): the table and the ring are the wave slot's region of
+// P.bsel instead of LDS -- VCAP table entries, QCAP ring entries, then (beamed engines) the beam
+// selection's scratch, P.bsel_stride uint4 per slot. The launch has at most n_slots workgroups, so
+// slot_acquire never waits. Only the claim words (HBM_CLAIM_WORDS) stay in LDS.
+template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LK, bool LIVE = false, bool HBM = false>
 __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
-  __shared__ KState s_vis[VCAP ? VCAP : 1];
+  static_assert(!HBM || (!LK && !LIVE && VCAP > 0), "HBM rungs: main passes with a table only");
+  __shared__ KState s_vis[(VCAP && !HBM) ? VCAP : 1];
   __shared__ KState s_live[LIVE ? LIVE_CAP : 1];
-  __shared__ KState s_q[QCAP];
-  __shared__ __attribute__((aligned(16))) uint32_t s_claim[claim_slots(VCAP)];
+  __shared__ KState s_q[HBM ? 1 : QCAP];
+  __shared__ __attribute__((aligned(16))) uint32_t s_claim[claim_words<VCAP, HBM>()];
   const uint32_t lane = lane_id();
 #ifdef FAC_PHASE_PROF
   const uint64_t t_life = __builtin_amdgcn_s_memtime();
@@ -3682,6 +3780,13 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
   const uint32_t slot = slot_acquire(P);
   EmitList EL{P.ebuf + (size_t)slot * P.ecap, P.ecap, 0};
   uint4* bsel = (VCAP > 0 && P.bsel) ? P.bsel + (size_t)slot * P.bsel_stride : nullptr;
+  KState* w_vis = s_vis;  // the window's table and ring
+  KState* w_q = s_q;
+  if constexpr (HBM) {
+    w_vis = reinterpret_cast<KState*>(bsel);
+    w_q = w_vis + VCAP;
+    bsel += (size_t)VCAP + QCAP;
+  }
   uint64_t popped = 0, cached = 0;     // wave-uniform
   uint64_t cached_lane = 0;            // per lane: lane-flushed windows' snapshot pops
   unsigned long long pool_cur = 0, pool_end = 0;  // cache build: this wave's snapshot pool chunk
@@ -3690,7 +3795,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
   // dedup-commit claim sequence (phase C): fresh claims are >= 128, above any stale word the
   // expansion scratch leaves behind (<= 64)
   uint32_t cseq = 1;
-  for (uint32_t i = lane_id(); i < claim_slots(VCAP); i += 64) s_claim[i] = 0u;
+  for (uint32_t i = lane_id(); i < claim_words<VCAP, HBM>(); i += 64) s_claim[i] = 0u;
   __builtin_amdgcn_wave_barrier();
   unsigned err = 0;
   // chunks are handed out by a global work counter (counters[7]): waves that become resident late,
@@ -3799,8 +3904,8 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
         const uint64_t t_w0 = __builtin_amdgcn_s_memtime();
 #endif
         const uint32_t qlen =
-            run_window<VCAP, QCAP, MAP, LIVE>(P, S, s_vis, s_q, s_claim, cseq, EL, st, rc, popped, cached, err, qhead,
-                                              vcnt, s_live, jbeam, bsel
+            run_window<VCAP, QCAP, MAP, LIVE, HBM>(P, S, w_vis, w_q, s_claim, cseq, EL, st, rc, popped, cached, err, qhead,
+                                                   vcnt, s_live, jbeam, bsel
 #ifdef FAC_PHASE_PROF
                                               , prof_acc
 #endif
@@ -3847,7 +3952,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
           // jbeam[0]: a live entry has j + 1 <= jlive, so that is j + 1 <= jcheck below). The writing
           // passes read from LDS again only the entries they store (held in registers, the 8 slots' 32
           // VGPRs made this the kernel's register peak and pushed loop state into scratch)
-          constexpr uint32_t NSL = VCAP ? VCAP / 64 : 1;
+          constexpr uint32_t NSL = (VCAP && !HBM) ? VCAP / 64 : 1;  // (cache builds never run on an HBM rung)
           uint32_t lmask = 0, cmask = 0;
           if (sweep) {
             for (uint32_t i = lane; i < nq; i += 64) jmin = min(jmin, s_q[(qhead + i) & (QCAP - 1)].jm & 0xFFFFu);
@@ -4008,6 +4113,12 @@ template <uint32_t QCAP, bool MAP>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QCAP <= 512 ? 4 : 1))) void bfs_window_kernel_nd(SearchParams P) {
   bfs_window_body<0, QCAP, MAP, false>(P);
 }
+// HBM rungs: a table and a ring of CAP states each in the wave slot's global scratch
+// region; 8 KB of LDS (the claim words), so residency is bounded by the slots the launcher hands out
+template <uint32_t CAP, bool MAP>
+__global__ __launch_bounds__(64) void bfs_window_kernel_hbm(SearchParams P) {
+  bfs_window_body<CAP, CAP, MAP, false, false, true>(P);
+}
 // dedup-free first pass of a beamed engine (launch_pass): windows that would beam are spilled, the
 // resumed snapshots' popped states still dedup (run_window LIVE)
 #ifndef FAC_LIVE_WAVES  // waves/SIMD bfs_window_kernel_live is compiled for (VGPR budget)
@@ -4027,6 +4138,7 @@ void rc_build_kernel(SearchParams P) {
 
 struct Variant {
   uint32_t vcap, qcap;  // vcap 0: no dedup table (unbeamed engines only)
+  bool hbm = false;     // table and ring in the wave slots' global scratch (hbm_scratch), not in LDS
 };
 
 // FAC_LDS_PAD (bytes of unused dynamic LDS per workgroup): occupancy experiments only
@@ -4055,9 +4167,18 @@ void launch_one(uint32_t grid, hipStream_t s, const SearchParams& P) {
   else hipLaunchKernelGGL((bfs_window_kernel<V, Q, false>), dim3(grid), dim3(64), lds_pad(), s, P);
 }
 
-// LDS per wave: 16 B x (vcap + qcap) + vcap claim bytes
+template <uint32_t CAP>
+void launch_hbm(uint32_t grid, hipStream_t s, const SearchParams& P) {
+  if (P.has_map) hipLaunchKernelGGL((bfs_window_kernel_hbm<CAP, true>), dim3(grid), dim3(64), 0, s, P);
+  else hipLaunchKernelGGL((bfs_window_kernel_hbm<CAP, false>), dim3(grid), dim3(64), 0, s, P);
+}
+
+// LDS per wave: 16 B x (vcap + qcap) + vcap claim bytes. The last kNumHbm rungs keep both in global
+// memory, 16 B x (vcap + qcap) per wave slot: they are tried after every LDS rung.
 constexpr Variant kVariants[] = {{0, 128},   {0, 256},   {0, 512},     {256, 256},   {512, 256},
-                                 {512, 512}, {1024, 1024}, {2048, 2048}, {4096, 4096}, {0, 8192}};
+                                 {512, 512}, {1024, 1024}, {2048, 2048}, {4096, 4096}, {0, 8192},
+                                 {1u << 14, 1u << 14, true}, {1u << 17, 1u << 17, true}, {1u << 20, 1u << 20, true}};
+constexpr size_t kNumHbm = 3;
 
 // cache-build ring: at least the root's pushes after the popped root and the main pass's ring
 bool launch_rc_build(uint32_t need_q, uint32_t grid, hipStream_t s, const SearchParams& P) {
@@ -4071,6 +4192,12 @@ bool launch_rc_build(uint32_t need_q, uint32_t grid, hipStream_t s, const Search
 }
 
 hipError_t launch_variant(const Variant& v, uint32_t grid, hipStream_t s, const SearchParams& P) {
+  if (v.hbm) {
+    if (v.qcap == (1u << 14)) launch_hbm<(1u << 14)>(grid, s, P);
+    else if (v.qcap == (1u << 17)) launch_hbm<(1u << 17)>(grid, s, P);
+    else launch_hbm<(1u << 20)>(grid, s, P);
+    return hipGetLastError();
+  }
   switch (v.vcap * 16384u + v.qcap) {
     case 0 * 16384u + 128: launch_nd<128>(grid, s, P); break;
     case 0 * 16384u + 256: launch_nd<256>(grid, s, P); break;
@@ -4214,6 +4341,13 @@ struct Ladder {  // fan_root, fan_nr: the most pushes of the root state, of any 
   bool exact_dedup;
 };
 constexpr size_t kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+constexpr size_t kNumLds = kNumVariants - kNumHbm;  // the LDS rungs come first
+// the first HBM rung tried holds at least this many states (FAC_HBM_CAP0: tests start on, and
+// escalate between, the larger rungs at small shapes; default: the smallest rung)
+uint32_t hbm_cap0() {
+  const char* e = diag_env("FAC_HBM_CAP0");
+  return e ? (uint32_t)std::min<unsigned long long>(kVariants[kNumVariants - 1].qcap, std::strtoull(e, nullptr, 10)) : 0u;
+}
 bool fits(const Ladder& L, const Variant& v) {
   if (L.beam) return v.vcap > 0 && L.fan_root + 1 <= v.qcap && 2ull * L.beam + L.fan_nr + 1 <= v.qcap;
   return (v.vcap > 0 || !L.exact_dedup) && L.fan_root + 1 <= v.qcap && L.fan_nr + 1 <= v.qcap;
@@ -4223,13 +4357,17 @@ size_t first_variant(const Ladder& L, bool bail_ok) {
   size_t vi = kNumVariants;
   // defaults (measured on MI355X): beamed -> 512-entry table + 256-entry ring
   // (12.8 KB LDS); unbeamed -> no table + 512-entry ring (a 128 ring cuts batches too often)
-  for (size_t i = 0; i < kNumVariants && vi == kNumVariants; ++i)
+  for (size_t i = 0; i < kNumLds && vi == kNumVariants; ++i)
     if (fits(L, kVariants[i]) && (L.beam          ? kVariants[i].vcap >= default_beam_vcap()
                                : L.exact_dedup ? kVariants[i].vcap >= 512 && kVariants[i].qcap >= 512
                                              : kVariants[i].vcap == 0 && kVariants[i].qcap >= 512))
       vi = i;
-  for (size_t i = 0; i < kNumVariants && vi == kNumVariants; ++i)
+  for (size_t i = 0; i < kNumLds && vi == kNumVariants; ++i)
     if (fits(L, kVariants[i])) vi = i;
+  // no LDS rung holds the beam or the widest node's pushes: the pass starts on an HBM rung (unless the
+  // dedup-free first pass below takes it, as it did before the HBM rungs: its spills then escalate here)
+  for (size_t i = kNumLds; i < kNumVariants && vi == kNumVariants; ++i)
+    if (fits(L, kVariants[i]) && kVariants[i].qcap >= hbm_cap0()) vi = i;
   // Beamed main passes start dedup-free (no table: more windows per CU, no dedup work) and spill the
   // windows whose pending count would pass 2·bw to the dedup variants (run_window).
   // Not for the auto-beam count pass (exact queue.len() per window) or mappings.
@@ -4246,12 +4384,15 @@ size_t first_variant(const Ladder& L, bool bail_ok) {
 }
 size_t escalate(const Ladder& L, size_t cur) {  // next variant for spilled windows (kNumVariants: none)
   const uint32_t want_v = std::max<uint32_t>(kVariants[cur].vcap * 2, 512);
-  for (size_t i = cur + 1; i < kNumVariants; ++i)
+  for (size_t i = cur + 1; i < kNumLds; ++i)
     if (fits(L, kVariants[i]) && kVariants[i].vcap >= want_v && kVariants[i].qcap >= kVariants[cur].qcap) return i;
   // past the largest table: an unbeamed, non-exact engine may still trade the table for a
   // longer ring (dedup never changes unbeamed results)
-  for (size_t i = cur + 1; i < kNumVariants; ++i)
+  for (size_t i = cur + 1; i < kNumLds; ++i)
     if (fits(L, kVariants[i]) && kVariants[i].vcap == 0 && kVariants[i].qcap > kVariants[cur].qcap) return i;
+  // past the LDS rungs, (4096, 4096) or (0, 8192): the HBM rungs, each to the next
+  for (size_t i = std::max(cur + 1, kNumLds); i < kNumVariants; ++i)
+    if (fits(L, kVariants[i]) && kVariants[i].qcap >= hbm_cap0() && kVariants[i].qcap > kVariants[cur].qcap) return i;
   return kNumVariants;
 }
 
@@ -4334,8 +4475,19 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   const uint64_t fan_nr = 3ull + e.max_map + 2ull * e.max_degree_nonroot;
   const Ladder ladder{fan_root, fan_nr, beam, exact_dedup};
   size_t vi = first_variant(ladder, !counts && !e.has_map);
-  if (vi == kNumVariants) {
-    err = "beam width too large for the on-chip frontier";
+  if (vi == kNumVariants) {  // not even the largest HBM rung's ring holds one state's pushes behind the beam
+    const uint32_t qmax = kVariants[kNumVariants - 1].qcap;
+    char msg[192];
+    if (fan_root + 1 > qmax)
+      std::snprintf(msg, sizeof(msg), "root fan-out too large for the frontier: %llu pushes, the largest ring holds %u states",
+                    (unsigned long long)fan_root, qmax);
+    else if (fan_nr + 1 > qmax)
+      std::snprintf(msg, sizeof(msg), "node fan-out too large for the frontier: %llu pushes, the largest ring holds %u states",
+                    (unsigned long long)fan_nr, qmax);
+    else
+      std::snprintf(msg, sizeof(msg), "beam width too large for the frontier: 2 x %u pending states and %llu pushes, the "
+                    "largest ring holds %u states", beam, (unsigned long long)fan_nr, qmax);
+    err = msg;
     return FAC_E_UNSUPPORTED;
   }
 
@@ -4350,6 +4502,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   DevBuf d_bhits, d_bpops; // prefix cache builds: the representatives' parent snapshots
   DevBuf d_slots, d_bsel;  // wave-slot rings (one per stream), beam-selection scratch
   DevBuf d_dense;          // the start level's dense key bitmaps
+  DevBuf d_hbm;            // HBM rungs: the wave slots' tables, rings and selection scratch (allocated on first use)
   ScratchSet* bound = t_scratch;  // a streaming worker's own set, else the engine's
   std::unique_lock<std::mutex> lease(bound ? bound->mu : e.scratch_mu, std::try_to_lock);
   void** scratch_p = bound ? bound->p : e.scratch_p;
@@ -4370,7 +4523,8 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     bufs.push_back(&d_bhits);
     bufs.push_back(&d_bpops);
     bufs.push_back(&d_dense);
-    static_assert(Engine::kScratch >= 31 + 5 * (kRcLevels - 1) + kRcLevels, "engine scratch slots");
+    bufs.push_back(&d_hbm);
+    static_assert(Engine::kScratch >= 32 + 5 * (kRcLevels - 1) + kRcLevels, "engine scratch slots");
     static_assert(ScratchSet::kSlots >= Engine::kScratch, "stream scratch slots");
     for (size_t i = 0; i < bufs.size(); ++i) bufs[i]->bind(&scratch_p[i], &scratch_n[i]);
   }
@@ -5136,12 +5290,47 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
         if (int drc = lane_debug_line(lms)) return drc;
       }
     }
-    if (int src = prep_slots(P, stream, kVariants[vi].qcap, kVariants[vi].vcap > 0)) {
+    if (int src = prep_slots(P, stream, kVariants[vi].qcap, kVariants[vi].vcap > 0 && !kVariants[vi].hbm)) {
       rc = src;
       break;
     }
+    uint32_t vgrid = grid;
+    if (kVariants[vi].hbm) {
+      // HBM rung: one scratch region per wave slot -- the table, the ring and (beamed) the selection's
+      // scratch -- handed to the kernel as P.bsel. As many slots as the budget holds (FAC_HBM_FRONTIER_MB,
+      // default 1 GiB) and the pass has chunks for; the grid is no larger, so no wave waits for a slot.
+      const Variant& v = kVariants[vi];
+      if (P.beam && P.beam_canonical) {  // diagnostics knob: these kernels have no canonical tie rule
+        err = "FAC_BEAM_CANONICAL is not available on the HBM frontier rungs";
+        rc = FAC_E_UNSUPPORTED;
+        break;
+      }
+      const uint64_t slot_u4 = (uint64_t)v.vcap + v.qcap + (P.beam ? bsel_stride(v.qcap) : 0u);
+      uint64_t budget_mb = 1024;
+      if (const char* mb = diag_env("FAC_HBM_FRONTIER_MB")) budget_mb = std::strtoull(mb, nullptr, 10);
+      // (the scratch pool allocates a quarter more than it is asked for: that headroom counts against the budget)
+      const uint64_t slot_b = slot_u4 * sizeof(uint4);
+      const uint64_t fit = (std::min<uint64_t>(budget_mb, 1ull << 24) << 20) / (slot_b + slot_b / 4);
+      if (fit == 0) {
+        char msg[256];
+        std::snprintf(msg, sizeof(msg), "per-window frontier needs the (%u, %u) HBM rung: one wave slot of %llu states takes "
+                      "%.1f MiB plus a quarter of headroom, the HBM frontier budget is %llu MiB", v.vcap, v.qcap, (unsigned long long)v.qcap,
+                      (double)(slot_u4 * sizeof(uint4)) / (1 << 20), (unsigned long long)budget_mb);
+        err = msg;
+        rc = FAC_E_CAPACITY;
+        break;
+      }
+      const uint32_t n_slots = (uint32_t)std::min<uint64_t>(fit, grid);
+      HIP_TRY(d_hbm.alloc((size_t)n_slots * slot_u4 * sizeof(uint4), stream));
+      P.bsel = static_cast<uint4*>(d_hbm.p);
+      P.bsel_stride = (uint32_t)slot_u4;
+      vgrid = n_slots;
+      if (diag_env("FAC_RC_DEBUG"))
+        std::fprintf(stderr, "FAC_HBM rung=%u,%u windows=%llu slots=%u\n", v.vcap, v.qcap, (unsigned long long)pass_windows,
+                     n_slots);
+    }
     HIP_TRY(hipEventRecord(ev.a, stream));
-    const hipError_t le = launch_variant(kVariants[vi], grid, stream, P);
+    const hipError_t le = launch_variant(kVariants[vi], vgrid, stream, P);
     if (le != hipSuccess) {
       err = std::string("kernel launch: ") + hipGetErrorString(le);
       rc = FAC_E_HIP;
@@ -5240,8 +5429,13 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     if (cnt[3] == 0) break;
     // windows that overflowed this variant's frontier: re-run just those on the next one
     const size_t nx = escalate(ladder, vi);
-    if (nx == kNumVariants) {
-      err = "per-window frontier exceeded the on-chip capacity";
+    if (nx == kNumVariants) {  // past the last rung that fits this engine (the largest HBM rung, unless its ring is too short)
+      char msg[224];
+      std::snprintf(msg, sizeof(msg), "per-window frontier exceeded the largest rung: %llu window(s) overflowed the %s of the "
+                    "(%u, %u) %s rung, which holds %u states", (unsigned long long)cnt[3],
+                    P.exact_dedup ? "dedup table or ring" : "ring", kVariants[vi].vcap, kVariants[vi].qcap,
+                    kVariants[vi].hbm ? "HBM" : "LDS", kVariants[vi].qcap);
+      err = msg;
       rc = FAC_E_CAPACITY;
       break;
     }
@@ -5435,11 +5629,32 @@ __global__ __launch_bounds__(64) void diag_select_kernel(const float* keys, cons
   for (uint32_t i = lane; i < bw; i += 64u) perm[(size_t)a * bw + i] = q[(head + i) & (QCAP - 1u)].node;
 }
 
+// lds == 2: the ring of the largest HBM rung, in global memory like the selection's scratch (the
+// selection as bfs_window_kernel_hbm runs it: W past 64 groups, sel_pivot_big from 32768 states on)
+constexpr uint32_t DIAG_HBM_RING = 1u << 20;
+constexpr uint64_t DIAG_HBM_REGION = (uint64_t)DIAG_HBM_RING + bsel_stride(DIAG_HBM_RING);  // uint4 per array
+__global__ __launch_bounds__(64) void diag_select_hbm_kernel(const float* keys, const uint64_t* offs, uint32_t bw,
+                                                             uint32_t limit, uint4* region, uint32_t* perm) {
+  constexpr uint32_t QCAP = DIAG_HBM_RING;
+  const uint32_t lane = lane_id();
+  const uint32_t a = blockIdx.x;
+  uint4* reg = region + (size_t)a * DIAG_HBM_REGION;
+  KState* q = reinterpret_cast<KState*>(reg);
+  const uint64_t b = offs[a], P = offs[a + 1] - b;
+  const uint32_t head = (a * 37u + QCAP - 5u) & (QCAP - 1u);  // (the first arrays wrap around the ring's end)
+  for (uint32_t i = lane; i < (uint32_t)P; i += 64u) q[(head + i) & (QCAP - 1u)] = KState{i, 0u, keys[b + i], 0u};
+  wave_mem_fence();
+  const uint32_t tail = head + (uint32_t)P;
+  beam_select<QCAP>(q, head, tail, bw, reg + QCAP, limit);
+  wave_mem_fence();
+  for (uint32_t i = lane; i < bw; i += 64u) perm[(size_t)a * bw + i] = q[(head + i) & (QCAP - 1u)].node;
+}
+
 int diag_beam_select(const float* keys, const uint64_t* offs, uint64_t count, uint32_t bw, int32_t lds,
                      int32_t sel_limit, uint32_t* perm, std::string& err) {
-  const uint32_t cap = lds ? 256u : 1024u;
-  if (bw == 0 || count == 0 || count > (1u << 20)) {
-    err = "diag_beam_select: bw and count must be in [1, 2^20]";
+  const uint32_t cap = lds == 2 ? DIAG_HBM_RING : lds ? 256u : 1024u;
+  if (bw == 0 || count == 0 || count > (lds == 2 ? 16u : 1u << 20)) {
+    err = "diag_beam_select: bw and count must be in [1, 2^20] (count <= 16 for the HBM ring)";
     return FAC_E_INVALID;
   }
   for (uint64_t a = 0; a < count; ++a) {  // the kernels' preconditions: 2 bw < P <= ring
@@ -5471,8 +5686,10 @@ int diag_beam_select(const float* keys, const uint64_t* offs, uint64_t count, ui
   auto run = [&]() -> int {
     HIP_TRY(hipMalloc((void**)&dp, count * bw * sizeof(uint32_t)));
     if (!lds) HIP_TRY(hipMalloc((void**)&db, count * bsel_stride(1024) * sizeof(uint4)));
+    if (lds == 2) HIP_TRY(hipMalloc((void**)&db, count * DIAG_HBM_REGION * sizeof(uint4)));
     const uint32_t lim = sel_limit < 0 ? 16u : (uint32_t)sel_limit;
-    if (lds) hipLaunchKernelGGL((diag_select_kernel<256, true>), dim3((uint32_t)count), dim3(64), 0, 0, dk, dof, bw, lim, db, dp);
+    if (lds == 2) hipLaunchKernelGGL(diag_select_hbm_kernel, dim3((uint32_t)count), dim3(64), 0, 0, dk, dof, bw, lim, db, dp);
+    else if (lds) hipLaunchKernelGGL((diag_select_kernel<256, true>), dim3((uint32_t)count), dim3(64), 0, 0, dk, dof, bw, lim, db, dp);
     else hipLaunchKernelGGL((diag_select_kernel<1024, false>), dim3((uint32_t)count), dim3(64), 0, 0, dk, dof, bw, lim, db, dp);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(perm, dp, count * bw * sizeof(uint32_t), hipMemcpyDeviceToHost));

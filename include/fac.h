@@ -19,12 +19,19 @@
  *   FAC_E_HAYSTACK_TOO_LARGE    1   SearchError::HaystackTooLarge{graphemes} (search.rs:198-201)
  *   FAC_E_INVALID             100   bad argument (NULL, invalid UTF-8, beam_width == 0, ...)
  *   FAC_E_UNSUPPORTED         101   configuration outside the GPU path (> 64 mapping transitions
- *                                   at one node, > 2^26 nodes, ...) — never a silent CPU fallback
+ *                                   at one node, > 2^26 nodes, a beam or a node fan-out past the
+ *                                   largest frontier ring of 2^20 states, ...) — never a silent CPU
+ *                                   fallback
  *   FAC_E_HIP                 102   HIP runtime error (fac_last_error() has the text)
  *   FAC_E_NO_DEVICE           103   no usable MI355X (gfx950) device
  *   FAC_E_OOM                 104   host or device allocation failure
  *   FAC_E_CAPACITY            105   a per-window device work buffer overflowed even after the
- *                                   automatic retries (pathological input)
+ *                                   automatic retries: one window's frontier past the largest
+ *                                   HBM rung (2^20 states), or past what the HBM frontier budget
+ *                                   holds; fac_last_error() names the bound. The budget: at most
+ *                                   1 GiB of device scratch, allocated when a search first needs
+ *                                   an HBM rung; like the engine's other scratch it stays bound
+ *                                   to the engine (or stream worker) until that is freed
  *   FAC_E_OUTPUT_CAPACITY     106   the caller's device output buffer is too small; *n_out holds
  *                                   the record count needed (fac_search_staged_ex)
  *   FAC_E_INTERNAL            107   unexpected internal error (fac_last_error() has the text)
@@ -767,7 +774,8 @@ uint32_t fac_fold_first_char(const uint8_t* utf8, uint64_t len, int32_t case_ins
 void fac_edge_order(const uint32_t* cps, const uint64_t* off, uint64_t n, uint32_t* order);
 
 /* Diagnostics (tests): the device beam cut alone. Array a holds keys[offs[a] .. offs[a+1]) as the
- * penalties of a queue's pending states (2*bw < length <= 256 for lds != 0, <= 1024 otherwise); the
+ * penalties of a queue's pending states (2*bw < length <= 256 for lds == 1, <= 1024 for lds == 0;
+ * lds == 2: a ring in global memory as on the largest HBM rung, length <= 2^20, count <= 16); the
  * kernel keeps bw of them exactly as the search's beam does -- the reference's
  * `queue[q_idx..].select_nth_unstable_by(bw - 1, total_cmp)` + `truncate(q_idx + bw)`
  * (search.rs:584-587) -- and writes the survivors' original indices, in queue order, to
