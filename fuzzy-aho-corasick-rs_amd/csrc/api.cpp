@@ -18,6 +18,7 @@
 #include <tuple>
 
 #include "fac_internal.h"
+#include "host_util.h"
 
 struct fac_engine {
   fac::Engine e;
@@ -814,7 +815,8 @@ namespace fac {
 // sorted().non_overlapping() and cut at its commit point on the host. FAC_E_UNSUPPORTED (nothing
 // done) when the batch does not qualify: a Unicode haystack (a window's grapheme segmentation
 // depends on where its text starts and ends), windows out of order or overlapping beyond their
-// neighbours, or pre-filter tables that need the packed full scan.
+// neighbours, or pre-filter tables that need the packed full scan. (Its counterpart for every other
+// task, stream_windows_docs, stands at the end of this file: it calls batch_kept, defined below.)
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
                          bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
                          std::vector<uint64_t>* win_off, uint64_t* searched) {
@@ -1370,14 +1372,16 @@ struct BatchKept {
   explicit BatchKept(hipStream_t st) : raw(st), doff(st) {}
 };
 
-// d_doc_user: where the index goes instead of the call's own scratch (may be NULL)
+// d_doc_user: where the index goes instead of the call's own scratch (may be NULL); searched
+// (optional): += the start windows handed to the search launcher
 static int batch_kept(const fac::Engine& e, const fac::Batch& b, float threshold, int order, int overlap,
                       const uint64_t* unique_ids, bool prefilter, hipStream_t st, uint64_t* d_doc_user, fac_stats* stats,
-                      BatchKept& k, std::string& err) {
+                      BatchKept& k, std::string& err, uint64_t* searched = nullptr) {
   const uint64_t nd = b.n_docs;
   fac::BatchWindows pw;  // pre-filtered: every document's merged windows, found once
   bool filtered = false;
   if (int rc = batch_prefilter(e, b, threshold, prefilter, st, pw, filtered, stats, err)) return rc;
+  if (searched) *searched += filtered ? pw.windows : b.windows;
   uint64_t cap = std::max<uint64_t>(4096, (filtered ? pw.windows : b.windows) / 64);
   for (;;) {
     if (int rc = k.raw.alloc(2 * cap * sizeof(fac_match), err)) return rc;
@@ -1870,6 +1874,19 @@ int fac_stream_open_ex(const fac_engine* engine, float threshold, uint64_t windo
 
 uint64_t fac_stream_windows_searched(const fac_stream* stream) { return stream ? stream->s->windows_searched : 0; }
 
+static void task_counts(const fac::StreamCore* s, uint64_t* batched, uint64_t* single) {
+  if (batched) *batched = s ? s->tasks_batched : 0;
+  if (single) *single = s ? s->tasks_single : 0;
+}
+
+void fac_stream_task_counts(const fac_stream* stream, uint64_t* batched, uint64_t* single) {
+  task_counts(stream ? stream->s : nullptr, batched, single);
+}
+
+void fac_replace_stream_task_counts(const fac_replace_stream* stream, uint64_t* batched, uint64_t* single) {
+  task_counts(stream ? stream->s : nullptr, batched, single);
+}
+
 int fac_stream_feed(fac_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, fac_match** out,
                     uint64_t* n_out, uint8_t** text, uint64_t* text_len) {
   if (!stream || !out || !n_out || !text || !text_len || (len && !data)) return fail(FAC_E_INVALID, "NULL argument");
@@ -2002,4 +2019,136 @@ int fac_diag_beam_select(const float* keys, const uint64_t* offs, uint64_t count
   return rc ? fail(rc, err) : FAC_OK;
 }
 
+int fac_diag_stream_gather(const fac_engine* engine, const uint8_t* utf8, uint64_t len, const uint64_t* windows,
+                           uint64_t n_windows, uint8_t* out, uint64_t cap, uint64_t* offsets) {
+  if (!engine || !offsets || (len && !utf8) || (n_windows && !windows) || (cap && !out))
+    return fail(FAC_E_INVALID, "NULL argument");
+  if (n_windows > fac::kBatchMaxDocs) return fail(FAC_E_UNSUPPORTED, "at most 2^24 windows");
+  const fac::Engine& e = engine->e;
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  std::vector<uint64_t> tab(2 * n_windows + 1, 0);  // sources, then lengths and their closing entry
+  uint64_t total = 0;
+  for (uint64_t w = 0; w < n_windows; ++w) {
+    const uint64_t off = windows[2 * w], wl = windows[2 * w + 1];
+    if (off > len || wl > len - off) return fail(FAC_E_INVALID, "a window lies outside the text");
+    tab[w] = off;
+    tab[n_windows + w] = wl;
+    total += wl;
+  }
+  if (total > cap) return fail(FAC_E_OUTPUT_CAPACITY, "output buffer too small");
+  hipStream_t st = e.stream;
+  std::string err;
+  DevMem d_text(st), d_tab(st), d_off(st), d_out(st);
+  if (int rc = d_text.alloc(len, err)) return fail(rc, err);
+  if (int rc = d_tab.alloc(tab.size() * 8, err)) return fail(rc, err);
+  if (int rc = d_off.alloc((n_windows + 1) * 8, err)) return fail(rc, err);
+  if (int rc = d_out.alloc(total, err)) return fail(rc, err);
+  const uint64_t* dt = static_cast<const uint64_t*>(d_tab.p);
+  int rc = FAC_OK;
+  if ((len && hipMemcpyAsync(d_text.p, utf8, len, hipMemcpyHostToDevice, st) != hipSuccess) ||
+      hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
+    rc = FAC_E_HIP;
+    err = "upload of the windows failed";
+  }
+  if (!rc)
+    rc = fac::stream_gather_device(static_cast<const uint8_t*>(d_text.p), len, dt, dt + n_windows, n_windows, total,
+                                   static_cast<uint8_t*>(d_out.p), static_cast<uint64_t*>(d_off.p), st, err);
+  if (!rc && ((total && hipMemcpyAsync(out, d_out.p, total, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+              hipMemcpyAsync(offsets, d_off.p, (n_windows + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess)) {
+    rc = FAC_E_HIP;
+    err = "copy of the expanded text failed";
+  }
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) {
+    rc = FAC_E_HIP;
+    err = "the gather of the windows failed";
+  }
+  return rc ? fail(rc, err) : FAC_OK;
+}
+
 }  // extern "C"
+
+namespace fac {
+
+// A task of stream windows as one batch of window documents (stream.rs window_matches for each,
+// :262-297): document w is window w's text, staged as if it were staged alone (stage_batch_device),
+// so a window's segmentation starts and ends with its own bytes whatever its neighbours hold. The
+// table of the windows (sources, lengths, commit points, rebase offsets) is the only upload; the
+// expanded text, the offsets, the staging, the search, the per-document rank and overlap walk and
+// the commit cut run on the device, and only the owned records and their index come back.
+int stream_windows_docs(const Engine& e, WindowDocs& wd, const uint8_t* d_text, uint64_t text_len, const uint64_t* wins,
+                        uint64_t n_windows, float threshold, bool prefilter, hipStream_t st, std::vector<fac_match>& owned,
+                        std::string& err, std::vector<uint64_t>& win_off, uint64_t* searched) {
+  owned.clear();
+  win_off.assign(n_windows + 1, 0);
+  if (n_windows == 0) return FAC_OK;
+  if (n_windows > kBatchMaxDocs) return FAC_E_UNSUPPORTED;
+  const uint64_t n = n_windows;
+  // sources [0, n), lengths and their closing entry [n, 2n], commit points, rebase offsets
+  std::vector<uint64_t> tab(4 * n + 1, 0);
+  uint64_t total = 0;
+  for (uint64_t w = 0; w < n; ++w) {
+    const uint64_t off = wins[4 * w], end = wins[4 * w + 1];
+    if (off > end || end > text_len) {
+      err = "a stream window lies outside its task's text";
+      return FAC_E_INTERNAL;
+    }
+    tab[w] = off;
+    tab[n + w] = end - off;
+    tab[2 * n + 1 + w] = wins[4 * w + 2];
+    tab[3 * n + 1 + w] = wins[4 * w + 3];
+    total += end - off;
+  }
+  if (total >= (1ull << kDocTagShift)) return FAC_E_UNSUPPORTED;
+  Batch& b = wd.b;
+  b.h.device = e.device;
+  if (wd.text_cap < std::max<uint64_t>(total, 16)) {
+    if (b.h.d_utf8) HIP_TRY(hipFree(b.h.d_utf8));
+    b.h.d_utf8 = nullptr;
+    wd.text_cap = 0;
+    const uint64_t want = std::max<uint64_t>(total + total / 8, 16);
+    HIP_TRY(hipMalloc((void**)&b.h.d_utf8, want));
+    wd.text_cap = want;
+  }
+  b.h.own_utf8 = true;
+  if (b.offsets_cap < n + 1) {
+    if (b.d_offsets) HIP_TRY(hipFree(b.d_offsets));
+    b.d_offsets = nullptr;
+    b.offsets_cap = 0;
+    HIP_TRY(hipMalloc((void**)&b.d_offsets, (n + 1 + n / 8) * 8));
+    b.offsets_cap = n + 1 + n / 8;
+  }
+  b.own_offsets = true;
+  b.h.len = total;
+  b.n_docs = n;
+  b.unicode_pf = true;
+  b.unicode_map = true;
+  b.long_docs = true;  // a window is 256 KiB: segmented by chunks, not by one thread
+  DevMem d_tab(st);
+  if (int rc = d_tab.alloc(tab.size() * 8, err)) return rc;
+  const uint64_t* dt = static_cast<const uint64_t*>(d_tab.p);
+  int rc = FAC_OK;
+  if (hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
+    rc = FAC_E_HIP;
+    err = "upload of a stream task's windows failed";
+  }
+  if (!rc) rc = stream_gather_device(d_text, text_len, dt, dt + n, n, total, b.h.d_utf8, b.d_offsets, st, err);
+  if (!rc) rc = stage_batch_device(e, b, st, err);  // (synchronises: the table has been read)
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    b.n_docs = 0;  // a failed staging leaves an empty batch
+    b.n_segs = 0;
+    b.windows = 0;
+    b.h.len = 0;
+    b.h.n = 0;
+    // search_raw's error of the first window that fails: HaystackTooLarge has no message of its own
+    if (rc == FAC_E_HAYSTACK_TOO_LARGE) err.clear();
+    return rc;
+  }
+  BatchKept k(st);
+  if ((rc = batch_kept(e, b, threshold, /*Default*/ 1, /*NonOverlapping*/ 1, nullptr, prefilter, st, nullptr, nullptr, k, err,
+                       searched)))
+    return rc;
+  return windows_owned_device(k.res, k.n_res, k.d_doc, n, dt + 2 * n + 1, dt + 3 * n + 1, st, owned, win_off, err);
+}
+
+}  // namespace fac

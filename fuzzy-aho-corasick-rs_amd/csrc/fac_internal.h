@@ -528,6 +528,10 @@ struct Batch {
   // even if it holds non-ASCII documents (their grapheme ids: batch_grapheme_ids_kernel). Kept
   // across a restage like unicode_pf, and independent of it.
   bool unicode_map = false;
+  // stream_windows_docs: the documents are long (256 KiB windows), so stage_batch_device segments
+  // the non-ASCII ones by chunks of the text (batch_seg_chunk_kernel) instead of one thread each.
+  // The staged batch is the same either way.
+  bool long_docs = false;
   mutable uint32_t* d_sstart = nullptr;
   mutable uint64_t sstart_cap = 0;  // words d_sstart holds
   mutable bool sstart_ready = false;
@@ -876,6 +880,12 @@ struct StreamCore {
   bool prefilter = false;
   // start windows of the segments handed to the search launcher, for the windows handed out so far
   uint64_t windows_searched = 0;
+  // tasks handed out so far that were searched in one pass (stream_windows_batch or
+  // stream_windows_docs) and window by window (fac_stream_task_counts)
+  uint64_t tasks_batched = 0, tasks_single = 0;
+  // a task with non-ASCII text is searched as one batch of window documents (FAC_STREAM_WINDOW_DOCS=0,
+  // a diagnostics knob, turns that off: such a task's windows are then searched one by one)
+  bool window_docs = true;
   // replace mode (fac_replace_stream_*): the table, the output ready to hand out, the totals of the
   // tasks handed out, and ReplaceCursor::emitted (stream.rs:645-648) as it passes from task to task:
   // cur_emitted is the cursor after task cur_seq - 1, and task cur_seq plans next
@@ -940,6 +950,34 @@ void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
                          bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
                          std::vector<uint64_t>* win_off = nullptr, uint64_t* searched = nullptr);
+// stage_kernels.hip: the expanded text of a stream task. Window w is bytes [d_src[w], d_src[w] +
+// d_len[w]) of the text_len bytes at d_text (every range inside the text, checked by the caller;
+// d_len has a closing entry); the n_windows + 1 document offsets go to d_offsets (exclusive sums of
+// d_len) and the windows' bytes, one after the other, to the `total` bytes at d_out (asynchronous)
+int stream_gather_device(const uint8_t* d_text, uint64_t text_len, const uint64_t* d_src, const uint64_t* d_len,
+                         uint64_t n_windows, uint64_t total, uint8_t* d_out, uint64_t* d_offsets, hipStream_t st,
+                         std::string& err);
+// rank_kernels.hip: the commit cut of a batch of window documents. d_recs / d_doc_off:
+// apply_batch_device's result for NonOverlapping (a document's records in start order, document-
+// relative). Window w owns the records that start before d_commit[w], a prefix of its group; they go
+// to `owned` in window order with d_add[w] added to start and end, win_off receives their CSR index
+// (n_windows + 1). Only those records and the index are copied to the host (synchronous).
+int windows_owned_device(const fac_match* d_recs, uint64_t n_recs, const uint64_t* d_doc_off, uint64_t n_windows,
+                         const uint64_t* d_commit, const uint64_t* d_add, hipStream_t s, std::vector<fac_match>& owned,
+                         std::vector<uint64_t>& win_off, std::string& err);
+// api.cpp: a task of stream windows searched as one batch whose document w is window w's text
+// (wins as for stream_windows_batch, byte offsets into the text_len bytes at d_text): the expanded
+// text is gathered into wd.b (owned by the caller, restaged in place), staged per document, searched
+// through the batch front (pre-filter, one launch, per-document rank and overlap walk) and cut at
+// the commit points on the device. A window that fails staging gives its search_raw error.
+struct WindowDocs {
+  Batch b;                // h.d_utf8 (the expanded text) and d_offsets are the batch's own
+  uint64_t text_cap = 0;  // bytes h.d_utf8 holds
+};
+// FAC_E_UNSUPPORTED (nothing done): more than 2^24 windows or 2^40 expanded bytes.
+int stream_windows_docs(const Engine& e, WindowDocs& wd, const uint8_t* d_text, uint64_t text_len, const uint64_t* wins,
+                        uint64_t n_windows, float threshold, bool prefilter, hipStream_t st, std::vector<fac_match>& owned,
+                        std::string& err, std::vector<uint64_t>& win_off, uint64_t* searched);
 // prefilter_kernels.hip: merged bitap windows (prefilter.rs:319-342) of a text view of a staged haystack (view.ascii:
 // bytes [text_base, text_base + n) of h.d_utf8; else graphemes [text_base, text_base + n)); windows
 // in the view's local grapheme coordinates

@@ -677,6 +677,88 @@ void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std
   if (win_off) (*win_off)[nw] = out.size();
 }
 
+// ---------------------------------------------------------------- commit cut of window documents
+// A stream task searched as a batch of window documents (api.cpp stream_windows_docs): after
+// NonOverlapping a document's kept records are in start order, so the records window w owns
+// (start < commit[w], stream.rs:262-297) are a prefix of its group.
+namespace {
+
+// One thread per window: the owned count, by bisection of its group (cnt has a closing 0).
+__global__ void owned_count_kernel(const fac_match* __restrict__ m, const uint64_t* __restrict__ doc_off, uint64_t n_windows,
+                                   const uint64_t* __restrict__ commit, uint64_t* __restrict__ cnt) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w > n_windows) return;
+  if (w == n_windows) {
+    cnt[w] = 0;
+    return;
+  }
+  const uint64_t b = doc_off[w], c = commit[w];
+  uint64_t lo = b, hi = doc_off[w + 1];
+  while (lo < hi) {  // first record of the group that starts at or after the commit point
+    const uint64_t mid = (lo + hi) >> 1;
+    if (m[mid].start < c) lo = mid + 1;
+    else hi = mid;
+  }
+  cnt[w] = lo - b;
+}
+
+// One thread per kept record: its window (the last group that begins at or before it), and, if it is
+// among the window's owned prefix, its slot in the compacted output, rebased by add[w].
+__global__ void owned_write_kernel(const fac_match* __restrict__ m, uint64_t n, const uint64_t* __restrict__ doc_off,
+                                   uint64_t n_windows, const uint64_t* __restrict__ own_off,
+                                   const uint64_t* __restrict__ add, fac_match* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t lo = 0, hi = n_windows - 1;
+  while (lo < hi) {  // last w with doc_off[w] <= i: then doc_off[w + 1] > i (doc_off[n_windows] = n)
+    const uint64_t mid = (lo + hi + 1) >> 1;
+    if (doc_off[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint64_t k = i - doc_off[lo], o = own_off[lo];
+  if (k >= own_off[lo + 1] - o) return;
+  fac_match r = m[i];
+  r.start += add[lo];
+  r.end += add[lo];
+  out[o + k] = r;
+}
+
+}  // namespace
+
+int windows_owned_device(const fac_match* d_recs, uint64_t n_recs, const uint64_t* d_doc_off, uint64_t n_windows,
+                         const uint64_t* d_commit, const uint64_t* d_add, hipStream_t s, std::vector<fac_match>& owned,
+                         std::vector<uint64_t>& win_off, std::string& err) {
+  owned.clear();
+  win_off.assign(n_windows + 1, 0);
+  if (n_recs == 0 || n_windows == 0) return FAC_OK;
+  t_buf_stream = s;
+  Buf d_cnt, d_own, d_out;
+  HIP_TRY(d_cnt.alloc((n_windows + 1) * 8));
+  HIP_TRY(d_own.alloc((n_windows + 1) * 8));
+  HIP_TRY(d_out.alloc(n_recs * sizeof(fac_match)));
+  const uint32_t T = 256;
+  hipLaunchKernelGGL(owned_count_kernel, dim3((uint32_t)((n_windows + 1 + T - 1) / T)), dim3(T), 0, s, d_recs, d_doc_off,
+                     n_windows, d_commit, d_cnt.as<uint64_t>());
+  HIP_TRY(hipGetLastError());
+  if (int rc = exclusive_sum_u64(d_cnt.as<uint64_t>(), d_own.as<uint64_t>(), n_windows + 1, s, err)) return rc;
+  hipLaunchKernelGGL(owned_write_kernel, dim3((uint32_t)((n_recs + T - 1) / T)), dim3(T), 0, s, d_recs, n_recs, d_doc_off,
+                     n_windows, d_own.as<uint64_t>(), d_add, d_out.as<fac_match>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(win_off.data(), d_own.p, (n_windows + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t n_owned = win_off[n_windows];
+  if (n_owned > n_recs) {
+    err = "the commit cut of a stream task counted more records than it was given";
+    return FAC_E_INTERNAL;
+  }
+  owned.resize(n_owned);
+  if (n_owned) {
+    HIP_TRY(hipMemcpyAsync(owned.data(), d_out.p, n_owned * sizeof(fac_match), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return FAC_OK;
+}
+
 namespace {
 // One pool per process (not per thread: a stream's blocks must be found again by whoever destroys
 // the stream), keyed by (device, stream, size class). Size classes are powers of two up to 64 MiB

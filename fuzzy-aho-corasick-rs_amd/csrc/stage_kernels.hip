@@ -1227,6 +1227,97 @@ __global__ __launch_bounds__(64) void batch_seg_kernel(const uint8_t* __restrict
   if (!WRITE) tri_in[d].u = cnt;
 }
 
+// last document d in [lo, hi] with off[d] <= x (off[lo] <= x holds)
+__device__ inline uint64_t window_of(const uint64_t* __restrict__ off, uint64_t lo, uint64_t hi, uint64_t x) {
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The same segmentation for long documents (Batch::long_docs: a stream task's 256 KiB windows, where
+// one thread per document walks for milliseconds): one thread per kSegChunk bytes of the batch's
+// text, whatever documents they belong to. A thread decides the boundaries of the code points that
+// start in its bytes; the segmenter's state before the first of them comes from the nearest resync
+// code point before it, or from the document's first code point, whichever is nearer (so a long
+// combining, emoji or regional-indicator run costs its threads a walk back to the run's start, at
+// worst the one-thread-per-document walk). ASCII and invalid documents are stepped over, as there.
+// WRITE = false: the chunk's grapheme count to ccnt[chunk], and added to tri_in[d].u (zeroed by the
+// caller) for every document it touches. WRITE = true: cbase = the exclusive sums of ccnt; documents
+// lie in the text in order, so that is the chunk's first slot in goff / text32.
+constexpr uint32_t kSegChunk = 256;
+template <bool WRITE>
+__global__ __launch_bounds__(256) void batch_seg_chunk_kernel(const uint8_t* __restrict__ s, uint64_t total,
+                                                              const uint64_t* __restrict__ off, uint64_t n_docs,
+                                                              const uint32_t* __restrict__ flags,
+                                                              const uint8_t* __restrict__ ptab, const uint16_t* __restrict__ ltab,
+                                                              int ci, BatchTri* __restrict__ tri_in, uint64_t* __restrict__ ccnt,
+                                                              const uint64_t* __restrict__ cbase, uint64_t* __restrict__ goff,
+                                                              uint32_t* __restrict__ text32) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t c0 = k * kSegChunk;
+  if (c0 >= total) return;
+  const uint64_t c1 = total - c0 < kSegChunk ? total : c0 + kSegChunk;
+  uint64_t d = window_of(off, 0, n_docs - 1, c0);  // (off[0] = 0, off[n_docs] = total: checked before)
+  uint64_t cnt = 0;
+  uint64_t base = 0;
+  if (WRITE) base = cbase[k];
+  uint64_t i = c0;
+  while (i < c1) {
+    while (i >= off[d + 1]) ++d;  // (i < total = off[n_docs]: d stays below n_docs)
+    const uint64_t a = off[d], b = off[d + 1];
+    const uint64_t e = b < c1 ? b : c1;
+    const uint32_t f = flags[d];
+    if (!(f & 2u) || (f & 1u)) {
+      i = e;
+      continue;
+    }
+    // the first code point that starts in [i, e): the bytes before it belong to the chunk before
+    uint64_t p = i;
+    while (p < e && p > a && (s[p] & 0xC0u) == 0x80u) ++p;
+    SegState st{};
+    if (p < e && p > a) {  // the state before p
+      uint64_t q = p;
+      for (;;) {
+        do --q;
+        while (q > a && (s[q] & 0xC0u) == 0x80u);
+        if (q == a) break;
+        uint64_t t = q;
+        if (resync(props_fast(ptab, decode(s, b, t)))) break;
+      }
+      st = seg_init(props_fast(ptab, decode(s, b, q)));
+      while (q < p) seg_step(st, props_fast(ptab, decode(s, b, q)));
+    }
+    const uint64_t tag = d << kDocTagShift;
+    uint64_t here = 0;
+    while (p < e) {
+      const uint64_t pos = p;
+      const uint32_t cp = decode(s, b, p);
+      const Props R = props_fast(ptab, cp);
+      bool br;
+      if (pos == a) {
+        st = seg_init(R);
+        br = true;
+      } else {
+        br = seg_step(st, R);
+      }
+      if (br) {
+        if (WRITE) {
+          goff[base + cnt] = pos | tag;
+          text32[base + cnt] = ci ? fold_fast(ltab, cp) : cp;
+        }
+        ++cnt;
+        ++here;
+      }
+    }
+    if (!WRITE && here) atomicAdd(reinterpret_cast<unsigned long long*>(&tri_in[d].u), (unsigned long long)here);
+    i = e;  // (a code point may run past c1: the next chunk skips its continuation bytes)
+  }
+  if (!WRITE) ccnt[k] = cnt;
+}
+
 // windows and the "not empty" flag per document (an ASCII document's graphemes are its bytes); the
 // first document over the grapheme limit
 __global__ void batch_tri_kernel(const uint64_t* __restrict__ off, uint64_t n_docs, const uint32_t* __restrict__ flags,
@@ -1368,10 +1459,33 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   if (int trc = bmp_tables(h.device, st, tabs, err)) return trc;
   hipLaunchKernelGGL(batch_doc_scan_kernel, dim3((uint32_t)((nd + 3) / 4)), dim3(T), 0, st, h.d_utf8, b.d_offsets, nd,
                      b.d_flags, b.d_scal);
-  // (every thread returns at once in an all-ASCII batch: no segmentation work)
-  hipLaunchKernelGGL(batch_seg_kernel<false>, dim3((uint32_t)((nd + 63) / 64)), dim3(64), 0, st, h.d_utf8, b.d_offsets, nd,
-                     b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, b.d_tri_ex, (uint64_t*)nullptr,
-                     (uint32_t*)nullptr);
+  // long documents are segmented by chunks of the text: per chunk its count and its first slot
+  const uint64_t n_chunks = b.long_docs ? (len + kSegChunk - 1) / kSegChunk : 0;
+  struct Chunks {
+    uint64_t* p = nullptr;
+    hipStream_t st;
+    ~Chunks() {
+      if (p) call_scratch_give(p, st);
+    }
+  } chunks;
+  chunks.st = st;
+  if (n_chunks) {
+    hipError_t he = hipSuccess;
+    chunks.p = static_cast<uint64_t*>(call_scratch_take(2 * n_chunks * 8, st, &he));
+    if (he != hipSuccess) chunks.p = nullptr;
+    HIP_TRY(he);
+    HIP_TRY(hipMemsetAsync(b.d_tri_in, 0, tri_b, st));
+    hipLaunchKernelGGL(batch_seg_chunk_kernel<false>, dim3((uint32_t)((n_chunks + T - 1) / T)), dim3(T), 0, st, h.d_utf8, len,
+                       b.d_offsets, nd, b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, chunks.p,
+                       (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    if (int rc = exclusive_sum_u64(chunks.p, chunks.p + n_chunks, n_chunks, st, err)) return rc;
+  } else {
+    // (every thread returns at once in an all-ASCII batch: no segmentation work)
+    hipLaunchKernelGGL(batch_seg_kernel<false>, dim3((uint32_t)((nd + 63) / 64)), dim3(64), 0, st, h.d_utf8, b.d_offsets, nd,
+                       b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, b.d_tri_ex, (uint64_t*)nullptr,
+                       (uint32_t*)nullptr);
+  }
   hipLaunchKernelGGL(batch_tri_kernel, dim3(G1), dim3(T), 0, st, b.d_offsets, nd, b.d_flags, b.d_tri_in, grapheme_limit(),
                      b.d_scal);
   HIP_TRY(hipGetLastError());
@@ -1419,8 +1533,13 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
       HIP_TRY(hipMalloc((void**)&h.d_text32, std::max<uint64_t>(h.n * 4, 16)));
       h.off_cap = h.n + 1;
     }
-    hipLaunchKernelGGL(batch_seg_kernel<true>, dim3((uint32_t)((nd + 63) / 64)), dim3(64), 0, st, h.d_utf8, b.d_offsets, nd,
-                       b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, b.d_tri_ex, h.d_off, h.d_text32);
+    if (n_chunks)
+      hipLaunchKernelGGL(batch_seg_chunk_kernel<true>, dim3((uint32_t)((n_chunks + T - 1) / T)), dim3(T), 0, st, h.d_utf8, len,
+                         b.d_offsets, nd, b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, (uint64_t*)nullptr,
+                         chunks.p + n_chunks, h.d_off, h.d_text32);
+    else
+      hipLaunchKernelGGL(batch_seg_kernel<true>, dim3((uint32_t)((nd + 63) / 64)), dim3(64), 0, st, h.d_utf8, b.d_offsets, nd,
+                         b.d_flags, tabs.p, tabs.l, e.case_insensitive ? 1 : 0, b.d_tri_in, b.d_tri_ex, h.d_off, h.d_text32);
   }
   if (b.seg_cap < tot.s + 1) {
     if (b.d_segs) HIP_TRY(hipFree(b.d_segs));
@@ -1438,6 +1557,82 @@ int stage_batch_device(const Engine& e, Batch& b, hipStream_t st, std::string& e
   HIP_TRY(hipStreamSynchronize(st));
   b.n_segs = tot.s;
   b.windows = tot.w;
+  return FAC_OK;
+}
+
+// ---------------------------------------------------------------- stream tasks as window documents
+// The expanded text of a stream task (stream.cpp): consecutive windows overlap (the next one starts
+// at this one's commit point) and a batch's documents are disjoint, so every window's bytes, overlap
+// included, are copied one after the other into a second buffer. An output-stationary byte mover in
+// piece_copy_kernel's idiom: a workgroup owns a tile of kGatherTile output bytes, thread 0 bisects the
+// tile's first and last window once, a lane bisects only between them and moves its 16 bytes. Where
+// they come from one window: one 16-byte load if the source is 16-byte aligned like the destination,
+// else aligned words shifted into place (chunk_load16) if those words lie inside the text; bytes in
+// every other case (a lane across a window boundary, the text's last bytes, the output's tail).
+// Reads stay inside [0, text_len), writes inside [0, total).
+namespace {
+
+constexpr uint32_t kGatherTile = 4096, kGatherThreads = kGatherTile / 16;
+
+// doc_off has n_windows + 1 entries (the last one = total), n_windows >= 1, total >= 1.
+__global__ __launch_bounds__(kGatherThreads) void stream_gather_kernel(const uint8_t* __restrict__ text, uint64_t text_len,
+                                                                       const uint64_t* __restrict__ src,
+                                                                       const uint64_t* __restrict__ doc_off,
+                                                                       uint64_t n_windows, uint8_t* __restrict__ out,
+                                                                       uint64_t total, int wide) {
+  __shared__ uint64_t s_win[2];
+  const uint64_t tile0 = (uint64_t)blockIdx.x * kGatherTile;
+  if (tile0 >= total) return;
+  if (threadIdx.x == 0) {
+    const uint64_t tile_last = (total - tile0 < kGatherTile ? total : tile0 + kGatherTile) - 1;
+    const uint64_t w0 = window_of(doc_off, 0, n_windows - 1, tile0);
+    s_win[0] = w0;
+    s_win[1] = window_of(doc_off, w0, n_windows - 1, tile_last);
+  }
+  __syncthreads();
+  const uint64_t g = tile0 + (uint64_t)threadIdx.x * 16;
+  if (g >= total) return;
+  const uint32_t n = total - g < 16 ? (uint32_t)(total - g) : 16u;
+  // the lane's first byte lies in window w (the last one that starts at or before it, so not empty)
+  uint64_t w = window_of(doc_off, s_win[0], s_win[1], g);
+  uint64_t lo = doc_off[w], hi = doc_off[w + 1];
+  Chunk16 c;
+  if (n == 16 && g + 16 <= hi) {  // one window's bytes
+    const uint64_t sp = src[w] + (g - lo);
+    const uint32_t a16 = (uint32_t)(reinterpret_cast<uintptr_t>(text + sp) & 15u), a4 = a16 & 3u;
+    if (a16 == 0 && wide && sp + 16 <= text_len) {
+      *reinterpret_cast<uint4*>(out + g) = *reinterpret_cast<const uint4*>(text + sp);
+      return;
+    }
+    if (sp >= a4 && sp - a4 + (a4 ? 20u : 16u) <= text_len) chunk_load16(c, text + sp);
+  }
+  if (c.filled == 0) {
+    for (uint32_t t = 0; t < n; ++t) {
+      const uint64_t pos = g + t;
+      while (pos >= hi) {  // (pos < total = doc_off[n_windows]: w stays below n_windows)
+        ++w;
+        lo = hi;
+        hi = doc_off[w + 1];
+      }
+      const uint64_t sp = src[w] + (pos - lo);
+      chunk_put(c, sp < text_len ? (uint64_t)text[sp] : 0ull);
+    }
+  }
+  chunk_store(c, out + g, wide);
+}
+
+}  // namespace
+
+int stream_gather_device(const uint8_t* d_text, uint64_t text_len, const uint64_t* d_src, const uint64_t* d_len,
+                         uint64_t n_windows, uint64_t total, uint8_t* d_out, uint64_t* d_offsets, hipStream_t st,
+                         std::string& err) {
+  if (int rc = exclusive_sum_u64(d_len, d_offsets, n_windows + 1, st, err)) return rc;
+  if (!total || !n_windows) return FAC_OK;
+  const uint64_t tiles = (total + kGatherTile - 1) / kGatherTile;  // < 2^28: total < 2^40
+  const int wide = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0 ? 1 : 0;
+  hipLaunchKernelGGL(stream_gather_kernel, dim3((uint32_t)tiles), dim3(kGatherThreads), 0, st, d_text, text_len, d_src,
+                     d_offsets, n_windows, d_out, total, wide);
+  HIP_TRY(hipGetLastError());
   return FAC_OK;
 }
 

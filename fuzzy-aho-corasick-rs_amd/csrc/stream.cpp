@@ -11,10 +11,21 @@
 // Consecutive windows are collected into batches of about 32 MiB of text, and each batch is handed
 // to one of `depth` (2) worker threads, batch k to worker k % depth. A worker owns a HIP stream and
 // a device scratch set. An all-ASCII batch is staged once (H2D) and its windows searched in one
-// launch, each as its own text (stream_windows_batch); a batch with other text stages and searches
-// its windows one by one (H2D + device segmentation + folding each). A pre-filtered stream
-// (fac_stream_open_ex) searches every window's text as Prefiltered::search: the batched path hands the
-// flag to stream_windows_batch, a single window goes through prefiltered_view. Every window is ranked
+// launch, each as its own text (stream_windows_batch). A window's grapheme segmentation depends on
+// where its text starts and ends, so the windows of other text cannot be grapheme ranges of one staged
+// text; such a batch is uploaded once and searched as a fac::Batch whose document w is window w's text
+// (stream_windows_docs). Windows overlap their neighbours and a batch's documents are disjoint, so a
+// gather kernel copies every window's bytes, overlap included, into a second device buffer and
+// writes the document offsets; the worker's Batch is restaged over it (UTF-8 check, is_ascii and UAX
+// #29 from start-of-text per document, exactly a window's semantics; the windows are long documents,
+// so they are segmented by 256-byte chunks, Batch::long_docs), the batch front runs the
+// pre-filter where Prefiltered::search would, one search launch and the per-document rank and
+// overlap walk, and the commit cut keeps each document's owned prefix, all on the device: only the
+// owned records and their index come back. The same path takes an ASCII batch that
+// stream_windows_batch declines (pre-filter tables that need the packed full scan). Only a batch of
+// one window stages and searches it alone (H2D + device segmentation + folding). A pre-filtered
+// stream (fac_stream_open_ex) searches every window's text as Prefiltered::search: the batched paths
+// take the flag, a single window goes through prefiltered_view. Every window is ranked
 // sorted().non_overlapping() and keeps the matches it owns (stream.rs:262-297). Batch k + 1's
 // copies and kernels overlap batch k's (double buffering) while the host cuts the windows of batch
 // k + 2. Finished batches are handed out strictly in window order.
@@ -56,6 +67,7 @@ struct StreamTask {
   uint64_t searched = 0;  // start windows of the segments handed to the search launcher
   int rc = FAC_OK;
   std::string err;
+  bool batched = false;  // searched in one pass (else window by window)
   bool done = false;
 };
 
@@ -67,6 +79,9 @@ struct StreamWorker {
   bool stop = false;
   hipStream_t stream = nullptr;
   ScratchSet scratch;
+  // the window-documents batch, restaged in place from task to task and kept until stream_close: the
+  // expanded text (~36 MiB for a 32 MiB task) and 12 bytes per grapheme of its non-ASCII windows
+  WindowDocs docs;
 };
 
 namespace {
@@ -186,10 +201,12 @@ void splice_task(StreamCore& s, StreamWorker& w, StreamTask& t, const uint8_t* d
   s.cur_cv.notify_all();
 }
 
-// Search a batch of windows. An all-ASCII batch is staged once and searched as one launch over its
-// windows (stream_windows_batch: each window its own text, ranked and cut per window); otherwise each
-// window is staged and searched alone (its grapheme segmentation depends on where its text starts
-// and ends).
+// Search a task of windows. A task of one window stages and searches it alone. Any other task is
+// searched in one pass: all-ASCII text is staged once and its windows searched as one launch over
+// their union (stream_windows_batch: each window its own text, ranked and cut per window); text with
+// anything else, or a task that path declines, is uploaded once and searched as a batch whose
+// documents are the windows' texts (stream_windows_docs: a window's grapheme segmentation depends on
+// where its text starts and ends, so every window is staged as a document of its own).
 void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
   const bool replace = s.table != nullptr;
   // replace mode keeps the records at offsets of the task's text, which the splice reads
@@ -197,18 +214,20 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
   std::vector<fac_match> owned;
   std::vector<uint64_t> win_off(t.wins.size() + 1, 0);
   bool batched = false, staged = false;
-  Haystack h;  // the whole task's text (the batched path); resident until the splice is done
-  if (t.wins.size() > 1 && ascii_only(t.text.data(), t.text.size())) {
+  Haystack h;  // the whole task's text (the ASCII path); resident until the splice is done
+  void* up = nullptr;  // the same for the window-documents path
+  const bool multi = t.wins.size() > 1;
+  std::vector<uint64_t> wins(multi ? 4 * t.wins.size() : 0);
+  for (size_t i = 0; multi && i < t.wins.size(); ++i) {
+    wins[4 * i] = t.wins[i].off;
+    wins[4 * i + 1] = t.wins[i].off + t.wins[i].len;
+    wins[4 * i + 2] = t.wins[i].commit;
+    wins[4 * i + 3] = shift + t.wins[i].off;
+  }
+  if (multi && ascii_only(t.text.data(), t.text.size())) {
     t.rc = stage_haystack(*s.e, t.text.data(), t.text.size(), h, t.err, 1, w.stream);
     staged = true;
     if (!t.rc) {
-      std::vector<uint64_t> wins(4 * t.wins.size());
-      for (size_t i = 0; i < t.wins.size(); ++i) {
-        wins[4 * i] = t.wins[i].off;
-        wins[4 * i + 1] = t.wins[i].off + t.wins[i].len;
-        wins[4 * i + 2] = t.wins[i].commit;
-        wins[4 * i + 3] = shift + t.wins[i].off;
-      }
       uint64_t searched = 0;
       const int rc = stream_windows_batch(*s.e, h, wins.data(), t.wins.size(), s.threshold, s.prefilter, w.stream, owned,
                                           nullptr, t.err, &win_off, &searched);
@@ -220,6 +239,33 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
     }
     if (t.rc) batched = true;  // a staging failure is the task's error
   }
+  if (multi && !batched && s.window_docs) {
+    const uint8_t* d_text = staged ? h.d_utf8 : nullptr;
+    if (!d_text) {
+      hipError_t he = hipSuccess;
+      up = call_scratch_take(t.text.size(), w.stream, &he);
+      if (he != hipSuccess || !up) {
+        up = nullptr;
+        t.rc = FAC_E_OOM;
+        t.err = std::string("hipMalloc: ") + hipGetErrorString(he);
+      } else if (hipMemcpyAsync(up, t.text.data(), t.text.size(), hipMemcpyHostToDevice, w.stream) != hipSuccess) {
+        t.rc = FAC_E_HIP;
+        t.err = "upload of a stream task's text failed";
+      }
+      d_text = static_cast<const uint8_t*>(up);
+    }
+    if (!t.rc) {
+      uint64_t searched = 0;
+      const int rc = stream_windows_docs(*s.e, w.docs, d_text, t.text.size(), wins.data(), t.wins.size(), s.threshold,
+                                         s.prefilter, w.stream, owned, t.err, win_off, &searched);
+      if (rc != FAC_E_UNSUPPORTED) {  // (unsupported: more windows or bytes than a batch holds)
+        t.rc = rc;
+        t.searched += searched;
+        batched = true;
+      }
+    }
+    if (t.rc) batched = true;
+  }
   if (!batched) {
     owned.clear();
     for (size_t i = 0; i < t.wins.size(); ++i) {
@@ -228,8 +274,10 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
     }
     win_off[t.wins.size()] = owned.size();
   }
+  t.batched = batched;
   if (replace) {
-    splice_task(s, w, t, staged && !t.rc ? h.d_utf8 : nullptr, owned, win_off);
+    const uint8_t* resident = t.rc ? nullptr : staged ? h.d_utf8 : static_cast<const uint8_t*>(up);
+    splice_task(s, w, t, resident, owned, win_off);
   } else if (!t.rc) {
     for (const fac_match& m : owned) {
       t.res.push_back(m);
@@ -238,6 +286,10 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
     }
   }
   if (staged) free_haystack(h);
+  if (up) {
+    (void)hipStreamSynchronize(w.stream);  // (an error path may leave the upload in flight)
+    call_scratch_give(up, w.stream);
+  }
   std::vector<uint8_t>().swap(t.text);
 }
 
@@ -312,6 +364,7 @@ int collect(StreamCore& s, bool all, std::string& err) {
       s.skipped += t->skipped;
     }
     s.windows_searched += t->searched;
+    ++(t->batched ? s.tasks_batched : s.tasks_single);
     delete t;
   }
   if (s.failed) {
@@ -432,6 +485,8 @@ StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const
     s->batch_bytes = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
   if (const char* v = diag_env("FAC_STREAM_READ_BYTES"))  // diagnostics: the reader's read size, many windows of a small input
     s->read = std::max<uint64_t>(1, std::strtoull(v, nullptr, 10));
+  if (const char* v = diag_env("FAC_STREAM_WINDOW_DOCS"))  // diagnostics: 0 = non-ASCII tasks window by window
+    s->window_docs = std::strtoull(v, nullptr, 10) != 0;
   if (window) s->window = window;
   s->overlap = e.max_match_graphemes + 1;  // stream_overlap (stream.rs:256-258)
   (void)hipSetDevice(e.device);
@@ -459,6 +514,7 @@ void stream_close(StreamCore* s) {
     w->th.join();
     (void)hipSetDevice(s->e->device);
     scratch_free(w->scratch);
+    free_batch(w->docs.b);
     if (w->stream) {
       call_scratch_release_stream(w->stream);
       (void)hipStreamDestroy(w->stream);

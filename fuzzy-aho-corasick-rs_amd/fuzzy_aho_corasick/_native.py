@@ -196,6 +196,10 @@ SIGNATURES = {
     "fac_replace_stream_open_ex": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint64,
                                                   ctypes.c_int32, _P(ctypes.c_void_p)]),
     "fac_replace_stream_windows_searched": (ctypes.c_uint64, [ctypes.c_void_p]),
+    "fac_stream_task_counts": (None, [ctypes.c_void_p, _u64p, _u64p]),
+    "fac_replace_stream_task_counts": (None, [ctypes.c_void_p, _u64p, _u64p]),
+    "fac_diag_stream_gather": (ctypes.c_int, [_engine_p, ctypes.c_char_p, ctypes.c_uint64, _u64p, ctypes.c_uint64,
+                                              ctypes.c_void_p, ctypes.c_uint64, _u64p]),
     "fac_haystack_symbol_ids": (ctypes.c_int64, [_engine_p, _hay_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_uint64]),
     "fac_stream_feed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int32,

@@ -745,6 +745,13 @@ class _Stream:
         """Start windows of the segments searched for the windows handed out so far."""
         return int(_native.lib.fac_stream_windows_searched(self._h))
 
+    def task_counts(self) -> Tuple[int, int]:
+        """(batched, single): the device tasks handed out so far that were searched in one pass, and
+        window by window."""
+        b, s = ctypes.c_uint64(), ctypes.c_uint64()
+        _native.lib.fac_stream_task_counts(self._h, ctypes.byref(b), ctypes.byref(s))
+        return int(b.value), int(s.value)
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and _native.lib is not None:
@@ -784,6 +791,13 @@ class _ReplaceStream:
     def windows_searched(self) -> int:
         """Start windows of the segments searched for the output handed out so far."""
         return int(_native.lib.fac_replace_stream_windows_searched(self._h))
+
+    def task_counts(self) -> Tuple[int, int]:
+        """(batched, single): the device tasks handed out so far that were searched in one pass, and
+        window by window."""
+        b, s = ctypes.c_uint64(), ctypes.c_uint64()
+        _native.lib.fac_replace_stream_task_counts(self._h, ctypes.byref(b), ctypes.byref(s))
+        return int(b.value), int(s.value)
 
     def counts(self) -> Tuple[int, int]:
         """(records replaced, records skipped by the cursor's guard) in the output handed out so far."""

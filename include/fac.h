@@ -714,6 +714,10 @@ int fac_stream_open_ex(const fac_engine* engine, float threshold, uint64_t windo
  * handed out so far: the graphemes of every window's text for a plain stream (bytes where a window's
  * text is ASCII), the lengths of every window's merged bitap windows for a pre-filtered one. */
 uint64_t fac_stream_windows_searched(const fac_stream* stream);
+/* Tests and hosts: the device tasks of this stream handed out so far that were searched in one
+ * pass (*batched: the ASCII union path or the window-documents path) and window by window
+ * (*single). Either pointer may be NULL. */
+void fac_stream_task_counts(const fac_stream* stream, uint64_t* batched, uint64_t* single);
 int fac_stream_feed(fac_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, fac_match** out,
                     uint64_t* n_out, uint8_t** text, uint64_t* text_len);
 uint64_t fac_stream_total(const fac_stream* stream);
@@ -743,6 +747,8 @@ int fac_replace_stream_open(const fac_engine* engine, const fac_replacements* re
 int fac_replace_stream_open_ex(const fac_engine* engine, const fac_replacements* replacements, float threshold,
                                uint64_t window_bytes, int32_t prefilter, fac_replace_stream** out);
 uint64_t fac_replace_stream_windows_searched(const fac_replace_stream* stream);
+/* fac_stream_task_counts of a replace stream. */
+void fac_replace_stream_task_counts(const fac_replace_stream* stream, uint64_t* batched, uint64_t* single);
 int fac_replace_stream_feed(fac_replace_stream* stream, const uint8_t* data, uint64_t len, int32_t eof, uint8_t** out,
                             uint64_t* out_len);
 /* Bytes handed out so far: replace_stream's return value (ReplaceCursor::written) after the feed with eof. */
@@ -782,6 +788,14 @@ void fac_edge_order(const uint32_t* cps, const uint64_t* off, uint64_t n, uint32
  * perm[a*bw .. a*bw + bw). sel_limit < 0: core's 16 partition rounds. Uses device 0. */
 int fac_diag_beam_select(const float* keys, const uint64_t* offs, uint64_t count, uint32_t bw, int32_t lds,
                          int32_t sel_limit, uint32_t* perm);
+
+/* Diagnostics (tests): the expanded text of a stream task alone. Window w is bytes
+ * [windows[2w], windows[2w] + windows[2w + 1]) of the len bytes at utf8 (ranges may overlap); the
+ * device copies them one after the other into `out` (cap bytes; the lengths summed must fit) and
+ * writes the n_windows + 1 document offsets to `offsets`. FAC_E_INVALID for a range outside the
+ * text. Uses the engine's device. */
+int fac_diag_stream_gather(const fac_engine* engine, const uint8_t* utf8, uint64_t len, const uint64_t* windows,
+                           uint64_t n_windows, uint8_t* out, uint64_t cap, uint64_t* offsets);
 
 #ifdef __cplusplus
 }
