@@ -104,11 +104,74 @@ __device__ __forceinline__ int32_t node_limits(const SearchParams& P, uint32_t n
   return P.pats[pi].has_limits ? pi : -1;
 }
 
+// Compile-time configuration of the window kernels (*Specialised instances*). The
+// flag-like SearchParams fields that run_window, bfs_window_body, lane_window_kernel and their
+// per-batch helpers read go through the cf_* accessors below: CfGeneric reads P (every engine, every
+// knob), CfPlain fixes them to the values of the plain engine -- a fixed edit budget (mef 1..6, no
+// per-pattern or global limits path), no non-ASCII similarity pairs, the goto fast path, no auto-beam
+// counting, no live_nqmax and no diagnostics knob -- and to the kernel's role (BUILD: rc_mode == 2,
+// the cache builds; else a main pass, rc_mode 0 or 1). Numeric values (beam, penalties, thr, mef
+// itself) stay run-time. The host picks the instance (plain_engine, below the kernels).
+struct CfGeneric {
+  static constexpr bool fixed = false;  // (the accessors read nothing else of it)
+};
+template <bool BUILD>
+struct CfPlain {
+  static constexpr bool fixed = true;
+  static constexpr bool build = BUILD;           // P.rc_mode == 2
+  static constexpr bool fast_edits = true;       // P.mef != 255
+  static constexpr bool pattern_limits = false;  // P.has_pattern_limits
+  static constexpr bool sim_pairs = false;       // P.n_sim != 0
+  static constexpr bool gt_fast = true;          // P.gt_fast
+  static constexpr bool win_counts = false;      // P.win_counts (auto-beam counting pass)
+  static constexpr bool live_nqmax = false;      // P.live_nqmax != 0
+  static constexpr bool diag = false;            // P.lane_debug, P.dup_cut, P.beam_canonical, P.rc_full_sweep
+};
+// a field as P holds it (CfGeneric: the very expression the kernels had), or the plain engine's value
+#define FAC_CF_FIELD(name, field, plain_value)                                   \
+  template <typename CF>                                                         \
+  __device__ __forceinline__ auto name(const SearchParams& P) -> decltype(P.field) { \
+    if constexpr (CF::fixed) return (decltype(P.field))(plain_value);            \
+    else return P.field;                                                         \
+  }
+FAC_CF_FIELD(cf_pattern_limits, has_pattern_limits, CF::pattern_limits)
+FAC_CF_FIELD(cf_n_sim, n_sim, CF::sim_pairs)  // (0 pairs)
+FAC_CF_FIELD(cf_gt_fast, gt_fast, CF::gt_fast)
+FAC_CF_FIELD(cf_live_nqmax, live_nqmax, CF::live_nqmax)  // (0: no limit)
+FAC_CF_FIELD(cf_lane_debug, lane_debug, CF::diag)
+FAC_CF_FIELD(cf_dup_cut, dup_cut, CF::diag)
+FAC_CF_FIELD(cf_beam_canonical, beam_canonical, CF::diag)
+FAC_CF_FIELD(cf_rc_full_sweep, rc_full_sweep, CF::diag)
+#undef FAC_CF_FIELD
+template <typename CF>
+__device__ __forceinline__ bool cf_build(const SearchParams& P) {  // the kernel's role: a cache build
+  if constexpr (CF::fixed) return CF::build;
+  else return P.rc_mode == 2;
+}
+template <typename CF>
+__device__ __forceinline__ int32_t cf_rc_mode(const SearchParams& P) {  // (a plain main pass keeps 0 / 1 run-time)
+  if constexpr (CF::fixed) {
+    if constexpr (CF::build) return 2;
+  }
+  return P.rc_mode;
+}
+template <typename CF>
+__device__ __forceinline__ bool cf_fast_edits(const SearchParams& P) {  // the edit model: a fixed budget, mef 1..6
+  if constexpr (CF::fixed) return CF::fast_edits;
+  else return P.mef != 255u;
+}
+template <typename CF>
+__device__ __forceinline__ uint32_t* cf_win_counts(const SearchParams& P) {
+  if constexpr (CF::fixed) return nullptr;
+  else return P.win_counts;
+}
+
 // get_similarity (search.rs:76-82) -> Similarity::get (structs.rs:82-92)
+template <typename CF = CfGeneric>
 __device__ __forceinline__ float similarity(const SearchParams& P, uint32_t a, uint32_t b) {
   if (a == b) return 1.0f;
   if (a < 128u && b < 128u) return P.sim_ascii[a * 128u + b];
-  if (P.n_sim == 0) return 0.0f;
+  if (cf_n_sim<CF>(P) == 0) return 0.0f;
   const uint64_t key = ((uint64_t)a << 32) | b;
   uint32_t lo = 0, hi = P.n_sim;
   while (lo < hi) {
@@ -1044,12 +1107,13 @@ __device__ __forceinline__ bool visited_check(KState* vis, uint32_t& vcount, con
 
 // Emission (search.rs:659-737) for one accepted state; lanes spread over the node's output list.
 // Called in FIFO pop order, so the per-window best list keeps the reference's first-found ties.
+template <typename CF = CfGeneric>
 __device__ void emit_state(const SearchParams& P, EmitList& EL, uint32_t me_rel, float pen, uint32_t packed,
                            uint32_t node, unsigned& err) {
   const uint2 orr = P.out_range[node];
   const uint32_t out_begin = orr.x, out_end = orr.y;
   const uint32_t lane = lane_id();
-  const bool fast = P.mef != 255u;
+  const bool fast = cf_fast_edits<CF>(P);
   const uint32_t edits = edits_of(packed);
   const uint32_t ins = packed & 0xFFu, del = (packed >> 8) & 0xFFu, sub = (packed >> 16) & 0xFFu, swp = packed >> 24;
   for (uint32_t base = out_begin; base < out_end; base += 64) {
@@ -1099,11 +1163,11 @@ __device__ __forceinline__ int64_t wave_find_gid(const SearchParams& P, uint32_t
   return -1;
 }
 
-template <uint32_t QCAP, bool MAP>
+template <uint32_t QCAP, bool MAP, typename CF = CfGeneric>
 __device__ void expand_wide(const SearchParams& P, const SegDesc& S, KState* q, uint32_t head, uint32_t& tail,
                             const KState& st, const DevNode& nd, uint64_t start, unsigned& err) {
   const uint32_t lane = lane_id();
-  const bool fast = P.mef != 255u;
+  const bool fast = cf_fast_edits<CF>(P);
   const uint64_t n = S.n;
   const float pen = st.pen;
   const float remaining = __fsub_rn(P.max_penalties, pen);  // :648
@@ -1111,7 +1175,7 @@ __device__ void expand_wide(const SearchParams& P, const SegDesc& S, KState* q, 
   const uint32_t edits = edits_of(packed);
   const uint32_t j_rel = st.jm & 0xFFFFu, me_rel = st.jm >> 16;
   const uint64_t j = start + j_rel;
-  const int32_t nlim = P.has_pattern_limits ? node_limits(P, st.node) : -1;  // :653-657
+  const int32_t nlim = cf_pattern_limits<CF>(P) ? node_limits(P, st.node) : -1;  // :653-657
     const bool is_last_edit = fast && edits + 1u >= P.mef;  // :742
     const uint32_t cur_ch = j < n ? text_char(P, S, j, err) : 0u;
     // Nodes with <= 64 edges (all but the top trie levels) are handled from one register-resident
@@ -1183,7 +1247,7 @@ __device__ void expand_wide(const SearchParams& P, const SegDesc& S, KState* q, 
           if (keep) {
             const uint32_t child = nx & EDGE_NEXT_MASK;
             keep = !(exact_next >= 0 && child == (uint32_t)exact_next);
-            const float sim = similarity(P, ch, cur_ch);
+            const float sim = similarity<CF>(P, ch, cur_ch);
             keep = keep && !(sim < P.min_sym);
             const float penalty = __fmul_rn(P.p_sub, __fsub_rn(1.0f, sim));
             keep = keep && !(penalty > remaining);
@@ -1308,17 +1372,18 @@ struct Prep {
 constexpr uint32_t PF_SUB = 1u, PF_DEL = 2u, PF_LAST = 4u, PF_CSB = 8u, PF_NEXT = 16u, PF_CUR = 32u, PF_SWAP = 64u,
                    PF_EX = 128u, PF_INS = 256u;
 
+template <typename CF = CfGeneric>
 __device__ Prep lane_prep(const SearchParams& P, const SegDesc& S, const KState& st, const DevNode& nd, uint64_t start,
                           uint32_t c0, uint32_t c1, uint4 own_sb) {  // c0/c1: text at j / j + 1 (0 past the end)
   Prep r{0u, 0u, 0u, 0u, 0.0f};
-  const bool fast = P.mef != 255u;
+  const bool fast = cf_fast_edits<CF>(P);
   const uint64_t n = S.n;
   r.remaining = __fsub_rn(P.max_penalties, st.pen);  // :648
   const uint32_t packed = st.packed;
   const uint32_t edits = edits_of(packed);
   const uint32_t j_rel = st.jm & 0xFFFFu, me_rel = st.jm >> 16;
   const uint64_t j = start + j_rel;
-  const int32_t nlim = P.has_pattern_limits ? node_limits(P, st.node) : -1;
+  const int32_t nlim = cf_pattern_limits<CF>(P) ? node_limits(P, st.node) : -1;
   const bool is_last_edit = fast && edits + 1u >= P.mef;  // :742
   const bool in_text = j < n;
   r.cur_ch = in_text ? c0 : 0u;
@@ -1417,7 +1482,7 @@ __device__ __forceinline__ int unit_owner(ExpScratch* X, uint32_t R, uint32_t nu
 // the units of all states are dealt to lanes in rounds of 64 (a lane-per-state loop would run
 // for the batch's largest degree). Per edge: the exact/swap first-char match (structs.rs:512-519),
 // substitution (:814-874) and deletion (:1055-1088) keep tests incl. the last-edit dead-end filter.
-template <uint32_t UK, bool MAP>
+template <uint32_t UK, bool MAP, typename CF = CfGeneric>
 __device__ void expand_units(const SearchParams& P, ExpScratch* X, const DevNode& nd, const Prep& pr, bool act,
                              uint64_t& msub, uint64_t& mdel, uint32_t& ex, uint32_t& xe) {
   const uint32_t lane = lane_id();
@@ -1466,7 +1531,7 @@ __device__ void expand_units(const SearchParams& P, ExpScratch* X, const DevNode
       }
       fe = (ok && ex_on && fe == 0u && mex) ? enc : fe;
       fx = (ok && swap_ok && fx == 0u && msw) ? enc : fx;
-      const float sim = similarity(P, ed.ch, cur);
+      const float sim = similarity<CF>(P, ed.ch, cur);
       const float penalty = __fmul_rn(P.p_sub, __fsub_rn(1.0f, sim));
       const bool sb_next = child_out || (have_next && sb_word_bit(csb, nxt));
       const bool sb_cur = child_out || (have_cur && sb_word_bit(csb, cur));
@@ -1510,8 +1575,9 @@ __device__ __forceinline__ bool filt_has(uint32_t f, uint32_t c) { return (f >> 
 // with text[j]'s first char is the exact edge unless two edges share a first char. When none of
 // these can pass, the state has no substitution at all and the O(1) expansion applies (C3: most
 // states past the first edit read a non-ASCII char or a space).
+template <typename CF = CfGeneric>
 __device__ __forceinline__ bool no_subs(const SearchParams& P, const DevNode& nd, uint32_t cur, float remaining) {
-  if (P.n_sim != 0 || (nd.degf & NODE_DUP_CH)) return false;
+  if (cf_n_sim<CF>(P) != 0 || (nd.degf & NODE_DUP_CH)) return false;
   if (cur >= 128u || !(nd.degf & NODE_ASCII_EDGE)) return true;
   return __fmul_rn(P.p_sub, __fsub_rn(1.0f, P.sim_ascii[128u * 128u + cur])) > remaining;
 }
@@ -1556,7 +1622,7 @@ __device__ void expand_fast(const SearchParams& P, const KState& st, const DevNo
 
 // Per-state completion: exact successor, the exact edge leaves the substitution set, swap target
 // goto(goto(node, text[j+1]), text[j]) (:945-967), push count.
-template <bool MAP>
+template <bool MAP, typename CF = CfGeneric>
 __device__ LaneExp lane_finish(const SearchParams& P, const SegDesc& S, uint64_t start, const KState& st,
                                const DevNode& nd, const Prep& pr, uint64_t msub, uint64_t mdel, uint32_t ex,
                                uint32_t xe, unsigned& err) {
@@ -1573,7 +1639,7 @@ __device__ LaneExp lane_finish(const SearchParams& P, const SegDesc& S, uint64_t
       if (gt_get(P, GT_VALID | GT_GOTO | ((uint64_t)(xe & CHILD26_MASK) << 21) | pr.cur_ch, true, g))
         x.swap = (int64_t)(g & CHILD26_MASK);
     }
-    if (x.swap >= 0 && P.mef == 255u) {  // within_limits_swap_ahead with node2's limits (:962-967)
+    if (x.swap >= 0 && !cf_fast_edits<CF>(P)) {  // within_limits_swap_ahead with node2's limits (:962-967)
       const uint32_t packed = st.packed, edits = edits_of(packed);
       const Lim m = pick_limits(P, node_limits(P, (uint32_t)x.swap));
       if (!(m.has ? (lim_lt(m.l.edits, edits) && lim_lt(m.l.swp, packed >> 24)) : false)) x.swap = -1;
@@ -1611,7 +1677,7 @@ __device__ __forceinline__ uint32_t nth_set_bit(uint64_t m, uint32_t r) {
 // substitutions (edge order), swap, insertion, deletions (edge order), written at the state's
 // exclusive-prefix offset. The owner lane writes exact/swap/insertion; substitutions and deletions
 // are written by the units that cover their edges (balanced like expand_units).
-template <uint32_t QCAP, uint32_t UK, bool MAP>
+template <uint32_t QCAP, uint32_t UK, bool MAP, typename CF = CfGeneric>
 __device__ void push_units(const SearchParams& P, ExpScratch* X, KState* q, uint32_t base, const KState& st,
                            const DevNode& nd, const LaneExp& x, uint32_t cur_ch, bool act) {
   const uint32_t lane = lane_id();
@@ -1671,7 +1737,7 @@ __device__ void push_units(const SearchParams& P, ExpScratch* X, KState* q, uint
       const DevEdge ed = P.edges[o_eb + e];
       const uint32_t child = ed.next & EDGE_NEXT_MASK;
       if (is_sub) {
-        const float sim = similarity(P, ed.ch, o_cur);
+        const float sim = similarity<CF>(P, ed.ch, o_cur);
         const float penalty = __fmul_rn(P.p_sub, __fsub_rn(1.0f, sim));
         const uint32_t o_j1 = (o_jm & 0xFFFFu) + 1u;
         q[(o_sb + r) & (QCAP - 1)] = KState{child, o_j1 | (o_j1 << 16), __fadd_rn(o_pen, penalty), o_packed + 0x10000u};
@@ -1824,7 +1890,28 @@ __global__ void slot_init_kernel(unsigned int* ring, unsigned int* ctr, uint32_t
 // HBM (the HBM rungs): vis and q point into the wave slot's global scratch region; every exchange of
 // ring or table data between lanes is fenced (frontier_sync), claim has HBM_CLAIM_WORDS.
 constexpr uint32_t LIVE_CAP = 256;
-template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LIVE = false, bool HBM = false>
+// run_window LIVE: the snapshot's nv check entries (at src) into the live table, cleared first. In the
+// plain instance a real call (most windows never need it): pointers and a count by value -- a reference
+// to P or to a caller's local would give that object a stack slot for the whole window loop (DESIGN.md
+// §5 *Scratch-resident `tail`*). It takes the block's registers out of the batch loop's allocation.
+__device__ __forceinline__ void live_table_fill(KState* live, const uint4* src, uint32_t nv) {
+  const uint32_t lane = lane_id();
+  for (uint32_t i = lane; i < LIVE_CAP; i += 64) live[i].node = EMPTY;
+  __builtin_amdgcn_wave_barrier();
+  for (uint32_t i = lane; i < nv; i += 64) {
+    const uint4 w = src[i];
+    uint32_t slot = vis_hash(KState{w.x, w.y, 0.f, w.w}) & (LIVE_CAP - 1);
+    while (atomicCAS(&live[slot].node, EMPTY, w.x) != EMPTY) slot = (slot + 1) & (LIVE_CAP - 1);
+    live[slot].jm = w.y;
+    live[slot].pen = __uint_as_float(w.z);
+    live[slot].packed = w.w;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+__device__ __attribute__((noinline)) void live_table_fill_call(KState* live, const uint4* src, uint32_t nv) {
+  live_table_fill(live, src, nv);
+}
+template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LIVE = false, bool HBM = false, typename CF = CfGeneric>
 __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegDesc& S, KState* vis, KState* q, uint32_t* claim,
                            uint32_t& cseq, EmitList& EL, uint64_t start, const RcHit& rc, uint64_t& popped,
                            uint64_t& cached, unsigned& err, uint32_t& head_out, uint32_t& vcount_out,
@@ -1836,7 +1923,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
   const uint32_t lane = lane_id();
   const uint64_t popped_w0 = popped;  // diagnostics: this window's pops
   if constexpr (LIVE)  // a window resuming with a long queue would most likely beam: the exact variant takes it
-    if (P.live_nqmax && rc.off != EMPTY && rc.tail - rc.head > P.live_nqmax) {
+    if (cf_live_nqmax<CF>(P) && rc.off != EMPTY && rc.tail - rc.head > cf_live_nqmax<CF>(P)) {
       err |= ERR_QUEUE;
       head_out = rc.head;
       vcount_out = 0;
@@ -1859,7 +1946,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
   if constexpr (LIVE) {
     const uint32_t nv = rc.off != EMPTY ? (rc.nv_nel & 0xFFFFu) : 0u;
     if (nv) jlive = P.rc_pool[rc.off + 1].y;  // jcheck | ncheck << 16
-    if (P.lane_debug && lane == 0) atomicAdd(&g_live_dbg[jlive ? 4 : 5], 1ull);
+    if (cf_lane_debug<CF>(P) && lane == 0) atomicAdd(&g_live_dbg[jlive ? 4 : 5], 1ull);
   }
   // cache builds of beamed engines: jbeam = 1 + the largest j popped before the last beam event of the
   // snapshot chain (0: none). Only dedup entries popped before a beam can have beam-pruned subtrees,
@@ -1867,7 +1954,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
   // jp1: 1 + the largest j popped in the chain so far (0: none), kept per lane (the lanes' committed
   // states) and reduced over the wave only at beam events and at the end
   uint32_t jp1 = 0, jbeam = 0;
-  const bool track_beam = P.rc_mode == 2 && P.beam;
+  const bool track_beam = cf_build<CF>(P) && P.beam;
   if (track_beam && rc.off != EMPTY) {
     const uint4 h1 = P.rc_pool[rc.off + 1];
     jbeam = h1.z;
@@ -1928,7 +2015,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
         if constexpr (HBM) {  // (no canonical rule here: its keys are QCAP / 64 registers per lane)
           beam_select<QCAP>(q, head, tail, P.beam, bsel, P.sel_limit);
           wave_mem_fence();  // the survivors written back to the ring, before the next pop
-        } else if (P.beam_canonical) beam_select_canonical<QCAP>(q, head, tail, P.beam);  // diagnostics
+        } else if (cf_beam_canonical<CF>(P)) beam_select_canonical<QCAP>(q, head, tail, P.beam);  // diagnostics
         else if constexpr (QCAP <= 256) beam_select_lds<QCAP>(q, head, tail, P.beam, claim, P.sel_limit);  // :577-589
         else beam_select<QCAP>(q, head, tail, P.beam, bsel, P.sel_limit);
         tail = head + P.beam;  // truncate(bw) (:587)
@@ -1940,7 +2027,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       // never shorter than the dedup queue at the same pop). Here it would: the window is spilled
       // and re-run from its start (snapshot) on a dedup variant.
       err |= ERR_QUEUE;
-      if (P.lane_debug && lane == 0) {  // spilled windows: their live pops, snapshot queue, pops / queue at the spill
+      if (cf_lane_debug<CF>(P) && lane == 0) {  // spilled windows: their live pops, snapshot queue, pops / queue at the spill
         atomicAdd(&g_live_dbg[6], 1ull);
         atomicAdd(&g_live_dbg[7], (unsigned long long)(popped - popped_w0));
         atomicAdd(&g_live_dbg[8], (unsigned long long)(rc.off != EMPTY ? rc.tail - rc.head : 1u));
@@ -1950,7 +2037,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       break;
     }
     // cache build: stop before the first state that reads text past the key
-    if (P.rc_mode == 2 && (q[head & (QCAP - 1)].jm & 0xFFFFu) + 1u >= P.rc_k) break;
+    if (cf_build<CF>(P) && (q[head & (QCAP - 1)].jm & 0xFFFFu) + 1u >= P.rc_k) break;
     PROF_ACC(0, t0);
     PROF_T(t1);
     const uint32_t B = min(tail - head, 64u);
@@ -1999,22 +2086,15 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
           err |= ERR_QUEUE;
           break;
         }
-        for (uint32_t i = lane; i < LIVE_CAP; i += 64) live[i].node = EMPTY;
-        __builtin_amdgcn_wave_barrier();
-        const uint4* src = P.rc_pool + rc.off + RC_HDR + nq;
-        for (uint32_t i = lane; i < nv; i += 64) {
-          const uint4 w = src[i];
-          uint32_t slot = vis_hash(KState{w.x, w.y, 0.f, w.w}) & (LIVE_CAP - 1);
-          while (atomicCAS(&live[slot].node, EMPTY, w.x) != EMPTY) slot = (slot + 1) & (LIVE_CAP - 1);
-          live[slot].jm = w.y;
-          live[slot].pen = __uint_as_float(w.z);
-          live[slot].packed = w.w;
+        if constexpr (CF::fixed) {
+          live_table_fill_call(live, P.rc_pool + rc.off + RC_HDR + nq, nv);
+        } else {
+          live_table_fill(live, P.rc_pool + rc.off + RC_HDR + nq, nv);
         }
-        __builtin_amdgcn_wave_barrier();
         live_loaded = true;
       }
       if (chk) vis_lookup<LIVE_CAP>(live, st, found, stored_bits, vslot);
-      if (P.lane_debug && lane == 0) {
+      if (cf_lane_debug<CF>(P) && lane == 0) {
         atomicAdd(&g_live_dbg[2], (unsigned long long)__popcll(__ballot(chk)));
         atomicAdd(&g_live_dbg[3], (unsigned long long)__popcll(__ballot(found && __uint_as_float(stored_bits) <= st.pen)));
       }
@@ -2035,8 +2115,8 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       if constexpr (VCAP > 0)
         if (visited_check<VCAP, HBM>(vis, vcount, s0, P.exact_dedup != 0, err)) continue;
       const DevNode n0 = P.nodes[s0.node];
-      if (node_has_out(n0)) emit_state(P, EL, s0.jm >> 16, s0.pen, s0.packed, s0.node, err);
-      expand_wide<QCAP, MAP>(P, S, q, head, tail, s0, n0, start, err);
+      if (node_has_out(n0)) emit_state<CF>(P, EL, s0.jm >> 16, s0.pen, s0.packed, s0.node, err);
+      expand_wide<QCAP, MAP, CF>(P, S, q, head, tail, s0, n0, start, err);
       if constexpr (HBM) wave_mem_fence();  // its table insert and push_lanes' ring stores, before the next pop
       PROF_ACC(2, t2);
       if (any_err(err)) break;
@@ -2049,7 +2129,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
     const bool act = alive && lane < Bc;
     Prep pr{0u, 0u, 0u, 0u, 0.0f};
     PROF_T(tb0);
-    if (act) pr = lane_prep(P, S, st, nd, start, c0, c1, nd.sb);
+    if (act) pr = lane_prep<CF>(P, S, st, nd, start, c0, c1, nd.sb);
     if constexpr (MAP) {
       pr.gcur = g0;
       pr.gnx = g1;
@@ -2059,13 +2139,13 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
     uint64_t msub = 0, mdel = 0;
     uint32_t ex = 0u, xe = 0u;
     const bool fast =
-        act && P.gt_fast && (!(pr.flags & PF_SUB) || P.p_sub <= pr.remaining || no_subs(P, nd, pr.cur_ch, pr.remaining));
+        act && cf_gt_fast<CF>(P) && (!(pr.flags & PF_SUB) || P.p_sub <= pr.remaining || no_subs<CF>(P, nd, pr.cur_ch, pr.remaining));
 #ifdef FAC_PHASE_PROF
     prof_acc[12] += (uint64_t)__popcll(__ballot(act && !fast));
     prof_acc[13] += (uint64_t)__popcll(__ballot(fast));
 #endif
     if (__ballot(act && !fast))  // per-edge path for the states similarity can prune
-      expand_units<FAC_UK, MAP>(P, reinterpret_cast<ExpScratch*>(claim), nd, pr, act && !fast, msub, mdel, ex, xe);
+      expand_units<FAC_UK, MAP, CF>(P, reinterpret_cast<ExpScratch*>(claim), nd, pr, act && !fast, msub, mdel, ex, xe);
     if (fast) expand_fast(P, st, nd, pr, aux, msub, mdel, ex, xe);
 #if defined(FAC_DUP) && FAC_DUP == 1
     if (fast) {
@@ -2084,7 +2164,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
 #endif
     PROF_ACC(10, tb1);
     PROF_T(tb2);
-    if (act) x = lane_finish<MAP>(P, S, start, st, nd, pr, msub, mdel, ex, xe, err);
+    if (act) x = lane_finish<MAP, CF>(P, S, start, st, nd, pr, msub, mdel, ex, xe, err);
 #if defined(FAC_DUP) && FAC_DUP == 2
     if (act) {
       KState s2{opq(st.node), opq(st.jm), opqf(st.pen), opq(st.packed)};
@@ -2109,7 +2189,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
     const uint32_t P0 = tail - head;
     const bool trig = lane >= 1 && lane < Bc && P.beam && (P0 - lane + excl > beam2);
     const bool ovf = lane < Bc && (P0 - lane - 1 + incl > QCAP);
-    const bool past = P.rc_mode == 2 && lane < Bc && (st.jm & 0xFFFFu) + 1u >= P.rc_k;  // cache build
+    const bool past = cf_build<CF>(P) && lane < Bc && (st.jm & 0xFFFFu) + 1u >= P.rc_k;  // cache build
     const uint64_t mcut = __ballot(trig) | __ballot(ovf) | __ballot(past);
 #ifdef FAC_PHASE_PROF
     {  // cut reasons (the first cut lane's): 25 beam trigger, 26 ring, 27 key end (builds), 29 wide node
@@ -2165,7 +2245,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       const bool loser = wr && w != lane && !same;
       uint64_t dup = __ballot(same);
       const uint64_t lmask = __ballot(loser);
-      if (lmask && P.dup_cut) {
+      if (lmask && cf_dup_cut<CF>(P)) {
         bool d2 = false;
         uint64_t mm = lmask;
         while (mm) {
@@ -2180,7 +2260,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
       prof_acc[28] += (dup && (uint32_t)first_lane(dup) < Bc) ? 1 : 0;  // batches holding an in-batch duplicate
       prof_acc[30] += (uint64_t)__popcll(dup & ((Bc >= 64u) ? ~0ull : ((1ull << Bc) - 1ull)));  // duplicate lanes
 #endif
-      if (P.dup_cut) {  // diagnostics (FAC_DUP_CUT): the round-5 rule, cut before the first duplicate
+      if (cf_dup_cut<CF>(P)) {  // diagnostics (FAC_DUP_CUT): the round-5 rule, cut before the first duplicate
         if (dup) Bc = min(Bc, (uint32_t)first_lane(dup));  // lane 0 is never a duplicate
         dup = 0;
       }
@@ -2253,12 +2333,12 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
     while (mem) {
       const int l = first_lane(mem);
       mem &= mem - 1;
-      emit_state(P, EL, shfl_u32(st.jm, l) >> 16, shfl_f32(st.pen, l), shfl_u32(st.packed, l), shfl_u32(st.node, l),
+      emit_state<CF>(P, EL, shfl_u32(st.jm, l) >> 16, shfl_f32(st.pen, l), shfl_u32(st.packed, l), shfl_u32(st.node, l),
                  err);
     }
     PROF_ACC(5, t5);
     PROF_T(t6);
-    push_units<QCAP, FAC_UK, MAP>(P, reinterpret_cast<ExpScratch*>(claim), q, tail + excl2, st, nd, x, pr.cur_ch,
+    push_units<QCAP, FAC_UK, MAP, CF>(P, reinterpret_cast<ExpScratch*>(claim), q, tail + excl2, st, nd, x, pr.cur_ch,
                                   keep && x.count != 0);
 #if defined(FAC_DUP) && FAC_DUP == 4
     push_units<QCAP, FAC_UK, MAP>(P, reinterpret_cast<ExpScratch*>(claim), q, opq(tail + excl2), st, nd, x, opq(pr.cur_ch),
@@ -2293,7 +2373,7 @@ __device__ __forceinline__ uint32_t run_window(const SearchParams& P, const SegD
   wave_mem_fence();
   // a window that overflowed the frontier is spilled whole (re-run on a larger variant): no flush;
   // a cache build's representative is searched again by the main pass: no flush either
-  if (EL.n && P.rc_mode != 2 && !(wave_or(err) & (ERR_EMIT | ERR_QUEUE | ERR_VISITED))) {
+  if (EL.n && !cf_build<CF>(P) && !(wave_or(err) & (ERR_EMIT | ERR_QUEUE | ERR_VISITED))) {
     unsigned long long base = 0;
     if (lane == 0) base = atomicAdd(P.counters, (unsigned long long)EL.n);
     base = shfl_u64(base, 0);
@@ -3378,6 +3458,7 @@ __device__ __forceinline__ void lane_unpack(uint32_t w, uint32_t& jm, uint32_t& 
 struct LiveDedup {
   uint32_t off, n, jlive;
 };
+template <typename CF = CfGeneric>
 __device__ __forceinline__ bool live_dup(const SearchParams& P, const LiveDedup& L, const KState& st) {
   if (L.n == 0 || (st.jm & 0xFFFFu) + 1u > L.jlive) return false;
   bool hit = false;
@@ -3394,7 +3475,7 @@ __device__ __forceinline__ bool live_dup(const SearchParams& P, const LiveDedup&
       }
     if (done) break;
   }
-  if (P.lane_debug) {
+  if (cf_lane_debug<CF>(P)) {
     atomicAdd(&g_live_dbg[0], 1ull);
     if (hit) atomicAdd(&g_live_dbg[1], 1ull);
   }
@@ -3404,12 +3485,12 @@ __device__ __forceinline__ bool live_dup(const SearchParams& P, const LiveDedup&
 // The body of one lane-serial pop after its dedup decision (search.rs:629-1089): node ceiling,
 // emission into the lane's best list, expansion pushed at the tail. LINEAR: the lane's states are
 // a linear array (the cache build keeps its popped states for the dedup scans), else a ring.
-template <uint32_t QL, uint32_t ELN, bool LINEAR>
+template <uint32_t QL, uint32_t ELN, bool LINEAR, typename CF = CfGeneric>
 __device__ __forceinline__ void lane_expand(const SearchParams& P, uint32_t* s_q, uint4* s_e, const SegDesc& S,
                                             uint64_t start, const KState& st, uint32_t& status, uint32_t& head,
                                             uint32_t& tail, uint32_t& nel, unsigned& err) {
   const uint32_t lane = lane_id();
-  const bool fast = P.mef != 255u;
+  const bool fast = cf_fast_edits<CF>(P);
   // the state's reads go out together: node record, char filters, text at j and j + 1
   const DevNode nd = P.nodes[st.node];
   const uint4 aux = P.aux[st.node];
@@ -3458,7 +3539,7 @@ __device__ __forceinline__ void lane_expand(const SearchParams& P, uint32_t* s_q
     }
     if (status != LANE_RUN) return;
   }
-  const Prep pr = lane_prep(P, S, st, nd, start, c0, c1, nd.sb);
+  const Prep pr = lane_prep<CF>(P, S, st, nd, start, c0, c1, nd.sb);
   auto push = [&](uint32_t node, uint32_t jm, float pen, uint32_t pk) {
     uint32_t w;
     if ((LINEAR ? tail >= QL : tail - head >= QL) || !lane_pack(jm, pk, w)) {
@@ -3477,8 +3558,8 @@ __device__ __forceinline__ void lane_expand(const SearchParams& P, uint32_t* s_q
   // O(1) expansion (expand_fast: the wave kernel's decisions for a state whose similarity cannot drop
   // a substitution): the substitution / deletion sets come as edge masks, so only their set bits are
   // walked -- at the last edit the dead-end filters leave a few of a node's edges
-  if (P.gt_fast && node_deg(nd) <= 64u &&
-      (!(pr.flags & PF_SUB) || P.p_sub <= pr.remaining || no_subs(P, nd, pr.cur_ch, pr.remaining))) {
+  if (cf_gt_fast<CF>(P) && node_deg(nd) <= 64u &&
+      (!(pr.flags & PF_SUB) || P.p_sub <= pr.remaining || no_subs<CF>(P, nd, pr.cur_ch, pr.remaining))) {
     uint64_t msub = 0, mdel = 0;
     uint32_t ex = 0u, xe = 0u;
     expand_fast(P, st, nd, pr, aux, msub, mdel, ex, xe);
@@ -3490,7 +3571,7 @@ __device__ __forceinline__ void lane_expand(const SearchParams& P, uint32_t* s_q
       const uint32_t e = (uint32_t)__ffsll((unsigned long long)msub) - 1u;
       msub &= msub - 1;
       const DevEdge ed = P.edges[eb + e];
-      const float penalty = __fmul_rn(P.p_sub, __fsub_rn(1.0f, similarity(P, ed.ch, pr.cur_ch)));
+      const float penalty = __fmul_rn(P.p_sub, __fsub_rn(1.0f, similarity<CF>(P, ed.ch, pr.cur_ch)));
       if (!push(ed.next & EDGE_NEXT_MASK, jm1, __fadd_rn(st.pen, penalty), packed + 0x10000u)) return;
     }
     if (xe) {  // swap (:935-989): goto(goto(node, text[j+1]), text[j])
@@ -3525,7 +3606,7 @@ __device__ __forceinline__ void lane_expand(const SearchParams& P, uint32_t* s_q
   if (ex >= 0 && !push((uint32_t)ex, jm1, st.pen, packed)) return;  // exact (:776-800)
   // substitutions (:803-874), edge order, the exact edge excluded; none when similarity must be
   // positive and no edge can have it (no_subs)
-  if ((pr.flags & PF_SUB) && !(P.p_sub > pr.remaining && no_subs(P, nd, pr.cur_ch, pr.remaining))) {
+  if ((pr.flags & PF_SUB) && !(P.p_sub > pr.remaining && no_subs<CF>(P, nd, pr.cur_ch, pr.remaining))) {
     bool ok = true;
     for (uint32_t e0 = eb; e0 < ee && ok; e0 += 4) {
       DevEdge ed[4];
@@ -3534,7 +3615,7 @@ __device__ __forceinline__ void lane_expand(const SearchParams& P, uint32_t* s_q
 #pragma unroll
       for (uint32_t k = 0; k < 4; ++k) ed[k] = e0 + k < ee ? P.edges[e0 + k] : DevEdge{0u, 0u};
 #pragma unroll
-      for (uint32_t k = 0; k < 4; ++k) sim[k] = similarity(P, ed[k].ch, pr.cur_ch);
+      for (uint32_t k = 0; k < 4; ++k) sim[k] = similarity<CF>(P, ed[k].ch, pr.cur_ch);
 #pragma unroll
       for (uint32_t k = 0; k < 4; ++k)
         sbn[k] = (pr.flags & PF_LAST) && (pr.flags & PF_NEXT) && e0 + k < ee && sb_has(P, ed[k].next & EDGE_NEXT_MASK, pr.next_ch);
@@ -3586,7 +3667,7 @@ __device__ __forceinline__ void lane_expand(const SearchParams& P, uint32_t* s_q
   }
 }
 
-template <uint32_t QL, uint32_t ELN>
+template <uint32_t QL, uint32_t ELN, typename CF = CfGeneric>
 __device__ __forceinline__ void lane_step(const SearchParams& P, uint32_t* s_q, uint4* s_e, const SegDesc& S, uint64_t start,
                                           const LiveDedup& lv, uint32_t& status, uint32_t& head, uint32_t& tail,
                                           uint32_t& nel, uint32_t& pops, unsigned& err) {
@@ -3605,15 +3686,15 @@ __device__ __forceinline__ void lane_step(const SearchParams& P, uint32_t* s_q, 
   ++head;
   ++pops;
   const KState st{s_q[slot], jm0, __uint_as_float(s_q[QL * 64 + slot]), pk0};
-  if (live_dup(P, lv, st)) return;  // :618-622 against the snapshot's popped states
-  lane_expand<QL, ELN, false>(P, s_q, s_e, S, start, st, status, head, tail, nel, err);
+  if (live_dup<CF>(P, lv, st)) return;  // :618-622 against the snapshot's popped states
+  lane_expand<QL, ELN, false, CF>(P, s_q, s_e, S, start, st, status, head, tail, nel, err);
 }
 
 // Persistent lanes: a lane whose window finishes (or bails) takes the next listed window at once,
 // so a wave is not held by its slowest window; the wave lists unfinished windows from the lookup
 // results chunk by chunk as its idle lanes need them.
-template <uint32_t QL, uint32_t ELN>
-__global__ __launch_bounds__(64) void lane_window_kernel(SearchParams P) {
+template <uint32_t QL, uint32_t ELN, typename CF>
+__device__ __forceinline__ void lane_window_body(const SearchParams& P) {
   __shared__ uint32_t s_q[3 * QL * 64];  // ring slot i of lane l at i * 64 + l, three planes
   // best lists in this workgroup's slice of the emit scratch (read only on emissions; keeping them out
   // of LDS lets more waves share a CU): entry i of lane l at i * 64 + l
@@ -3716,7 +3797,7 @@ __global__ __launch_bounds__(64) void lane_window_kernel(SearchParams P) {
       ++started;
     }
     ++trips;
-    if (status == LANE_RUN) lane_step<QL, ELN>(P, s_q, s_e, S, start, lv, status, head, tail, nel, pops, err);
+    if (status == LANE_RUN) lane_step<QL, ELN, CF>(P, s_q, s_e, S, start, lv, status, head, tail, nel, pops, err);
     const bool fin = status == LANE_OK, bail = status == LANE_BAIL;
     if (__ballot(fin || bail)) {  // finished windows write their records (one output atomic per wave)
       const uint32_t ne = fin ? nel : 0u;
@@ -3745,7 +3826,7 @@ __global__ __launch_bounds__(64) void lane_window_kernel(SearchParams P) {
   wave_add_counter(P.counters + 1, popped_lane);
   wave_add_counter(P.counters + 4, cached_lane);
   wave_add_counter(P.counters + 8, done_lane);
-  if (P.lane_debug) {  // diagnostics (FAC_RC_DEBUG): windows started / finished, pop steps, cycles
+  if (cf_lane_debug<CF>(P)) {  // diagnostics (FAC_RC_DEBUG): windows started / finished, pop steps, cycles
     const uint32_t st = (uint32_t)wave_inclusive_sum((uint32_t)started), dn = wave_inclusive_sum(done_lane);
     if (lane == 63) {
       atomicAdd(&g_lane_dbg[0], (unsigned long long)st);
@@ -3758,13 +3839,20 @@ __global__ __launch_bounds__(64) void lane_window_kernel(SearchParams P) {
   }
 }
 
+template <uint32_t QL, uint32_t ELN>
+__global__ __launch_bounds__(64) void lane_window_kernel(SearchParams P) {
+  lane_window_body<QL, ELN, CfGeneric>(P);
+}
+// (No plain instance: lane_window_body<12, 8, CfPlain<false>> is 17 % shorter and takes 96 VGPRs for 108, but
+// reloads more spilled SGPRs in its loop and ran 7.78 ms for 7.00 per C3 step)
+
 // LK: the window prologue looks snapshots up itself (cache builds); otherwise a main pass with the
 // prefix cache reads the hits rc_lookup_kernel stored.
 // HBM (the HBM rungs, bfs_window_kernel_hbm): the table and the ring are the wave slot's region of
 // P.bsel instead of LDS -- VCAP table entries, QCAP ring entries, then (beamed engines) the beam
 // selection's scratch, P.bsel_stride uint4 per slot. The launch has at most n_slots workgroups, so
 // slot_acquire never waits. Only the claim words (HBM_CLAIM_WORDS) stay in LDS.
-template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LK, bool LIVE = false, bool HBM = false>
+template <uint32_t VCAP, uint32_t QCAP, bool MAP, bool LK, bool LIVE = false, bool HBM = false, typename CF = CfGeneric>
 __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
   static_assert(!HBM || (!LK && !LIVE && VCAP > 0), "HBM rungs: main passes with a table only");
   __shared__ KState s_vis[(VCAP && !HBM) ? VCAP : 1];
@@ -3808,7 +3896,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
   };
   const uint64_t stride = (uint64_t)gridDim.x * P.chunk;
   // behind the lookups a chunk holds the open entries of each region it covers: one sub-range each
-  const bool regions = !LK && P.rc_mode == 1 && !P.win_list;
+  const bool regions = !LK && cf_rc_mode<CF>(P) == 1 && !P.win_list;
   for (uint64_t cb0 = P.dyn_chunks ? next_chunk() : (uint64_t)blockIdx.x * P.chunk; cb0 < P.total_windows;
        cb0 = P.dyn_chunks ? next_chunk() : cb0 + stride) {
     const uint64_t ce0 = min(cb0 + (uint64_t)P.chunk, P.total_windows);
@@ -3826,7 +3914,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
     // and the rest are skipped without their dependent segment / hit / pops loads (C2 1 GiB: 6K
     // live windows out of 1G).
     uint64_t live_groups = ~0ull;
-    if (!LK && P.rc_mode == 1 && !P.win_list && P.chunk > 256) {
+    if (!LK && cf_rc_mode<CF>(P) == 1 && !P.win_list && P.chunk > 256) {
       live_groups = 0ull;
       const uint32_t ng = (uint32_t)((ce - cb + 63) / 64);  // P.chunk <= 4096: at most 64 groups
       const uint32_t* hx = reinterpret_cast<const uint32_t*>(P.rc_hits);
@@ -3854,11 +3942,11 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
       RcHit hit{EMPTY, 0u, 0u, 0u, 0u};  // prefix-cache snapshot of this lane's window
       if (active) {
         vid = P.win_list ? P.win_list[v] : v;
-        wid = (!LK && P.rc_mode == 1) ? rc_window_of(P, vid) : vid;
+        wid = (!LK && cf_rc_mode<CF>(P) == 1) ? rc_window_of(P, vid) : vid;
         kl = find_seg(P, wid);
         const SegDesc S = P.segs[kl];
         start = S.w_begin + (wid - P.seg_prefix[kl]);
-        if (!LK && P.rc_mode == 1) {  // skip decision and lookup made by rc_lookup_kernel
+        if (!LK && cf_rc_mode<CF>(P) == 1) {  // skip decision and lookup made by rc_lookup_kernel
           const uint4 h = P.rc_hits[vid];
           hit = RcHit{h.x, h.y, h.z, h.w, P.rc_hit_pops[vid]};
           active = h.x != RC_DONE;
@@ -3867,16 +3955,16 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
         }
       }
       if constexpr (LK)
-        if (P.rc_mode != 0 && P.rc_ntab && active && P.rc_bhits) {  // rc_parent_kernel's lookup
+        if (cf_rc_mode<CF>(P) != 0 && P.rc_ntab && active && P.rc_bhits) {  // rc_parent_kernel's lookup
           const uint4 h = P.rc_bhits[v];
           hit = RcHit{h.x, h.y, h.z, h.w, P.rc_bpops[v]};
         }
-      if (LK && P.rc_mode == 1) {
+      if (LK && cf_rc_mode<CF>(P) == 1) {
         const bool resumed = active && hit.off != EMPTY;
         res_lane += resumed ? 1u : 0u;
         active = active && !flush_final(P, resumed, hit, kl, start, wid, cached_lane, triv_lane);
       }
-      if (P.rc_mode == 2) {
+      if (cf_build<CF>(P)) {
         // a representative whose parent snapshot has an empty queue ends at the parent: its own
         // snapshot would hold the same best list, so the key stays uncached (lookups fall through)
         const bool done = active && hit.off != EMPTY && hit.tail == hit.head && !P.rc_keep_final;
@@ -3904,14 +3992,14 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
         const uint64_t t_w0 = __builtin_amdgcn_s_memtime();
 #endif
         const uint32_t qlen =
-            run_window<VCAP, QCAP, MAP, LIVE, HBM>(P, S, w_vis, w_q, s_claim, cseq, EL, st, rc, popped, cached, err, qhead,
+            run_window<VCAP, QCAP, MAP, LIVE, HBM, CF>(P, S, w_vis, w_q, s_claim, cseq, EL, st, rc, popped, cached, err, qhead,
                                                    vcnt, s_live, jbeam, bsel
 #ifdef FAC_PHASE_PROF
                                               , prof_acc
 #endif
                                               );
 #ifdef FAC_WIN_HIST
-        if (lane == 0 && P.rc_mode != 2) {
+        if (lane == 0 && !cf_build<CF>(P)) {
           const uint32_t b = hist_bucket(popped - popped0);
           atomicAdd(&g_hist[b], 1ull);
           atomicAdd(&g_hist[6 + b], (unsigned long long)(popped - popped0));
@@ -3919,7 +4007,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
           atomicAdd(&g_hist[18 + b], rc.off != EMPTY ? 1ull : 0ull);
         }
 #endif
-        if (LK && P.rc_mode == 2) {  // cache build: entry = list position; what does not fit stays uncached
+        if (LK && cf_build<CF>(P)) {  // cache build: entry = list position; what does not fit stays uncached
 #ifdef FAC_PHASE_PROF
           struct EpAcc {
             uint64_t t;
@@ -3944,7 +4032,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
           // at least the smallest j in the queue (j never decreases along a path)
           // A final key (empty queue) has no future state, so no dedup entry is live: nv = jlive =
           // ncheck = 0 without a look at the table. FAC_RC_FULL_SWEEP=1 (A/B) sweeps it all the same.
-          const bool full = P.rc_full_sweep != 0;
+          const bool full = cf_rc_full_sweep<CF>(P) != 0;
           const bool sweep = nq != 0 || full;  // wave-uniform
           uint32_t jmin = 0xFFFFu;
           uint32_t nv = 0, jlive = 0;  // 1 + the largest j among the live entries (0: none)
@@ -4060,7 +4148,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
         }
         const bool overflow = (wave_or(err) & (ERR_QUEUE | ERR_VISITED)) != 0;
         const uint64_t w_id = shfl_u64(wid, l);
-        if (P.win_counts && !overflow && lane == 0) P.win_counts[w_id] = qlen;
+        if (cf_win_counts<CF>(P) && !overflow && lane == 0) P.win_counts[w_id] = qlen;
         if (overflow) {  // frontier overflow: spill the window
           const uint64_t id = shfl_u64(vid, l);
           if (lane == 0) {
@@ -4081,7 +4169,7 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
   if (lane == 0 && kept_snaps) atomicAdd(P.counters + 11, (unsigned long long)kept_snaps);  // sizes the lookup table
 #ifdef FAC_PHASE_PROF
   if (lane == 0) {
-    const int pb = P.rc_mode == 2 ? kProf : 0;
+    const int pb = cf_build<CF>(P) ? kProf : 0;
     for (int i = 0; i < kProf; ++i)
       if (i != 23 && i != 24) atomicAdd(&g_prof[pb + i], (unsigned long long)prof_acc[i]);
     atomicAdd(&g_prof[pb + 23], (unsigned long long)t_grp);
@@ -4135,6 +4223,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAC_BEAM_WA
 void rc_build_kernel(SearchParams P) {
   bfs_window_body<512, QCAP, false, true>(P);  // the prefix cache is off with mappings
 }
+// The plain engine's instances (CfPlain) of the kernels the C2 / C3 steps launch, each with
+// its generic twin's register budget; their own symbols, so profiles tell the two apart. The generic
+// kernels above serve every other engine, variant and knob (plain_engine picks).
+template <uint32_t QCAP>  // 256: beamed engines (C3); 512: unbeamed engines, whose main pass has a 512 ring (C2)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((FAC_BEAM_WAVES && QCAP <= 256) ? FAC_BEAM_WAVES : 1)))
+void rc_build_kernel_plain(SearchParams P) {
+  bfs_window_body<512, QCAP, false, true, false, false, CfPlain<true>>(P);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FAC_LIVE_WAVES))) void bfs_window_kernel_live_plain(SearchParams P) {
+  bfs_window_body<0, 256, false, false, true, false, CfPlain<false>>(P);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FAC_BEAM_WAVES ? FAC_BEAM_WAVES : 1)))
+void bfs_window_kernel_plain(SearchParams P) {  // <512, 256>: the beamed engines' spilled windows
+  bfs_window_body<512, 256, false, false, false, false, CfPlain<false>>(P);
+}
+// (No plain <0, 512> for the unbeamed engines' first variant: it gained nothing on C2)
 
 struct Variant {
   uint32_t vcap, qcap;  // vcap 0: no dedup table (unbeamed engines only)
@@ -4150,19 +4254,78 @@ uint32_t lds_pad() {
   return v;
 }
 
+// What the environment says about a pass's instances, read once per launch_pass (spec_env_read) and
+// not per launch: FAC_NO_SPECIALIZE=1 (A/B knob) and the diagnostics knobs that are copied into P only
+// late in a pass, after its cache builds (FAC_RC_DEBUG's device counters, FAC_LIVE_NQMAX), so that a
+// diagnostics run is one from its first launch; and whether FAC_RC_DEBUG wants the FAC_INSTANCE lines.
+struct SpecEnv {
+  bool generic = false;  // every launch takes the generic instance
+  bool lines = false;    // FAC_RC_DEBUG: print the instance each launch used
+};
+thread_local SpecEnv t_spec_env;
+
+// FAC_RC_DEBUG's device counters (P.lane_debug). FAC_RC_DEBUG=launch prints the host's lines only and
+// leaves the counters off, so the run is no diagnostics run and takes the instances production takes.
+bool rc_debug_counters() {
+  const char* e = diag_env("FAC_RC_DEBUG");
+  return e && std::strcmp(e, "launch") != 0;
+}
+
+void spec_env_read() {
+  const char* ns = diag_env("FAC_NO_SPECIALIZE");
+  t_spec_env.generic = (ns && ns[0] == '1') || rc_debug_counters() || diag_env("FAC_LIVE_NQMAX") != nullptr;
+  t_spec_env.lines = diag_env("FAC_RC_DEBUG") != nullptr;
+}
+
+// The plain engine (CfPlain): what a pass's parameters must be for its launches to take a specialised
+// instance. One of these false -- another edit model, similarity pairs beyond ASCII, no goto fast path,
+// mappings, the auto-beam counting pass, a key partition (host-side only: no window kernel reads kp_n),
+// any diagnostics knob -- and the launch takes the generic instance.
+bool plain_params(const SearchParams& P) {
+  const bool engine = P.mef != 255u && !P.has_pattern_limits && P.n_sim == 0 && P.gt_fast && !P.has_map;
+  const bool pass = !P.win_counts && P.kp_n <= 1u;
+  const bool knobs = !P.live_nqmax && !P.lane_debug && !P.dup_cut && !P.beam_canonical && !P.rc_full_sweep;
+  return engine && pass && knobs;
+}
+bool plain_engine(const SearchParams& P) { return !t_spec_env.generic && plain_params(P); }
+
+// FAC_RC_DEBUG: the instance a launch used (tests/test_gpu_specialized_kernels.py reads it)
+void instance_line(const char* kernel, bool plain) {
+  if (t_spec_env.lines) std::fprintf(stderr, "FAC_INSTANCE kernel=%s instance=%s\n", kernel, plain ? "plain" : "generic");
+}
+
 template <uint32_t Q>
 void launch_nd(uint32_t grid, hipStream_t s, const SearchParams& P) {
+  const bool plain = plain_engine(P);
   if constexpr (Q == 256)
     if (P.beam && !P.has_map) {
-      hipLaunchKernelGGL((bfs_window_kernel_live<Q>), dim3(grid), dim3(64), lds_pad(), s, P);
+      instance_line("bfs_window_kernel_live<256>", plain);
+      if (plain) hipLaunchKernelGGL(bfs_window_kernel_live_plain, dim3(grid), dim3(64), lds_pad(), s, P);
+      else hipLaunchKernelGGL((bfs_window_kernel_live<Q>), dim3(grid), dim3(64), lds_pad(), s, P);
       return;
     }
+  if (t_spec_env.lines) {
+    char name[48];
+    std::snprintf(name, sizeof(name), "bfs_window_kernel_nd<%u>", Q);
+    instance_line(name, false);
+  }
   if (P.has_map) hipLaunchKernelGGL((bfs_window_kernel_nd<Q, true>), dim3(grid), dim3(64), lds_pad(), s, P);
   else hipLaunchKernelGGL((bfs_window_kernel_nd<Q, false>), dim3(grid), dim3(64), lds_pad(), s, P);
 }
 
 template <uint32_t V, uint32_t Q>
 void launch_one(uint32_t grid, hipStream_t s, const SearchParams& P) {
+  if constexpr (V == 512 && Q == 256)  // the beamed engines' spill variant
+    if (plain_engine(P)) {
+      instance_line("bfs_window_kernel<512,256>", true);
+      hipLaunchKernelGGL(bfs_window_kernel_plain, dim3(grid), dim3(64), lds_pad(), s, P);
+      return;
+    }
+  if (t_spec_env.lines) {
+    char name[48];
+    std::snprintf(name, sizeof(name), "bfs_window_kernel<%u,%u>", V, Q);
+    instance_line(name, false);
+  }
   if (P.has_map) hipLaunchKernelGGL((bfs_window_kernel<V, Q, true>), dim3(grid), dim3(64), lds_pad(), s, P);
   else hipLaunchKernelGGL((bfs_window_kernel<V, Q, false>), dim3(grid), dim3(64), lds_pad(), s, P);
 }
@@ -4181,8 +4344,15 @@ constexpr Variant kVariants[] = {{0, 128},   {0, 256},   {0, 512},     {256, 256
 constexpr size_t kNumHbm = 3;
 
 // cache-build ring: at least the root's pushes after the popped root and the main pass's ring
-bool launch_rc_build(uint32_t need_q, uint32_t grid, hipStream_t s, const SearchParams& P) {
-  if (need_q <= 256) hipLaunchKernelGGL((rc_build_kernel<256>), dim3(grid), dim3(64), 0, s, P);
+// plain: the pass the build belongs to is a plain engine's (its own P alone does not say: a counting
+// pass's builds carry no win_counts)
+bool launch_rc_build(uint32_t need_q, uint32_t grid, hipStream_t s, const SearchParams& P, bool plain) {
+  plain = plain && need_q <= 512 && plain_engine(P);
+  if (need_q <= 4096)
+    instance_line(need_q <= 256 ? "rc_build_kernel<256>" : need_q <= 512 ? "rc_build_kernel<512>" : "rc_build_kernel<larger>", plain);
+  if (plain && need_q <= 256) hipLaunchKernelGGL((rc_build_kernel_plain<256>), dim3(grid), dim3(64), 0, s, P);
+  else if (plain) hipLaunchKernelGGL((rc_build_kernel_plain<512>), dim3(grid), dim3(64), 0, s, P);
+  else if (need_q <= 256) hipLaunchKernelGGL((rc_build_kernel<256>), dim3(grid), dim3(64), 0, s, P);
   else if (need_q <= 512) hipLaunchKernelGGL((rc_build_kernel<512>), dim3(grid), dim3(64), 0, s, P);
   else if (need_q <= 1024) hipLaunchKernelGGL((rc_build_kernel<1024>), dim3(grid), dim3(64), 0, s, P);
   else if (need_q <= 2048) hipLaunchKernelGGL((rc_build_kernel<2048>), dim3(grid), dim3(64), 0, s, P);
@@ -4450,6 +4620,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   const auto t_begin = std::chrono::steady_clock::now();
   auto host_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
   const bool timing = diag_env("FAC_TIMING") != nullptr;  // diagnostics: host wall-clock phases
+  spec_env_read();
   HIP_TRY(hipSetDevice(e.device));
   if (!stream) stream = e.stream;
   std::vector<SegDesc> segs;
@@ -4882,7 +5053,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       uint32_t qk = 256;  // launch_rc_build's ring
       while (qk < qbuild) qk <<= 1;
       if (int src = prep_slots(Q, bs, qk, true)) return src;
-      launch_rc_build(qbuild, grid, bs, Q);
+      launch_rc_build(qbuild, grid, bs, Q, plain_engine(P));
       const hipError_t le = hipGetLastError();
       if (le != hipSuccess) {
         err = std::string("kernel launch: ") + hipGetErrorString(le);
@@ -5157,6 +5328,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     // C3: lane 13.6 -> 7.1 ms, wave 41.0 -> 45.0 ms (133.5 vs 135.7 per step); fresh words 447.5 vs
     // 442.4 (profiles/r04ab/r04ag.txt). Round 2: 16 states against 8, lane 19 + wave 37 ms vs 6 + 58.
     // (The 8-, 16- and 32-state variants were removed in round 5; git history keeps them.)
+    instance_line("lane_window_kernel<12,8>", false);  // (the lane kernel has no plain instance: measured slower)
     hipLaunchKernelGGL((lane_window_kernel<12, 8>), dim3(lgrid), dim3(64), 0, stream, P);
     HIP_TRY(hipGetLastError());
     return FAC_OK;
@@ -5247,7 +5419,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       P.rc_region_cnt = static_cast<uint32_t*>(d_rcnt.p);
       P.rc_qcap = kVariants[vi].qcap;
       HIP_TRY(hipEventRecord(ev.a, stream));
-      P.lane_debug = diag_env("FAC_RC_DEBUG") ? 1 : 0;
+      P.lane_debug = rc_debug_counters() ? 1 : 0;
       // one region per wave turn, up to 32 waves per CU (7 fit: SGPR-bound)
       hipLaunchKernelGGL(rc_lookup_kernel, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_reg + 3) / 4, (uint64_t)cus * 8))),
                          dim3(256), 0, stream, P);
@@ -5258,7 +5430,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       const bool lane_on = !diag_env("FAC_NO_LANE") && !P.win_counts && !P.has_map;  // beamed: exact_dedup is set, bail-outs keep it exact
       if (lane_on) {
         if (!ev_lane) HIP_TRY(hipEventCreate(&ev_lane));
-        P.lane_debug = diag_env("FAC_RC_DEBUG") ? 1 : 0;
+        P.lane_debug = rc_debug_counters() ? 1 : 0;
         P.lane_popmax = (uint32_t)std::max<unsigned long>(1, diag_env("FAC_LANE_POPS") ? std::strtoul(diag_env("FAC_LANE_POPS"), nullptr, 10) : 32ul);
         P.live_nqmax = diag_env("FAC_LIVE_NQMAX") ? (uint32_t)std::strtoul(diag_env("FAC_LIVE_NQMAX"), nullptr, 10) : 0u;
         if (int lrc = launch_lane()) return lrc;
