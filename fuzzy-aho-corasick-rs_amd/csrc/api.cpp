@@ -15,6 +15,7 @@
 #include <map>
 #include <new>
 #include <string>
+#include <thread>
 #include <tuple>
 
 #include "fac_internal.h"
@@ -2017,6 +2018,50 @@ int fac_diag_beam_select(const float* keys, const uint64_t* offs, uint64_t count
   std::string err;
   int rc = fac::diag_beam_select(keys, offs, count, bw, lds, sel_limit, perm, err);
   return rc ? fail(rc, err) : FAC_OK;
+}
+
+void fac_engine_drop_prefix_cache(fac_engine* engine) {
+  if (!engine) return;
+  fac::Engine& e = engine->e;
+  if (hipSetDevice(e.device) != hipSuccess) return;
+  std::lock_guard<std::mutex> lk(e.rc_store.mu);  // waits for a search that holds the store
+  fac::rc_store_drop(e.rc_store);
+}
+
+int fac_diag_rc_store_decide(int32_t valid, uint64_t calls, uint64_t used, uint64_t cap, uint64_t last_call,
+                             int32_t pending, const uint32_t* have_sig, const uint32_t* want_sig, uint64_t want_cap,
+                             uint64_t cap_limit, const uint64_t* dir_slots, const uint64_t* dir_keys, int32_t busy,
+                             uint32_t sleep) {
+  if (!have_sig || !want_sig || !dir_slots || !dir_keys) return fail(FAC_E_INVALID, "null argument");
+  fac::RcStore s;
+  s.valid = valid != 0;
+  s.calls = calls;
+  s.sleep = sleep;
+  s.used = used;
+  s.cap = cap;
+  s.last_call = last_call;
+  s.pending = pending;
+  std::memcpy(s.sig, have_sig, sizeof(s.sig));
+  for (int k = 0; k < 9; ++k) {
+    s.dir[k].n_slots = (uint32_t)dir_slots[k];
+    s.dir[k].count = dir_keys[k];
+  }
+  // the call's own steps: try-lock first (from a second thread, as a second call would), then decide
+  std::unique_lock<std::mutex> held(s.mu, std::defer_lock);
+  if (busy) held.lock();
+  int r = fac::kRcBusy;
+  std::thread t([&] {
+    std::unique_lock<std::mutex> lk(s.mu, std::try_to_lock);
+    if (lk.owns_lock()) r = fac::rc_store_decide(s, want_sig, want_cap, cap_limit);
+  });
+  t.join();
+  return r;
+}
+
+const char* fac_diag_rc_reset_name(int32_t reset) { return fac::rc_reset_name(reset); }
+
+uint32_t fac_diag_rc_store_gate(uint64_t carried, uint64_t built, uint32_t backoff, uint64_t gate_min) {
+  return fac::rc_store_gate(carried, built, backoff, gate_min);
 }
 
 int fac_diag_stream_gather(const fac_engine* engine, const uint8_t* utf8, uint64_t len, const uint64_t* windows,

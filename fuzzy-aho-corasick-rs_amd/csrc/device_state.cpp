@@ -1,5 +1,7 @@
 // device_state.cpp — host-only device state: the engine's tables and streams, a haystack's device
 // buffers and host copies, the per-worker scratch sets. Allocations and copies only, no kernel.
+#include <cstring>
+
 #include "host_util.h"
 
 namespace fac {
@@ -68,9 +70,147 @@ int upload_engine(Engine& e, std::string& err) {
   return FAC_OK;
 }
 
+// ---------------------------------------------------------------- the engine's snapshot store
+// (launch_pass in search_kernels.hip is the only user)
+const char* rc_reset_name(int r) {
+  switch (r) {
+    case kRcKeep: return "none";
+    case kRcFresh: return "fresh";
+    case kRcSignature: return "signature";
+    case kRcPool: return "pool";
+    case kRcDirectory: return "directory";
+    case kRcBusy: return "busy";
+    case kRcGated: return "gated";
+    default: return "off";
+  }
+}
+
+bool rc_dir_fits(const RcStoreDir& d, uint64_t n) { return d.n_slots && 2 * (d.count + n) <= d.n_slots; }
+
+// Unlike text must not pay for the store (its probes, inserts and the directories' clears; measured
+// +1.0 % per call on fresh-word C3 haystacks): a carrying call of at least gate_min
+// entries that found under a tenth of them doubles the back-off (1 .. 64 calls), any other ends it.
+uint32_t rc_store_gate(uint64_t carried, uint64_t built, uint32_t backoff, uint64_t gate_min) {
+  if (carried + built < gate_min || 10 * carried >= carried + built) return 0;
+  return backoff ? std::min<uint32_t>(64, 2 * backoff) : 1;
+}
+
+int rc_store_decide(const RcStore& s, const uint32_t sig[kRcSigWords], uint64_t want_cap, uint64_t cap_limit) {
+  if (s.sleep) return kRcGated;  // (the caller counts the call and goes without the store)
+  if (!s.valid || s.used == 0) return kRcFresh;
+  if (s.pending != kRcKeep) return s.pending;  // the previous call ran out of pool, or filled a directory
+  if (std::memcmp(s.sig, sig, sizeof(s.sig)) != 0) return kRcSignature;
+  // The pool never moves while it holds snapshots. A call's new snapshots are taken to need what the
+  // previous call's took, and half of that after the store's first call, which built every key; a
+  // pool sized for calls less than half this one's size is given up as well. (A call that runs out
+  // all the same leaves keys uncached and asks the next one to start empty: rc_store_finish.)
+  const uint64_t cap = std::min(s.cap, cap_limit);
+  const uint64_t need = std::min(want_cap, s.calls <= 1 ? s.last_call / 2 : s.last_call);
+  if (want_cap > 2 * s.cap || cap < s.used || cap - s.used < need) return kRcPool;
+  for (const RcStoreDir& d : s.dir)
+    if (d.n_slots && 2 * d.count > d.n_slots) return kRcDirectory;
+  return kRcKeep;
+}
+
+int rc_store_prepare(RcStore& s, int decision, const uint32_t sig[kRcSigWords], uint64_t want_cap, hipStream_t st,
+                     std::string& err) {
+  if (!s.last) HIP_TRY(hipEventCreateWithFlags(&s.last, hipEventDisableTiming));
+  if (!s.dev) HIP_TRY(hipMalloc((void**)&s.dev, RcStore::kDevWords * sizeof(unsigned long long)));
+  if (decision == kRcKeep) {  // this call's carried counts start at zero
+    HIP_TRY(hipMemsetAsync(s.dev + 1, 0, 9 * sizeof(unsigned long long), st));
+    ++s.calls;
+    return FAC_OK;
+  }
+  s.valid = false;
+  if (!s.pool || s.cap < want_cap) {
+    if (s.pool) HIP_TRY(hipFree(s.pool));
+    s.pool = nullptr;
+    s.cap = 0;
+    HIP_TRY(hipMalloc((void**)&s.pool, want_cap * sizeof(uint4)));
+    s.cap = want_cap;
+  }
+  HIP_TRY(hipMemsetAsync(s.dev, 0, RcStore::kDevWords * sizeof(unsigned long long), st));
+  for (RcStoreDir& d : s.dir) {
+    d.count = 0;
+    if (d.slots) HIP_TRY(hipMemsetAsync(d.slots, 0, (size_t)d.n_slots * 2 * sizeof(uint4), st));
+  }
+  std::memcpy(s.sig, sig, sizeof(s.sig));
+  s.used = 0;
+  s.last_call = 0;
+  s.pending = kRcKeep;
+  std::memset(s.last_built, 0, sizeof(s.last_built));
+  std::memset(s.carried, 0, sizeof(s.carried));
+  s.calls = 1;
+  s.valid = true;
+  return FAC_OK;
+}
+
+int rc_store_dir(RcStore& s, uint32_t k, uint64_t n_ent, hipStream_t st, std::string& err) {
+  RcStoreDir& d = s.dir[k];
+  // the most keys it has held count too: a directory emptied because it was full comes back larger
+  n_ent = std::max(n_ent, d.peak);
+  if (d.count || rc_dir_fits(d, n_ent)) return FAC_OK;
+  // empty and too small (or none yet): four slots per key, so the keys of later calls fit until the
+  // load reaches one half (rc_store_decide then empties the store)
+  uint32_t n = 1u << 12;
+  while (n < 4 * n_ent && n < (1u << 27)) n <<= 1;
+  if (d.slots) HIP_TRY(hipFree(d.slots));
+  d.slots = nullptr;
+  d.n_slots = 0;
+  HIP_TRY(hipMalloc((void**)&d.slots, (size_t)n * 2 * sizeof(uint4)));
+  d.n_slots = n;
+  HIP_TRY(hipMemsetAsync(d.slots, 0, (size_t)n * 2 * sizeof(uint4), st));
+  return FAC_OK;
+}
+
+int rc_store_finish(RcStore& s, uint64_t cap_limit, bool carrying, uint64_t gate_min, std::string& err) {
+  unsigned long long w[RcStore::kDevWords];
+  HIP_TRY(hipMemcpy(w, s.dev, sizeof(w), hipMemcpyDeviceToHost));
+  s.last_call = w[0] - std::min<uint64_t>(w[0], s.used);
+  s.used = w[0];
+  // the bump allocator ran past the pool: the keys that did not fit are stored as uncached
+  if (s.used > cap_limit) s.pending = kRcPool;
+  for (int k = 0; k < 9; ++k) {
+    s.carried[k] = w[1 + k];
+    s.last_built[k] = w[10 + k] - std::min<uint64_t>(w[10 + k], s.dir[k].count);
+    s.dir[k].count = w[10 + k];
+    s.dir[k].peak = std::max(s.dir[k].peak, s.dir[k].count);
+  }
+  if (carrying) {
+    uint64_t c = 0, b = 0;
+    for (int k = 0; k < 9; ++k) c += s.carried[k], b += s.last_built[k];
+    s.backoff = rc_store_gate(c, b, s.backoff, gate_min);
+    s.sleep = s.backoff;
+    if (s.sleep) s.valid = false;  // what it holds did not pay: empty when the store is used again
+  }
+  return FAC_OK;
+}
+
+void rc_store_drop(RcStore& s) {
+  if (s.pool) (void)hipFree(s.pool);
+  if (s.dev) (void)hipFree(s.dev);
+  for (RcStoreDir& d : s.dir) {
+    if (d.slots) (void)hipFree(d.slots);
+    const uint64_t peak = d.peak;
+    d = RcStoreDir{};
+    d.peak = peak;
+  }
+  if (s.last) (void)hipEventDestroy(s.last);
+  s.pool = nullptr;
+  s.dev = nullptr;
+  s.last = nullptr;
+  s.cap = s.used = s.last_call = 0;
+  s.valid = false;
+  s.pending = kRcKeep;
+}
+
 void free_engine_device(Engine& e) {
   if (e.d_nodes == nullptr && e.stream == nullptr) return;
   (void)hipSetDevice(e.device);
+  {
+    std::lock_guard<std::mutex> lk(e.rc_store.mu);
+    rc_store_drop(e.rc_store);
+  }
   void* ptrs[] = {e.d_nodes, e.d_out_range, e.d_pidx, e.d_edges, e.d_out_pat, e.d_sb_edge, e.d_gt, e.d_aux, e.d_pat_bytes, e.d_pats, e.d_sim_ascii, e.d_sim_keys,
                   e.d_sim_vals, e.d_ascii_id, e.d_edge_gid, e.d_ascii_gid, e.d_map_range,
                   e.d_map_ent, e.d_map_hay};

@@ -303,6 +303,10 @@ struct SearchParams {
   // diagnostics (FAC_RC_FULL_SWEEP=1): the build epilogue sweeps the dedup table for final keys too
   // and re-reads every slot in both writing passes (the epilogue before the single sweep; same pool)
   int32_t rc_full_sweep;
+  // carry-over (RcStore): rc_carry_kernel ran ahead of this level's build, and the entries
+  // whose rc_off is not RC_TOBUILD hold a snapshot of an earlier call (rc_parent_kernel and the build
+  // skip them). Last, like the fields above.
+  int32_t rc_carry;
 };
 
 constexpr unsigned ERR_QUEUE = 1u, ERR_VISITED = 2u, ERR_EMIT = 4u, ERR_HALO = 8u, ERR_OUT = 16u, ERR_SPILL = 32u;
@@ -343,6 +347,57 @@ struct GraphemeTable {
   uint32_t mask = 0;  // slots - 1
   uint32_t n_keys = 0, n_pool = 0;
 };
+
+// Engine-resident snapshot store: the snapshot pool and one exact-key directory
+// per key length, kept from call to call, so that a level's build runs only for the keys no earlier
+// call built. One call at a time uses it (mu, try-lock; a call that finds it taken runs with a pool
+// from call scratch and no carry-over). Host state only here: device_state.cpp owns the allocations.
+constexpr int kRcSigWords = 16;
+constexpr uint32_t RC_TOBUILD = 0xFFFFFFFDu;  // rc_off of an entry rc_carry_kernel did not find
+enum RcReset { kRcKeep = 0, kRcFresh, kRcSignature, kRcPool, kRcDirectory, kRcBusy, kRcOff, kRcGated };
+const char* rc_reset_name(int r);
+struct RcStoreDir {
+  uint4* slots = nullptr;  // rc_publish_kernel's 32-byte slots
+  uint32_t n_slots = 0;    // a power of two (0: none yet)
+  uint64_t count = 0;      // keys inserted (host copy, read back at the end of each call)
+  uint64_t peak = 0;       // the most it has held (sizes it when it is allocated again)
+};
+struct RcStore {
+  std::mutex mu;
+  bool valid = false;            // sig, the pool's contents and the directories belong together
+  uint32_t sig[kRcSigWords] = {};
+  uint4* pool = nullptr;
+  uint64_t cap = 0;              // pool words allocated
+  uint64_t used = 0;             // pool words used (host copy of dev[0])
+  uint64_t last_call = 0;        // pool words the previous call appended
+  int pending = kRcKeep;         // a reset the previous call asks of the next one (the pool ran out)
+  // the gate for unlike text: a carrying call that found under a tenth of its entries sends the next
+  // `sleep` calls past the store (1, 2, 4, .. 64 calls: `backoff`), and the store starts empty after them
+  uint32_t sleep = 0, backoff = 0;
+  RcStoreDir dir[9];             // by key length (2..8)
+  uint64_t last_built[9] = {};   // entries the previous call built, by key length (sizes the waves' pool chunks)
+  uint64_t carried[9] = {};      // entries the last call carried over, by key length
+  // device words: [0] pool words used, [1 + k] entries carried at key length k (this call),
+  // [10 + k] keys in directory k
+  unsigned long long* dev = nullptr;
+  static constexpr int kDevWords = 20;
+  hipEvent_t last = nullptr;     // the previous user's last work on the store
+  uint64_t calls = 0;
+};
+// what a call does with the store it has locked (no device work): kRcKeep carries over, every other
+// value starts from an empty store (kRcFresh: it was empty already)
+int rc_store_decide(const RcStore& s, const uint32_t sig[kRcSigWords], uint64_t want_cap, uint64_t cap_limit);
+// directory k can take n more keys at a load of at most one half
+bool rc_dir_fits(const RcStoreDir& d, uint64_t n);
+int rc_store_prepare(RcStore& s, int decision, const uint32_t sig[kRcSigWords], uint64_t want_cap, hipStream_t st,
+                     std::string& err);  // pool of want_cap words, empty directories
+int rc_store_dir(RcStore& s, uint32_t k, uint64_t n_ent, hipStream_t st, std::string& err);  // directory k for n_ent more keys
+// after the stream's sync: counts read back; carrying: the call carried over (the gate judges it);
+// gate_min: calls with fewer entries are not judged
+int rc_store_finish(RcStore& s, uint64_t cap_limit, bool carrying, uint64_t gate_min, std::string& err);
+// the gate alone: the back-off after a carrying call with these totals (0: the store stays in use)
+uint32_t rc_store_gate(uint64_t carried, uint64_t built, uint32_t backoff, uint64_t gate_min);
+void rc_store_drop(RcStore& s);  // frees everything (the caller holds mu)
 
 struct Engine {
   int device = 0;
@@ -436,6 +491,7 @@ struct Engine {
   static constexpr int kScratch = 64;
   mutable void* scratch_p[kScratch] = {};
   mutable size_t scratch_n[kScratch] = {};
+  mutable RcStore rc_store;  // prefix-cache snapshots kept across calls
 };
 
 struct Haystack {

@@ -2641,6 +2641,7 @@ __device__ __forceinline__ RcHit rc_lookup_shallow(const SearchParams& P, const 
 __global__ __launch_bounds__(256) void rc_parent_kernel(SearchParams P, uint32_t qcap) {
   for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < P.total_windows;
        v += (uint64_t)gridDim.x * blockDim.x) {
+    if (P.rc_carry && P.rc_off[v] != RC_TOBUILD) continue;  // carried over: the build skips it too
     const uint64_t wid = P.win_list[v];
     const uint32_t kl = find_seg(P, wid);
     const SegDesc S = P.segs[kl];
@@ -2686,6 +2687,115 @@ __global__ __launch_bounds__(256) void rc_publish_kernel(SearchParams P, const u
       }
     }
   }
+}
+
+// Carry-over (the engine's snapshot store). A directory holds, for one key length
+// and across calls, every key a build has settled: rc_publish_kernel's slot with the snapshot's pool
+// offset, or offset EMPTY for a key the build left uncached (its parent was final, or it did not fit).
+constexpr uint32_t RC_CARRIED = 0xFFFFFFFCu;  // rc_off of an entry carried over as uncached
+// the exact key of an entry's representative; false: not encodable (rc_publish_kernel's rules)
+__device__ __forceinline__ bool rc_entry_key(const SearchParams& P, uint64_t wid, uint32_t k, uint4& key) {
+  const uint32_t kl = find_seg(P, wid);
+  const SegDesc S = P.segs[kl];
+  uint32_t c[8];
+  if (!rc_chars(P, S, S.w_begin + (wid - P.seg_prefix[kl]), k, c)) return false;
+  bool enc = true;
+#pragma unroll
+  for (uint32_t i = 0; i < 8; ++i) enc = enc && (i >= k || c[i] == RC_PAD || c[i] < 0xFFFFu);
+  key = rc_exact_key(c, k);
+  return enc;
+}
+__device__ __forceinline__ bool rc_same_key(uint4 a, uint4 b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
+// one atomic per wave for a per-thread count
+__device__ __forceinline__ void rc_wave_count(unsigned long long* dst, uint32_t n) {
+  unsigned long long t = n;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t += shfl_u64(t, (lane_id() + o) & 63);
+  if (lane_id() == 0 && t) atomicAdd(dst, t);
+}
+// One thread per numbered entry of a level, ahead of rc_parent_kernel and the build: a key the
+// directory holds takes its snapshot (off / count as the build would have written them), every other
+// entry is marked RC_TOBUILD. keep_final: this level keeps the snapshots of keys whose parent is final,
+// so a key stored as uncached is built again. carried: entries found; kept: of those, with a snapshot
+// (counters[11], which sizes the level's lookup table).
+__global__ __launch_bounds__(256) void rc_carry_kernel(SearchParams P, const uint64_t* reps, uint32_t n_ent, uint32_t k,
+                                                       const uint4* dir, uint32_t mask, uint32_t* off, uint32_t* count,
+                                                       int keep_final, unsigned long long* carried,
+                                                       unsigned long long* kept) {
+  uint32_t n_hit = 0, n_kept = 0;
+  for (uint32_t ent = blockIdx.x * blockDim.x + threadIdx.x; ent < n_ent; ent += gridDim.x * blockDim.x) {
+    uint32_t o = RC_TOBUILD, cnt = EMPTY;
+    uint4 key;
+    if (rc_entry_key(P, reps[ent], k, key)) {
+      uint32_t slot = rc_key_hash(key) & mask;
+      for (uint32_t p = 0; p < RC_PROBES; ++p, slot = (slot + 1) & mask) {
+        const uint4* e = dir + 2 * (size_t)slot;
+        const uint4 val = e[1];
+        if (!(val.w & RC_OCC)) break;
+        if (!rc_same_key(e[0], key)) continue;
+        if (val.x != EMPTY) {
+          o = val.x;
+          cnt = val.z & 0xFFFFu;
+          ++n_kept;
+        } else if (!keep_final) {
+          o = RC_CARRIED;
+        }
+        break;
+      }
+    }
+    n_hit += o != RC_TOBUILD ? 1u : 0u;
+    off[ent] = o;
+    count[ent] = cnt;
+  }
+  rc_wave_count(carried, n_hit);
+  rc_wave_count(kept, n_kept);
+}
+// After a level's build: the entries it built (not carried: offsets from pool word used0 on, or
+// uncached) go into the directory, snapshot or not. A key already there (stored as uncached, built
+// again under keep_final) takes the new value. Launches are ordered, and a launch holds each key once.
+__global__ __launch_bounds__(256) void rc_store_insert_kernel(SearchParams P, const uint64_t* reps, const uint4* pool,
+                                                              const uint32_t* off, const uint32_t* count, uint32_t n_ent,
+                                                              uint32_t k, uint4* dir, uint32_t mask, uint32_t used0,
+                                                              unsigned long long* n_keys) {
+  uint32_t n_new = 0;
+  for (uint32_t ent = blockIdx.x * blockDim.x + threadIdx.x; ent < n_ent; ent += gridDim.x * blockDim.x) {
+    const uint32_t o = off[ent];
+    const bool cached = count[ent] != EMPTY;
+    if (o == RC_CARRIED || o == RC_TOBUILD || (cached && o < used0)) continue;
+    if (cached && (unsigned long long)o + RC_HDR > P.rc_pool_cap) continue;  // (an entry a failed build left unwritten)
+    uint4 key;
+    if (!rc_entry_key(P, reps[ent], k, key)) continue;
+    uint4 val = make_uint4(EMPTY, 0u, 0u, RC_OCC);
+    if (cached) {
+      const uint4 h0 = pool[o], h1 = pool[o + 1];
+      val = make_uint4(o, h0.x, (h0.y - h0.x) | (h1.x << 16), RC_OCC | (h0.z << 22) | min(h0.w, RC_POPS_MASK));
+    }
+    uint32_t slot = rc_key_hash(key) & mask;
+    for (uint32_t p = 0; p < RC_PROBES; ++p, slot = (slot + 1) & mask) {
+      uint4* e = dir + 2 * (size_t)slot;
+      const uint32_t w = atomicCAS(&e[1].w, 0u, val.w);
+      if (w == 0u) {
+        e[0] = key;
+        e[1].x = val.x;
+        e[1].y = val.y;
+        e[1].z = val.z;
+        ++n_new;
+        break;
+      }
+      // an earlier call's uncached mark of this key (a slot claimed in this launch may still lack its
+      // key, but it is another key's: the comparison fails either way)
+      if (w == RC_OCC && e[1].x == EMPTY && rc_same_key(e[0], key)) {
+        if (cached) {
+          e[1].x = val.x;
+          e[1].y = val.y;
+          e[1].z = val.z;
+          e[1].w = val.w;
+        }
+        break;
+      }
+    }
+  }
+  rc_wave_count(n_keys, n_new);
 }
 
 // Dense start-level bitmaps (P.rc_dense). Most windows' start-level snapshot is final without
@@ -3954,6 +4064,8 @@ __device__ __forceinline__ void bfs_window_body(const SearchParams& P) {
           active = !window_skipped(P, S, start, err);
         }
       }
+      if constexpr (LK)  // cache build: an entry rc_carry_kernel found in the engine's store is built already
+        if (cf_build<CF>(P) && P.rc_carry && active && P.rc_off[v] != RC_TOBUILD) active = false;
       if constexpr (LK)
         if (cf_rc_mode<CF>(P) != 0 && P.rc_ntab && active && P.rc_bhits) {  // rc_parent_kernel's lookup
           const uint4 h = P.rc_bhits[v];
@@ -4788,6 +4900,24 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       if (e) (void)hipEventDestroy(e);
     }
   } ev_lane_guard{ev_lane};
+  // the engine's snapshot store while this call holds it. On return the event the
+  // next user waits for is recorded and the lock released; a call that fails before the store's counts
+  // are read back leaves it invalid, and the next call starts it empty.
+  struct StoreLease {
+    RcStore* s = nullptr;
+    std::unique_lock<std::mutex> lk;
+    hipStream_t st = nullptr;
+    bool finished = false;
+    ~StoreLease() {
+      if (!s) return;
+      if (!finished) {
+        (void)hipDeviceSynchronize();
+        s->valid = false;
+      }
+      if (s->last) (void)hipEventRecord(s->last, st);
+    }
+  } store;
+  int store_reset = kRcOff;  // FAC_RC_DEBUG: why this call did not carry over (kRcKeep: it did)
 
   // Prefix cache. Level 1: every window's key of K0 chars (4, else 3, else 2,
   // whichever first gives every snapshot at least 8 windows on average); rc_count_kernel inserts
@@ -5035,6 +5165,29 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
         Q.dyn_chunks = 0;
         grid = (uint32_t)std::min<uint64_t>((n_ent + Q.chunk - 1) / Q.chunk, 0x7FFFFFFFull);
       }
+      // carry-over: the entries whose key the engine's store holds take their snapshot from it
+      // (rc_carry_kernel); the parent lookups and the build then skip them
+      Q.rc_carry = 0;
+      bool store_insert = false;
+      if (store.s) {
+        RcStore& S = *store.s;
+        if (int drc = rc_store_dir(S, T.k, n_ent, bs, err)) return drc;
+        RcStoreDir& D = S.dir[T.k];
+        // (an insert gives up after RC_PROBES slots, so a directory past its load only loses keys; the
+        // next call sees the count and starts the store empty, rc_store_decide)
+        store_insert = D.n_slots != 0;
+        if (D.count) {
+          hipLaunchKernelGGL(rc_carry_kernel, dim3(std::max<uint32_t>(1, std::min<uint32_t>((n_ent + 255) / 256, cus * 8))),
+                             dim3(256), 0, bs, Q, reps, n_ent, T.k, D.slots, D.n_slots - 1, Q.rc_off, Q.rc_count,
+                             (int)Q.rc_keep_final, S.dev + 1 + T.k, Q.counters + 11);
+          HIP_TRY(hipGetLastError());
+          Q.rc_carry = 1;
+          // the waves' pool chunks follow the entries the previous call built at this level: what a wave
+          // leaves of its last chunk is lost to the pool for good
+          const uint64_t est = std::min<uint64_t>(n_ent, S.last_built[T.k]);
+          Q.rc_pool_chunk = (uint32_t)std::max<uint64_t>(256, std::min<uint64_t>(P.rc_pool_chunk, est * 40 / (4ull * std::min<uint32_t>(n_ent, max_grid))));
+        }
+      }
       Q.rc_bhits = nullptr;
       Q.rc_bpops = nullptr;
       if (Q.rc_ntab > 0) {  // the representatives' parent snapshots (rc_parent_kernel)
@@ -5058,6 +5211,14 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       if (le != hipSuccess) {
         err = std::string("kernel launch: ") + hipGetErrorString(le);
         return FAC_E_HIP;
+      }
+      if (store_insert) {  // the keys this build settled, for later calls
+        RcStore& S = *store.s;
+        hipLaunchKernelGGL(rc_store_insert_kernel, dim3(std::max<uint32_t>(1, std::min<uint32_t>((n_ent + 255) / 256, cus * 8))),
+                           dim3(256), 0, bs, Q, reps, static_cast<const uint4*>(P.rc_pool), T.off, T.count, n_ent, T.k,
+                           S.dir[T.k].slots, S.dir[T.k].n_slots - 1, (uint32_t)std::min<uint64_t>(S.used, 0xFFFFFFFFull),
+                           S.dev + 10 + T.k);
+        HIP_TRY(hipGetLastError());
       }
       return FAC_OK;
     };
@@ -5088,9 +5249,49 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       P.rc_pool_chunk = (uint32_t)std::max<uint64_t>(worst, std::min<uint64_t>(RC_POOL_CHUNK, n_all * 40 / (4 * grids)));
       const uint64_t pool_words = std::max<uint64_t>(1024, std::min<uint64_t>(n_all * worst, budget / sizeof(uint4))) +
                                   grids * P.rc_pool_chunk;
-      HIP_TRY(d_rcs.alloc(pool_words * sizeof(uint4), stream));
-      P.rc_pool = static_cast<uint4*>(d_rcs.p);
-      P.rc_pool_cap = pool_words;
+      // The pool: the engine's store, with the snapshots of earlier calls, unless FAC_RC_NO_CARRY=1 (A/B,
+      // tests) or another call holds it; then call scratch, every key built, as before the store.
+      // (not for the auto-beam counting pass: its other dedup mode would empty the store before each main pass)
+      if (!diag_env("FAC_RC_NO_CARRY") && !counts) {
+        RcStore& S = e.rc_store;
+        store.lk = std::unique_lock<std::mutex>(S.mu, std::try_to_lock);
+        store_reset = kRcBusy;
+        if (store.lk.owns_lock()) {
+          uint32_t sig[kRcSigWords] = {};
+          std::memcpy(&sig[0], &P.thr, 4);
+          std::memcpy(&sig[1], &P.max_penalties, 4);
+          sig[2] = P.beam;
+          sig[3] = (uint32_t)P.exact_dedup | (uint32_t)P.beam_canonical << 1 | (uint32_t)P.gt_fast << 2 |
+                   (uint32_t)P.dup_cut << 3 | (uint32_t)P.rc_full_sweep << 4 | (uint32_t)P.case_insensitive << 5 |
+                   (uint32_t)P.window_skip << 6;
+          sig[4] = P.sel_limit;
+          sig[5] = P.rc_vmax;
+          sig[6] = P.rc_emax;
+          sig[7] = qbuild;
+          sig[8] = qmain;
+          sig[9] = vmain;
+          // FAC_RC_POOL_WORDS (tests): fewer pool words than allocated, so a small case can fill the pool
+          const uint64_t limit = env_u("FAC_RC_POOL_WORDS", UINT64_MAX);
+          store_reset = rc_store_decide(S, sig, pool_words, limit);
+          if (store_reset == kRcGated) {  // unlike text: this call goes without the store
+            --S.sleep;
+            store.lk.unlock();
+          } else {
+            if (S.last) HIP_TRY(hipStreamWaitEvent(stream, S.last, 0));  // the previous user's last work
+            store.s = &S;
+            store.st = stream;
+            if (int prc = rc_store_prepare(S, store_reset, sig, pool_words, stream, err)) return prc;
+            P.rc_pool = S.pool;
+            P.rc_pool_cap = std::min(S.cap, limit);
+            P.rc_pool_used = S.dev;
+          }
+        }
+      }
+      if (!store.s) {
+        HIP_TRY(d_rcs.alloc(pool_words * sizeof(uint4), stream));
+        P.rc_pool = static_cast<uint4*>(d_rcs.p);
+        P.rc_pool_cap = pool_words;
+      }
       if (!diag_env("FAC_RC_ONE_STREAM")) {
         // the lowest priority: the sampled-level counts beside it come first. A streaming worker's
         // scratch set has its own (only that worker's thread uses it), so two windows in flight do
@@ -5261,6 +5462,12 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     HIP_TRY(hipEventRecord(ev.b, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipEventElapsedTime(&cache_ms, ev.a, ev.b));
+    if (store.s) {  // pool words, carried entries and directory keys, read back for the next call's decisions
+      // FAC_RC_GATE_MIN (tests): the fewest entries of a call the gate for unlike text judges
+      if (int frc = rc_store_finish(*store.s, P.rc_pool_cap, store_reset == kRcKeep, env_u("FAC_RC_GATE_MIN", 1ull << 16), err))
+        return frc;
+      store.finished = true;
+    }
     if (P.rc_dense) {
       // F-done windows among 16384 sampled: below FAC_RC_DENSE_OFF per mille the bitmaps are dropped
       // (their test costs the lookup more than it saves), from FAC_RC_DENSE_LIST per mille the lookups
@@ -5272,7 +5479,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     }
     if (P.rc_mode == 1 && diag_env("FAC_RC_DEBUG")) {  // diagnostics: keys, pool use, cached entries
       unsigned long long rcn[2] = {0, 0};
-      HIP_TRY(hipMemcpy(rcn, d_rcn.p, sizeof(rcn), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&rcn[1], P.rc_pool_used, sizeof(rcn[1]), hipMemcpyDeviceToHost));
       // fin: of the cached keys, the final ones (empty queue; the build epilogue skips their table sweep)
       auto cached_of = [&](const RcTable& T, uint32_t ne, uint64_t& qsum, uint64_t& fin) -> uint64_t {
         std::vector<uint32_t> cntv(ne);
@@ -5304,6 +5511,28 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       }
       uint64_t q0 = 0, f0 = 0;
       const uint64_t c0 = n_ent0 ? cached_of(L0, n_ent0, q0, f0) : 0;
+      // carry-over: per level the entries taken from the engine's store and the ones left to the build;
+      // the store's pool words, its directories' keys over their slots, and why the call started it empty
+      std::string cs = " | carry";
+      {
+        auto level = [&](uint32_t k, uint32_t ne) {
+          const uint64_t got = store.s ? std::min<uint64_t>(ne, store.s->carried[k]) : 0;
+          char b[96];
+          std::snprintf(b, sizeof(b), " k=%u carried=%llu built=%llu", k, (unsigned long long)got, (unsigned long long)(ne - got));
+          cs += b;
+        };
+        if (n_ent0) level(L0.k, n_ent0);
+        level(L1.k, n_ent1);
+        for (size_t x = 0; x < Lx.size(); ++x) level(Lx[x].k, n_entx[x]);
+        uint64_t keys = 0, dslots = 0;
+        for (int k = 0; store.s && k < 9; ++k) keys += store.s->dir[k].count, dslots += store.s->dir[k].n_slots;
+        char b[160];
+        std::snprintf(b, sizeof(b), " | store pool_words=%llu dir_keys=%llu dir_slots=%llu reset=%s",
+                      (unsigned long long)(store.s ? store.s->used : 0), (unsigned long long)keys, (unsigned long long)dslots,
+                      rc_reset_name(store_reset));
+        cs += b;
+      }
+      lv += cs;
       std::fprintf(stderr, "FAC_RC windows=%llu L0 k=%u entries=%u cached=%llu final=%llu open=%llu mean_queue=%.1f | L1 k=%u "
                    "keys=%llu cached=%llu final=%llu open=%llu mean_queue=%.1f%s | pool %.1f MB\n",
                    (unsigned long long)windows, L0.k, n_ent0, (unsigned long long)c0, (unsigned long long)f0,

@@ -145,6 +145,13 @@ SIGNATURES = {
     "fac_last_error": (ctypes.c_char_p, []),
     "fac_build": (ctypes.c_int, [_P(fac_pattern), ctypes.c_uint64, _P(fac_config), _P(_engine_p)]),
     "fac_engine_free": (None, [_engine_p]),
+    "fac_engine_drop_prefix_cache": (None, [_engine_p]),
+    "fac_diag_rc_store_decide": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                ctypes.c_uint64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int32, ctypes.c_uint32]),
+    "fac_diag_rc_reset_name": (ctypes.c_char_p, [ctypes.c_int32]),
+    "fac_diag_rc_store_gate": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64]),
     "fac_trim_scratch": (None, []),
     "fac_search_raw": (ctypes.c_int, [_engine_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_float,
                                       _P(_P(fac_match)), _u64p, _u64p]),

@@ -169,6 +169,11 @@ class FuzzyAhoCorasick:
             _native.lib.fac_engine_free(h)
             self._h = None
 
+    def drop_prefix_cache(self) -> None:
+        """fac_engine_drop_prefix_cache: frees the prefix-cache snapshots the engine keeps from search
+        to search (up to FAC_RC_POOL_MB of device memory); the next search builds every key again."""
+        _native.lib.fac_engine_drop_prefix_cache(self._h)
+
     # -- introspection
     def patterns(self) -> List[Pattern]:
         return self.patterns_

@@ -169,6 +169,10 @@ const char* fac_last_error(void);
 int fac_build(const fac_pattern* patterns, uint64_t n_patterns, const fac_config* cfg,
               fac_engine** out);
 void fac_engine_free(fac_engine* engine);
+/* Frees the prefix-cache snapshots the engine keeps from search to search (the snapshot pool, up to
+ * FAC_RC_POOL_MB, and its key directories); the next search builds every key again. Waits for a search
+ * that is using them. fac_engine_free frees them too. */
+void fac_engine_drop_prefix_cache(fac_engine* engine);
 /* Frees the device blocks the library keeps for reuse between calls (per-call scratch of the
  * pre-filter, ranking and stream windows; at most 2 GiB are kept, fac_engine_free trims too). */
 void fac_trim_scratch(void);
@@ -788,6 +792,24 @@ void fac_edge_order(const uint32_t* cps, const uint64_t* off, uint64_t n, uint32
  * perm[a*bw .. a*bw + bw). sel_limit < 0: core's 16 partition rounds. Uses device 0. */
 int fac_diag_beam_select(const float* keys, const uint64_t* offs, uint64_t count, uint32_t bw, int32_t lds,
                          int32_t sel_limit, uint32_t* perm);
+
+/* Diagnostics (tests): what a search does with its engine's snapshot store, from the store's host state
+ * alone (no device): 0 carries over, else the reason it starts the store empty (1 fresh, 2 signature,
+ * 3 pool, 4 directory) or does without it (5 busy: another call holds it; busy != 0 holds the store's
+ * lock while a second thread takes the call's steps; 7 gated: sleep != 0). calls: the calls the store has served since it was
+ * last empty; used, cap, last_call (appended by the previous call), want_cap (what this call would
+ * allocate), cap_limit: pool words; pending: a reason the previous call left. Signatures are 16 words,
+ * the directory arrays 9 entries (by key length). fac_diag_rc_reset_name: the reason as the
+ * FAC_RC_DEBUG line prints it. */
+int fac_diag_rc_store_decide(int32_t valid, uint64_t calls, uint64_t used, uint64_t cap, uint64_t last_call,
+                             int32_t pending, const uint32_t* have_sig, const uint32_t* want_sig, uint64_t want_cap,
+                             uint64_t cap_limit, const uint64_t* dir_slots, const uint64_t* dir_keys, int32_t busy,
+                             uint32_t sleep);
+const char* fac_diag_rc_reset_name(int32_t reset);
+/* The store's gate for unlike text: the calls that go without the store (7 gated; `sleep` above) after a
+ * carrying call that found `carried` of its carried + built entries: 0 from a tenth on or below gate_min
+ * entries, else twice `backoff` (1 at first, at most 64). */
+uint32_t fac_diag_rc_store_gate(uint64_t carried, uint64_t built, uint32_t backoff, uint64_t gate_min);
 
 /* Diagnostics (tests): the expanded text of a stream task alone. Window w is bytes
  * [windows[2w], windows[2w] + windows[2w + 1]) of the len bytes at utf8 (ranges may overlap); the
