@@ -1305,6 +1305,23 @@ int fac_batch_allow_unicode_mappings(fac_batch* batch, int32_t on) {
   return FAC_OK;
 }
 
+int fac_batch_require_boundaries(fac_batch* batch, int32_t sides) {
+  if (!batch) return fail(FAC_E_INVALID, "NULL argument");
+  if (sides < 0 || sides > FAC_BOUNDARY_WHOLE) return fail(FAC_E_INVALID, "sides must be 0..3");
+  batch->b.boundaries = sides;
+  return FAC_OK;
+}
+
+int32_t fac_boundary_class(uint32_t cp) { return (int32_t)fac::boundary_class(cp); }
+
+int32_t fac_boundary_ok(const uint8_t* utf8, uint64_t len, uint64_t start, uint64_t end, int32_t sides) {
+  if ((len && !utf8) || sides < 0 || sides > FAC_BOUNDARY_WHOLE) return -(int32_t)fail(FAC_E_INVALID, "bad argument");
+  if (start > end || end > len) return -(int32_t)fail(FAC_E_INVALID, "span outside the text");
+  if ((start < len && (utf8[start] & 0xC0) == 0x80) || (end < len && (utf8[end] & 0xC0) == 0x80))
+    return -(int32_t)fail(FAC_E_INVALID, "span not on a character boundary");
+  return fac::boundary_ok(utf8, len, start, end, sides) ? 1 : 0;
+}
+
 int64_t fac_batch_grapheme_ids(const fac_engine* engine, const fac_batch* batch, void* stream, uint32_t* out, uint64_t cap) {
   if (!engine || !batch) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
   return grapheme_ids_out(engine->e, batch->b.h, stream, out, cap);
@@ -1399,8 +1416,19 @@ static int batch_kept(const fac::Engine& e, const fac::Batch& b, float threshold
       continue;
     }
     k.d_doc = d_doc_user ? d_doc_user : static_cast<uint64_t*>(k.doff.p);
-    return fac::apply_batch_device(e, sink.dev, sink.dev + cap, sink.n, b.d_offsets, nd, order, overlap, unique_ids, st,
-                                   k.d_doc, &k.res, &k.n_res, err);
+    fac_match *recs = sink.dev, *other = sink.dev + cap;
+    uint64_t n = sink.n;
+    if (b.boundaries && n) {
+      // whole-token matches (fac.h fac_batch_require_boundaries): the complete raw set is filtered
+      // into the buffer's other half, before any overlap walk sees it; the index scratch lends the
+      // kernel its counter (the apply writes the index afterwards)
+      if (int rc = fac::boundary_filter_device(b, b.boundaries, recs, n, other, static_cast<unsigned long long*>(k.doff.p),
+                                               st, &n, err))
+        return rc;
+      std::swap(recs, other);
+    }
+    return fac::apply_batch_device(e, recs, other, n, b.d_offsets, nd, order, overlap, unique_ids, st, k.d_doc, &k.res,
+                                   &k.n_res, err);
   }
 }
 

@@ -37,6 +37,13 @@ void segment_graphemes(const uint8_t* s, uint64_t n, std::vector<uint64_t>& star
 int lower_full(uint32_t cp, uint32_t out[3]);
 void fold_grapheme(const uint8_t* s, uint64_t b, uint64_t e, bool ci, std::u32string& out);
 uint32_t fold_first_char(const uint8_t* s, uint64_t b, uint64_t e, bool ci);
+// The whole-token rule (fac.h fac_batch_require_boundaries). boundary_class: bit 0 alphanumeric
+// (Rust's char::is_alphanumeric), bit 1 transparent (General_Category M* and not alphanumeric); 0 for
+// surrogates and values above U+10FFFF. boundary_ok: whether the sides `sides` of [start, end) are
+// boundaries of the valid UTF-8 text s[0, n); start <= end <= n, both on character boundaries.
+constexpr uint32_t kBoundaryMaxSkip = 32;  // transparent code points the start side walks over
+uint32_t boundary_class(uint32_t cp);
+bool boundary_ok(const uint8_t* s, uint64_t n, uint64_t start, uint64_t end, int sides);
 
 // ---------------------------------------------------------------- device layout
 constexpr uint32_t EDGE_SINGLE_BYTE = 1u << 31;
@@ -584,6 +591,10 @@ struct Batch {
   // even if it holds non-ASCII documents (their grapheme ids: batch_grapheme_ids_kernel). Kept
   // across a restage like unicode_pf, and independent of it.
   bool unicode_map = false;
+  // fac_batch_require_boundaries: the sides (FAC_BOUNDARY_*) of every raw record that must be
+  // boundaries of its document for the record to reach the apply; 0 = off. Kept across a restage
+  // like the opt-ins above. The window batches of stream.cpp never set it.
+  int boundaries = 0;
   // stream_windows_docs: the documents are long (256 KiB windows), so stage_batch_device segments
   // the non-ASCII ones by chunks of the text (batch_seg_chunk_kernel) instead of one thread each.
   // The staged batch is the same either way.
@@ -610,6 +621,12 @@ void free_batch(Batch& b);
 int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t n, const uint64_t* d_offsets,
                        uint64_t n_docs, int order, int overlap, const uint64_t* unique_ids, hipStream_t s,
                        uint64_t* d_doc_off, fac_match** res, uint64_t* n_res, std::string& err);
+// boundary_kernels.hip: the whole-token filter of a batch's n raw records at d_in (tagged, as the
+// search left them): the records whose sides `sides` are boundaries of their own document go to
+// d_out (room for n, not overlapping d_in) in no particular order, *n_kept of them. d_count: 8 bytes
+// of device scratch. Reads b.h.d_utf8 inside the record's document only; synchronises once.
+int boundary_filter_device(const Batch& b, int sides, const fac_match* d_in, uint64_t n, fac_match* d_out,
+                           unsigned long long* d_count, hipStream_t s, uint64_t* n_kept, std::string& err);
 
 // replace_kernels.hip: the splice of a batch (fac.h fac_replace_batch; matches.rs:165-188 per
 // document). A replacement table holds per pattern {offset into d_bytes, byte length}, the length

@@ -335,4 +335,38 @@ uint32_t fold_first_char(const uint8_t* s, uint64_t b, uint64_t e, bool ci) {
   return lo[0];
 }
 
+// ---- the whole-token rule (fac.h fac_batch_require_boundaries; boundary_kernels.hip is the same
+// rule on the device, from the same generated ranges)
+namespace {
+#define FAC_UNICODE_QUAL
+#include "unicode_boundary.inc"
+#undef FAC_UNICODE_QUAL
+}  // namespace
+
+uint32_t boundary_class(uint32_t cp) {
+  if (cp < 0x80) return ((cp | 0x20u) - 'a' < 26u || cp - '0' < 10u) ? 1u : 0u;
+  if (cp > 0x10FFFF) return 0;
+  const GcbRange* r = find_range(kBoundaryRanges, sizeof(kBoundaryRanges) / sizeof(kBoundaryRanges[0]), cp);
+  return r ? r->prop : 0u;
+}
+
+bool boundary_ok(const uint8_t* s, uint64_t n, uint64_t start, uint64_t end, int sides) {
+  if ((sides & FAC_BOUNDARY_END) && end < n) {
+    uint64_t i = end;
+    if (boundary_class(utf8_decode(s, n, i)) & 1u) return false;
+  }
+  if (sides & FAC_BOUNDARY_START) {
+    uint64_t p = start;
+    for (uint32_t skipped = 0; skipped < kBoundaryMaxSkip && p > 0; ++skipped) {
+      uint64_t q = p - 1;  // the first byte of the code point that ends at p
+      while (q > 0 && p - q < 4 && (s[q] & 0xC0) == 0x80) --q;
+      uint64_t i = q;
+      const uint32_t c = boundary_class(utf8_decode(s, p, i));
+      if (!(c & 2u)) return !(c & 1u);
+      p = q;
+    }
+  }
+  return true;
+}
+
 }  // namespace fac

@@ -118,6 +118,9 @@ FAC_UNMATCHED = 0xFFFFFFFF  # pattern_index of an unmatched segment (fac_segment
 FAC_RENDER_STRIP_PREFIX = 0
 FAC_RENDER_STRIP_SUFFIX = 1
 FAC_RENDER_SEGMENT_TEXT = 2
+FAC_BOUNDARY_START = 1  # sides of fac_batch_require_boundaries / fac_boundary_ok
+FAC_BOUNDARY_END = 2
+FAC_BOUNDARY_WHOLE = 3
 
 assert ctypes.sizeof(fac_match) == 32
 
@@ -243,6 +246,10 @@ SIGNATURES = {
     "fac_batch_docs": (ctypes.c_uint64, [ctypes.c_void_p]),
     "fac_batch_allow_unicode_prefilter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "fac_batch_allow_unicode_mappings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "fac_batch_require_boundaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "fac_boundary_class": (ctypes.c_int32, [ctypes.c_uint32]),
+    "fac_boundary_ok": (ctypes.c_int32, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.c_int32]),
     "fac_batch_grapheme_ids": (ctypes.c_int64, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_uint64]),
     "fac_haystack_grapheme_ids": (ctypes.c_int64, [_engine_p, _hay_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -12,7 +12,7 @@ from . import _native
 
 _TIMING = bool(os.environ.get("FAC_TIMING"))  # diagnostics: host-side phase times
 from .matches import FuzzyMatch, FuzzyMatches, Segment, UnmatchedSegment
-from .structs import (DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge, Order, Overlap,
+from .structs import (Boundary, DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge, Order, Overlap,
                       Pattern, SearchError, SearchOptions, Similarity, UnsupportedConfiguration, f32)
 
 
@@ -348,9 +348,25 @@ class FuzzyAhoCorasick:
         return self._to_matches(matches.haystack, matches.haystack.encode("utf-8"), rows)
 
     # -- query.rs
-    def search(self, haystack: str, opts: SearchOptions = None) -> FuzzyMatches:
+    def search(self, haystack: str, opts: SearchOptions = None, boundaries: Boundary = Boundary.NONE) -> FuzzyMatches:
+        """`boundaries` (non-zero): only matches whose named sides are word boundaries take part in
+        ranking and overlap resolution (DESIGN.md 6a "Whole-token matches"); the haystack then runs
+        as a one-document batch, where that filter is on the device."""
         opts = opts or SearchOptions()
+        if int(boundaries):
+            return self.search_batch([haystack], opts, unicode_mappings=True, boundaries=boundaries)[0]
         return self._search_ranked(haystack, opts.threshold_, opts.order_, opts.overlap_)
+
+    def _search_bounded(self, haystack: str, threshold: float, order: Order, overlap: Overlap, prefilter: bool,
+                        boundaries) -> FuzzyMatches:
+        """One haystack on the host route: search_raw, FuzzyMatches.retain_boundaries, then apply (the
+        per-document form the batch conveniences fall back to)."""
+        if not int(boundaries):
+            return self._search_ranked(haystack, threshold, order, overlap, prefilter=prefilter)
+        ms = self.search_raw(haystack, threshold, prefilter=prefilter).retain_boundaries(boundaries)
+        if order == Order.Unsorted and overlap == Overlap.Keep:
+            return ms
+        return self.apply_on_device(ms, order, overlap)
 
     def _segmented(self, haystack: str, opts: SearchOptions) -> FuzzyMatches:
         order = Order.Default if opts.order_ == Order.Unsorted else opts.order_
@@ -385,18 +401,21 @@ class FuzzyAhoCorasick:
 
     # -- many independent haystacks in one device pass (fac_search_batch)
     def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None,
-                     unicode_mappings: bool = False) -> List[FuzzyMatches]:
+                     unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[FuzzyMatches]:
         """`[self.search(h, opts) for h in haystacks]` as one call: every haystack is staged, searched
         and ranked as a text of its own (the crate has no such entry point; its answer to many
         documents is one engine shared by threads). Errors name the first offending document
         (`.doc` of the exception). `unicode_mappings` (here and in the other batch calls): an engine
         with multi-character mappings takes non-ASCII haystacks too (StagedBatch.allow_unicode_mappings;
-        default off: such a batch raises UnsupportedConfiguration)."""
+        default off: such a batch raises UnsupportedConfiguration). `boundaries` (here and in the
+        other batch calls): only matches whose named sides are word boundaries of their own haystack
+        reach ranking and overlap resolution (StagedBatch.require_boundaries)."""
         opts = opts or SearchOptions()
         haystacks = list(haystacks)
         enc = [h.encode("utf-8") for h in haystacks]
         data, offsets = batch_offsets(enc)
-        recs, doc_off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings).search_records(opts)
+        recs, doc_off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings,
+                                    boundaries=boundaries).search_records(opts)
         out = []
         for d, (hay, raw) in enumerate(zip(haystacks, enc)):
             rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
@@ -406,7 +425,7 @@ class FuzzyAhoCorasick:
         return out
 
     def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements,
-                      unicode_mappings: bool = False) -> List[str]:
+                      unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[str]:
         """`[self.replace(t, opts, lambda m: replacements[m.pattern_index]) for t in texts]` as one
         call (fac_replace_batch): searched, ranked and spliced on the device. `replacements` has one
         entry per pattern, `None` = keep the matched text (the callback's None, matches.rs:180-183).
@@ -416,11 +435,12 @@ class FuzzyAhoCorasick:
         enc = [t.encode("utf-8") for t in texts]
         data, offsets = batch_offsets(enc)
         table = replacements if isinstance(replacements, ReplacementTable) else ReplacementTable(self, replacements)
-        out, off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings).replace_bytes(table, opts)
+        out, off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings,
+                               boundaries=boundaries).replace_bytes(table, opts)
         return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
     def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None,
-                      unicode_mappings: bool = False) -> List[List[str]]:
+                      unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
         """Per text, one string per match of `self.search(t, opts)`, in its order, as one call
         (fac_extract_batch): the matched text, or with `replacements` (one entry per pattern, or a
         ReplacementTable) what replace would put in its place -- the entry, `Wrap` rendered around
@@ -429,36 +449,40 @@ class FuzzyAhoCorasick:
         if replacements is not None and not isinstance(replacements, ReplacementTable):
             table = ReplacementTable(self, replacements)
         return _extract_batch(self, [t.encode("utf-8") for t in texts], opts or SearchOptions(), table, False,
-                              unicode_mappings)
+                              unicode_mappings, boundaries)
 
     def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None,
-                              unicode_mappings: bool = False) -> List[List[str]]:
+                              unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
         """`[self.search(t, opts).matched_strings() for t in texts]` as one call (matches.rs:513-515)."""
-        return self.extract_batch(texts, opts, unicode_mappings=unicode_mappings)
+        return self.extract_batch(texts, opts, unicode_mappings=unicode_mappings, boundaries=boundaries)
 
     # -- the other segmentation helpers of a whole batch (fac_render_batch, fac_segment_batch): each is
     # one device call; whitespace is Rust's char::is_whitespace (DESIGN.md 6a "Batched segmentation")
-    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[str]:
+    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
+                           boundaries: Boundary = Boundary.NONE) -> List[str]:
         """`[self.strip_prefix(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_PREFIX, opts, False, unicode_mappings)
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_PREFIX, opts, False, unicode_mappings, boundaries)
 
-    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[str]:
+    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
+                           boundaries: Boundary = Boundary.NONE) -> List[str]:
         """`[self.strip_suffix(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, False, unicode_mappings)
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, False, unicode_mappings, boundaries)
 
-    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[str]:
+    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
+                           boundaries: Boundary = Boundary.NONE) -> List[str]:
         """`[self.segment_text(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, False, unicode_mappings)
+        return _render_batch(self, texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, False, unicode_mappings, boundaries)
 
-    def segment_batch(self, texts: Sequence[str], opts: SearchOptions,
-                      unicode_mappings: bool = False) -> List[List[Segment]]:
+    def segment_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
+                      boundaries: Boundary = Boundary.NONE) -> List[List[Segment]]:
         """`[list(self.segment_iter(t, opts)) for t in texts]` as one call."""
-        return _segment_batch(self, texts, opts, False, unicode_mappings)
+        return _segment_batch(self, texts, opts, False, unicode_mappings, boundaries)
 
-    def split_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False) -> List[List[str]]:
+    def split_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
+                    boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
         """`[list(self.split(t, opts)) for t in texts]` as one call."""
         return [[s.unmatched().text for s in segs if s.unmatched() is not None]
-                for segs in _segment_batch(self, texts, opts, False, unicode_mappings)]
+                for segs in _segment_batch(self, texts, opts, False, unicode_mappings, boundaries)]
 
 
 class Prefiltered:
@@ -503,10 +527,12 @@ class Prefiltered:
             return list(range(len(enc)))
         return [d for d, raw in enumerate(enc) if raw.isascii()]
 
-    def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None) -> List[FuzzyMatches]:
+    def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None,
+                     boundaries: Boundary = Boundary.NONE) -> List[FuzzyMatches]:
         """`[self.search(h, opts) for h in haystacks]`: the haystacks as one pre-filtered batch
         (fac_search_batch_prefiltered; `_batch_parts`: all of them, or the ASCII ones and the others
-        one by one), results in input order."""
+        one by one), results in input order. `boundaries` (here and in the other batch calls): as the
+        engine's; the documents searched one by one go through FuzzyMatches.retain_boundaries."""
         opts = opts or SearchOptions()
         haystacks = list(haystacks)
         enc = [h.encode("utf-8") for h in haystacks]
@@ -514,7 +540,8 @@ class Prefiltered:
         idx = self._batch_parts(enc)
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
-            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True)
+            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True,
+                             boundaries=boundaries)
             recs, doc_off = sb.search_records(opts, prefilter=True)
             for k, d in enumerate(idx):
                 rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
@@ -523,10 +550,11 @@ class Prefiltered:
                 out[d] = self.engine._to_matches(haystacks[d], enc[d], rows)
         for d, h in enumerate(haystacks):
             if out[d] is None:
-                out[d] = self.search(h, opts)
+                out[d] = self.engine._search_bounded(h, opts.threshold_, opts.order_, opts.overlap_, True, boundaries)
         return out
 
-    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements) -> List[str]:
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements,
+                      boundaries: Boundary = Boundary.NONE) -> List[str]:
         """`engine.replace_batch` over the pre-filtered search: the ASCII texts as one pre-filtered
         batch (fac_replace_batch_prefiltered), the others through `search` and the host splice of
         matches.rs:170-187, results in input order. `replacements`: one entry per pattern (None
@@ -542,7 +570,8 @@ class Prefiltered:
             table = ReplacementTable(self.engine, reps) if idx else None
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
-            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True)
+            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True,
+                             boundaries=boundaries)
             buf, off = sb.replace_bytes(table, opts, prefilter=True)
             for k, d in enumerate(idx):
                 out[d] = buf[int(off[k]):int(off[k + 1])].decode("utf-8")
@@ -550,11 +579,12 @@ class Prefiltered:
         overlap = Overlap.NonOverlapping if opts.overlap_ == Overlap.Keep else opts.overlap_
         for d, t in enumerate(texts):
             if out[d] is None:
-                ms = self.engine._search_ranked(t, opts.threshold_, order, overlap, prefilter=True)
+                ms = self.engine._search_bounded(t, opts.threshold_, order, overlap, True, boundaries)
                 out[d] = ms.replace(lambda m: _rendered_entry(reps[m.pattern_index], m))
         return out
 
-    def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None) -> List[List[str]]:
+    def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None,
+                      boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
         """`engine.extract_batch` over the pre-filtered search: the ASCII texts as one pre-filtered
         batch (fac_extract_batch_prefiltered), the others through `search`, results in input order."""
         opts = opts or SearchOptions()
@@ -568,24 +598,26 @@ class Prefiltered:
             reps = None if replacements is None else list(replacements)
             table = ReplacementTable(self.engine, reps) if idx and reps is not None else None
         if idx:
-            for d, items in zip(idx, _extract_batch(self.engine, [enc[d] for d in idx], opts, table, True, True)):
+            for d, items in zip(idx, _extract_batch(self.engine, [enc[d] for d in idx], opts, table, True, True,
+                                                  boundaries)):
                 out[d] = items
         for d, t in enumerate(texts):
             if out[d] is None:
-                out[d] = [_item_text(reps, m) for m in self.search(t, opts)]
+                out[d] = [_item_text(reps, m) for m in self.engine._search_bounded(
+                    t, opts.threshold_, opts.order_, opts.overlap_, True, boundaries)]
         return out
 
-    def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None) -> List[List[str]]:
+    def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None,
+                              boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
         """`[self.search(t, opts).matched_strings() for t in texts]`, batched as extract_batch is."""
-        return self.extract_batch(texts, opts)
+        return self.extract_batch(texts, opts, boundaries=boundaries)
 
-
-    def _segmented(self, haystack: str, opts: SearchOptions) -> FuzzyMatches:
+    def _segmented(self, haystack: str, opts: SearchOptions, boundaries=Boundary.NONE) -> FuzzyMatches:
         order = Order.Default if opts.order_ == Order.Unsorted else opts.order_
         overlap = Overlap.NonOverlapping if opts.overlap_ == Overlap.Keep else opts.overlap_
-        return self.engine._search_ranked(haystack, opts.threshold_, order, overlap, prefilter=True)
+        return self.engine._search_bounded(haystack, opts.threshold_, order, overlap, True, boundaries)
 
-    def _rendered(self, texts, mode: int, opts: SearchOptions, host) -> List[str]:
+    def _rendered(self, texts, mode: int, opts: SearchOptions, host, boundaries=Boundary.NONE) -> List[str]:
         """The ASCII texts as one pre-filtered batch (fac_render_batch_prefiltered), the others
         through `search` and the host method `host`, results in input order."""
         texts = list(texts)
@@ -593,23 +625,24 @@ class Prefiltered:
         out = [None] * len(texts)
         idx = self._batch_parts(enc)
         if idx:
-            for d, r in zip(idx, _render_batch(self.engine, [texts[d] for d in idx], mode, opts, True, True)):
+            for d, r in zip(idx, _render_batch(self.engine, [texts[d] for d in idx], mode, opts, True, True, boundaries)):
                 out[d] = r
         for d, t in enumerate(texts):
             if out[d] is None:
-                out[d] = host(self._segmented(t, opts))
+                out[d] = host(self._segmented(t, opts, boundaries))
         return out
 
-    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
-        return self._rendered(texts, _native.FAC_RENDER_STRIP_PREFIX, opts, lambda ms: ms.strip_prefix())
+    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_STRIP_PREFIX, opts, lambda ms: ms.strip_prefix(), boundaries)
 
-    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
-        return self._rendered(texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, lambda ms: ms.strip_suffix())
+    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, lambda ms: ms.strip_suffix(), boundaries)
 
-    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
-        return self._rendered(texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, lambda ms: ms.segment_text())
+    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, lambda ms: ms.segment_text(), boundaries)
 
-    def segment_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[Segment]]:
+    def segment_batch(self, texts: Sequence[str], opts: SearchOptions,
+                      boundaries: Boundary = Boundary.NONE) -> List[List[Segment]]:
         """The ASCII texts as one pre-filtered batch (fac_segment_batch_prefiltered), the others
         through `search` and the host's segment_iter, results in input order."""
         texts = list(texts)
@@ -617,16 +650,17 @@ class Prefiltered:
         out = [None] * len(texts)
         idx = self._batch_parts(enc)
         if idx:
-            for d, segs in zip(idx, _segment_batch(self.engine, [texts[d] for d in idx], opts, True, True)):
+            for d, segs in zip(idx, _segment_batch(self.engine, [texts[d] for d in idx], opts, True, True, boundaries)):
                 out[d] = segs
         for d, t in enumerate(texts):
             if out[d] is None:
-                out[d] = list(self._segmented(t, opts).segment_iter())
+                out[d] = list(self._segmented(t, opts, boundaries).segment_iter())
         return out
 
-    def split_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[str]]:
+    def split_batch(self, texts: Sequence[str], opts: SearchOptions,
+                    boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
         return [[s.unmatched().text for s in segs if s.unmatched() is not None]
-                for segs in self.segment_batch(texts, opts)]
+                for segs in self.segment_batch(texts, opts, boundaries)]
 
 
 def _as_text(r):
@@ -641,28 +675,31 @@ def _item_text(reps, m) -> str:
 
 
 def _extract_batch(engine: "FuzzyAhoCorasick", enc, opts: SearchOptions, table, prefilter: bool,
-                   unicode_mappings: bool = False) -> List[List[str]]:
+                   unicode_mappings: bool = False, boundaries=Boundary.NONE) -> List[List[str]]:
     data, offsets = batch_offsets(enc)
-    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings,
+                     boundaries=boundaries)
     _, doc_off, text, item_off = sb.extract(table, opts, prefilter=prefilter)
     return [[text[int(item_off[i]):int(item_off[i + 1])].decode("utf-8")
              for i in range(int(doc_off[d]), int(doc_off[d + 1]))] for d in range(len(enc))]
 
 
 def _render_batch(engine: "FuzzyAhoCorasick", texts, mode: int, opts: SearchOptions, prefilter: bool,
-                  unicode_mappings: bool = False) -> List[str]:
+                  unicode_mappings: bool = False, boundaries=Boundary.NONE) -> List[str]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
-    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings,
+                     boundaries=boundaries)
     out, off = sb.render_bytes(mode, opts, prefilter=prefilter)
     return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
 
 def _segment_batch(engine: "FuzzyAhoCorasick", texts, opts: SearchOptions, prefilter: bool,
-                   unicode_mappings: bool = False) -> List[List[Segment]]:
+                   unicode_mappings: bool = False, boundaries=Boundary.NONE) -> List[List[Segment]]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
-    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings)
+    sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings,
+                     boundaries=boundaries)
     recs, doc_off = sb.segment_records(opts, prefilter=prefilter)
     out = []
     for d, raw in enumerate(enc):
@@ -1180,7 +1217,7 @@ class StagedBatch:
     validity, is_ascii and grapheme segmentation per document)."""
 
     def __init__(self, engine: FuzzyAhoCorasick, data: bytes, offsets, unicode_prefilter: bool = False,
-                 unicode_mappings: bool = False):
+                 unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE):
         import numpy as np
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
         if off.ndim != 1 or len(off) < 1:
@@ -1202,16 +1239,19 @@ class StagedBatch:
             self.allow_unicode_prefilter()
         if unicode_mappings:
             self.allow_unicode_mappings()
+        if int(boundaries):
+            self.require_boundaries(boundaries)
 
     @classmethod
     def from_device(cls, engine: FuzzyAhoCorasick, d_utf8: int, d_offsets: int, n_docs: int, total_len: int,
                     stream=None, reuse: "StagedBatch" = None, unicode_prefilter: bool = False,
-                    unicode_mappings: bool = False) -> "StagedBatch":
+                    unicode_mappings: bool = False, boundaries: Boundary = None) -> "StagedBatch":
         """fac_batch_stage_device: the bytes (`d_utf8`, total_len of them) and the n_docs + 1 uint64
         offsets (`d_offsets`) are device addresses, e.g. torch tensors' data_ptr() (borrowed: keep both
         alive). `reuse`: a batch staged this way before, restaged in place and returned (it keeps its
-        opt-ins). `unicode_prefilter`, `unicode_mappings`: opt the batch in (allow_unicode_prefilter,
-        allow_unicode_mappings)."""
+        opt-ins and its require_boundaries mask). `unicode_prefilter`, `unicode_mappings`: opt the batch
+        in (allow_unicode_prefilter, allow_unicode_mappings). `boundaries`: require_boundaries (None:
+        a reused batch keeps what it had)."""
         h = ctypes.c_void_p(reuse._h.value if reuse is not None else None)
         ed = ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
         eg = ctypes.c_uint64()
@@ -1232,6 +1272,8 @@ class StagedBatch:
             obj.allow_unicode_prefilter()
         if unicode_mappings:
             obj.allow_unicode_mappings()
+        if boundaries is not None:
+            obj.require_boundaries(boundaries)
         return obj
 
     def __del__(self):
@@ -1254,6 +1296,16 @@ class StagedBatch:
         even if it holds non-ASCII documents (default off: every batch call raises
         UnsupportedConfiguration for such a batch). Returns self."""
         rc = _native.lib.fac_batch_allow_unicode_mappings(self._h, 1 if on else 0)
+        if rc:
+            _raise(rc)
+        return self
+
+    def require_boundaries(self, sides) -> "StagedBatch":
+        """fac_batch_require_boundaries: every later call on this batch, plain or pre-filtered, keeps
+        only the raw records whose sides `sides` (structs.Boundary; 0 = off) are word boundaries of
+        their own document, before ranking and overlap resolution (DESIGN.md 6a "Whole-token
+        matches"). Sets a flag and does no work. Returns self."""
+        rc = _native.lib.fac_batch_require_boundaries(self._h, int(sides))
         if rc:
             _raise(rc)
         return self
@@ -1652,10 +1704,11 @@ class FuzzyReplacer:
     def replace(self, text: str, opts: SearchOptions) -> str:
         return self.engine.replace(text, opts, self._callback)
 
-    def extract_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[List[str]]:
+    def extract_batch(self, texts: Sequence[str], opts: SearchOptions,
+                      boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
         """Per text, the replacement of every match `engine.search(t, opts)` finds, as one device pass
         (fac_extract_batch): the canonical form of each mention."""
-        return self.engine.extract_batch(texts, opts, self._device_table())
+        return self.engine.extract_batch(texts, opts, self._device_table(), boundaries=boundaries)
 
     def _device_table(self) -> "ReplacementTable":
         key = tuple(self.replacements)
@@ -1663,9 +1716,9 @@ class FuzzyReplacer:
             self._table = (key, ReplacementTable(self.engine, self.replacements))
         return self._table[1]
 
-    def replace_batch(self, texts: Sequence[str], opts: SearchOptions) -> List[str]:
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
         """`[self.replace(t, opts) for t in texts]` as one device pass (fac_replace_batch)."""
-        return self.engine.replace_batch(texts, opts, self._device_table())
+        return self.engine.replace_batch(texts, opts, self._device_table(), boundaries=boundaries)
 
     def replace_stream(self, reader, writer, threshold: float, prefilter: bool = False) -> int:
         """replacer.rs:35-44, spliced on the device (fac_replace_stream_*); `prefilter`: every window

@@ -261,6 +261,27 @@ class FuzzyMatches:
         self.inner = [m for m in self.inner if pred(m)]
         return self
 
+    def retain_boundaries(self, sides) -> "FuzzyMatches":
+        """Keep the matches whose sides `sides` (structs.Boundary) are word boundaries of the
+        haystack: the whole-token filter of DESIGN.md 6a, through fac_boundary_ok on the haystack's
+        bytes. To be called between search_raw and apply, as the crate's book describes: after the
+        overlap walk an in-word match may already have displaced a whole-token one."""
+        from . import _native
+        sides = int(sides)
+        if not 0 <= sides <= 3:
+            raise ValueError("sides must be a Boundary value (0..3)")
+        if sides:
+            data, n = self.hay_bytes, len(self.hay_bytes)
+            kept = []
+            for m in self.inner:
+                ok = _native.lib.fac_boundary_ok(data, n, m.start, m.end, sides)
+                if ok < 0:
+                    raise ValueError(_native.last_error())
+                if ok:
+                    kept.append(m)
+            self.inner = kept
+        return self
+
     def filter(self, pred) -> "FuzzyMatches":
         return FuzzyMatches(self.haystack, [m for m in self.inner if pred(m)], self.hay_bytes)
 

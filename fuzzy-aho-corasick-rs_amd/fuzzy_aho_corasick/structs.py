@@ -218,6 +218,15 @@ class Overlap(enum.Enum):
     NonOverlappingUnique = 2
 
 
+class Boundary(enum.IntFlag):
+    """The sides of a match that must be word boundaries (fac.h FAC_BOUNDARY_*, DESIGN.md 6a
+    "Whole-token matches"): the filter the crate's book describes between search_raw and apply."""
+    NONE = 0
+    START = 1
+    END = 2
+    WHOLE = 3
+
+
 DEFAULT_THRESHOLD = 0.0  # options.rs:7
 
 

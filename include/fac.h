@@ -454,6 +454,50 @@ int fac_batch_allow_unicode_prefilter(fac_batch* batch, int32_t on);
  * work; the flag survives a restage in place. Not to be called concurrently with a search of the
  * same batch. FAC_E_INVALID for NULL. */
 int fac_batch_allow_unicode_mappings(fac_batch* batch, int32_t on);
+
+/* ---- Whole-token matches. The search restarts at every grapheme, so "art" is found inside "party";
+ * the crate's answer is to filter search_raw's records by their surrounding characters before
+ * FuzzyMatches::apply. For a batch that filter runs on the device, between the search and the
+ * per-document apply, so an in-word match never takes part in the overlap walk.
+ *
+ * The rule. A record (start, end) of a document doc[0, n) has two sides; `sides` is a mask of
+ * FAC_BOUNDARY_START and FAC_BOUNDARY_END, and a record is kept when every requested side is a boundary.
+ *  - End side: a boundary when end == n, or when the code point that begins at byte `end` is not
+ *    alphanumeric. (No walk: `end` is a grapheme start.)
+ *  - Start side: walk left from `start` over code points. A transparent code point -- General_Category
+ *    M* (Mn, Mc, Me) and not alphanumeric: combining accents, variation selectors -- is skipped; the
+ *    first other code point decides, a boundary when it is not alphanumeric. Reaching byte 0 of the
+ *    document is a boundary. Having skipped 32 transparent code points without a decision is a
+ *    boundary too: a stated bound on the work per record, just above the 30 non-starters of the
+ *    Stream-Safe Text Format. (The walk keeps the accent of decomposed "cafe + U+0301 + bar" from passing
+ *    for a word break.)
+ *  - Alphanumeric is Rust's char::is_alphanumeric: the Alphabetic property, or General_Category
+ *    Nd / Nl / No. '_' and '-' are boundaries, U+00B2 and U+2160 are not; U+093E (an alphabetic Mc)
+ *    is alphanumeric, not transparent.
+ *  - A document's start and end are boundaries whatever its neighbours in the batch hold. Empty
+ *    spans follow the same rule. The rule reads the document's UTF-8 bytes only: it is the same for
+ *    ASCII and non-ASCII documents and does not depend on the engine, case folding or mappings.
+ *
+ * fac_batch_require_boundaries sets the mask of a batch (0 = off, the default; 0..3, anything else
+ * or NULL gives FAC_E_INVALID). It sets a flag and does no work; the flag survives a restage in
+ * place; not to be called concurrently with a search of the same batch. Every batch call on that
+ * batch, plain or pre-filtered (fac_search_batch, fac_replace_batch, fac_extract_batch,
+ * fac_segment_batch, fac_render_batch and their _prefiltered forms), then returns for every document
+ * apply(order, overlap) of the document's raw records with the rule applied first. With the mask
+ * off the calls launch and allocate nothing for it. Streams, fac_search_staged* and
+ * fac_matches_apply (which have no text) are not covered. */
+#define FAC_BOUNDARY_START 1
+#define FAC_BOUNDARY_END 2
+#define FAC_BOUNDARY_WHOLE 3
+int fac_batch_require_boundaries(fac_batch* batch, int32_t sides);
+/* Tests and hosts: bit 0 = alphanumeric, bit 1 = transparent (never both); 0 for surrogates and
+ * values above U+10FFFF. */
+int32_t fac_boundary_class(uint32_t cp);
+/* Tests and hosts: the rule above on the host, over one document's bytes: 1 = kept, 0 = dropped.
+ * A negative value is an error: -FAC_E_INVALID for NULL text with len > 0, sides outside 0..3,
+ * start > end, end > len, or an offset inside a code point (on a continuation byte). The text is
+ * taken as valid UTF-8 and not checked beyond that; no byte outside [0, len) is read. */
+int32_t fac_boundary_ok(const uint8_t* utf8, uint64_t len, uint64_t start, uint64_t end, int32_t sides);
 /* Tests and hosts: as fac_haystack_grapheme_ids for the graphemes of the batch's non-ASCII documents,
  * in document order (fac_batch_doc_graphemes of those documents, concatenated). An all-ASCII batch
  * writes nothing and returns 0. Needs no opt-in. */
