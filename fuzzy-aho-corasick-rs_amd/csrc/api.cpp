@@ -820,7 +820,7 @@ namespace fac {
 // task, stream_windows_docs, stands at the end of this file: it calls batch_kept, defined below.)
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
                          bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
-                         std::vector<uint64_t>* win_off, uint64_t* searched) {
+                         std::vector<uint64_t>* win_off, uint64_t* searched, const StreamBoundary* sb) {
   owned.clear();
   if (win_off) win_off->assign(n_windows + 1, 0);  // (the early returns below: no records at all)
   if (!h.ascii || h.open_end || h.base || n_windows == 0 || n_windows >= (1u << 24) || h.len >= (1ull << kWinTagShift))
@@ -872,10 +872,42 @@ int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* win
   }
   if (segs.empty()) return FAC_OK;
   if (searched) *searched += seg_windows(segs);
+  // whole-token matches (fac.h fac_stream_open_opts): the windows' sources and lengths, the carried
+  // context and the kernel's counter, one upload; the raw set is filtered in HBM into the record
+  // buffer's other half before it comes to the host
+  const bool flagged = sb && sb->sides;
+  DevMem d_sb(st);
+  StreamFilter sf;
+  unsigned long long* d_count = nullptr;
+  std::vector<uint64_t> sbt;
+  if (flagged) {
+    sbt.assign(2 * n_windows + kBoundaryCarry / 8 + 1, 0);
+    for (uint64_t w = 0; w < n_windows; ++w) {
+      sbt[w] = span[w].first;
+      sbt[n_windows + w] = span[w].second - span[w].first;
+    }
+    const uint32_t cn = std::min<uint32_t>(sb->before_len, kBoundaryCarry);
+    if (cn) std::memcpy(sbt.data() + 2 * n_windows, sb->before + (sb->before_len - cn), cn);
+    if (int rc = d_sb.alloc(sbt.size() * 8, err)) return rc;
+    if (hipMemcpyAsync(d_sb.p, sbt.data(), sbt.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
+      err = "upload of a stream task's boundary context failed";
+      return FAC_E_HIP;
+    }
+    const uint64_t* dt = static_cast<const uint64_t*>(d_sb.p);
+    sf.sides = sb->sides;
+    sf.d_text = h.d_utf8;
+    sf.text_len = h.len;
+    sf.d_src = dt;
+    sf.d_len = dt + n_windows;
+    sf.n_windows = n_windows;
+    sf.d_before = reinterpret_cast<const uint8_t*>(dt + 2 * n_windows);
+    sf.before_len = cn;
+    d_count = reinterpret_cast<unsigned long long*>(static_cast<uint64_t*>(d_sb.p) + sbt.size() - 1);
+  }
   uint64_t cap = 1u << 16;
   for (;;) {  // raw records into a device buffer, grown and searched again if it was too small
     DevMem raw(st);
-    if (int rc = raw.alloc(cap * sizeof(fac_match), err)) return rc;
+    if (int rc = raw.alloc((flagged ? 2 : 1) * cap * sizeof(fac_match), err)) return rc;
     MatchSink sink;
     sink.dev = static_cast<fac_match*>(raw.p);
     sink.dev_cap = cap;
@@ -883,6 +915,13 @@ int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* win
     if (sink.n > cap) {
       cap = sink.n;
       continue;
+    }
+    if (flagged && sink.n) {
+      uint64_t kept = 0;
+      if (int rc = stream_boundary_filter_device(e.device, sf, sink.dev, sink.n, sink.dev + cap, d_count, st, &kept, err))
+        return rc;
+      sink.dev += cap;
+      sink.n = kept;
     }
     std::vector<fac_match> recs(sink.n);
     if (sink.n) {
@@ -1322,6 +1361,18 @@ int32_t fac_boundary_ok(const uint8_t* utf8, uint64_t len, uint64_t start, uint6
   return fac::boundary_ok(utf8, len, start, end, sides) ? 1 : 0;
 }
 
+int32_t fac_boundary_ok_after(const uint8_t* before, uint64_t before_len, int32_t more_before, const uint8_t* utf8,
+                              uint64_t len, uint64_t start, uint64_t end, int32_t sides) {
+  if ((len && !utf8) || (before_len && !before) || sides < 0 || sides > FAC_BOUNDARY_WHOLE)
+    return -(int32_t)fail(FAC_E_INVALID, "bad argument");
+  if (start > end || end > len) return -(int32_t)fail(FAC_E_INVALID, "span outside the text");
+  if ((start < len && (utf8[start] & 0xC0) == 0x80) || (end < len && (utf8[end] & 0xC0) == 0x80))
+    return -(int32_t)fail(FAC_E_INVALID, "span not on a character boundary");
+  const int ok = fac::boundary_ok_after(before, before_len, more_before != 0, utf8, len, start, end, sides);
+  if (ok < 0) return -(int32_t)fail(FAC_E_INVALID, "the context before the text is too short to decide the start side");
+  return ok;
+}
+
 int64_t fac_batch_grapheme_ids(const fac_engine* engine, const fac_batch* batch, void* stream, uint32_t* out, uint64_t cap) {
   if (!engine || !batch) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
   return grapheme_ids_out(engine->e, batch->b.h, stream, out, cap);
@@ -1394,7 +1445,7 @@ struct BatchKept {
 // (optional): += the start windows handed to the search launcher
 static int batch_kept(const fac::Engine& e, const fac::Batch& b, float threshold, int order, int overlap,
                       const uint64_t* unique_ids, bool prefilter, hipStream_t st, uint64_t* d_doc_user, fac_stats* stats,
-                      BatchKept& k, std::string& err, uint64_t* searched = nullptr) {
+                      BatchKept& k, std::string& err, uint64_t* searched = nullptr, const fac::StreamFilter* sf = nullptr) {
   const uint64_t nd = b.n_docs;
   fac::BatchWindows pw;  // pre-filtered: every document's merged windows, found once
   bool filtered = false;
@@ -1424,6 +1475,14 @@ static int batch_kept(const fac::Engine& e, const fac::Batch& b, float threshold
       // kernel its counter (the apply writes the index afterwards)
       if (int rc = fac::boundary_filter_device(b, b.boundaries, recs, n, other, static_cast<unsigned long long*>(k.doff.p),
                                                st, &n, err))
+        return rc;
+      std::swap(recs, other);
+    } else if (sf && n) {
+      // the window documents of a flagged stream (fac.h fac_stream_open_opts): the stream's filter at
+      // the same point, which reads a window's neighbours from the task's text and the carried
+      // context (a document's start is no boundary there)
+      if (int rc = fac::stream_boundary_filter_device(b.h.device, *sf, recs, n, other,
+                                                      static_cast<unsigned long long*>(k.doff.p), st, &n, err))
         return rc;
       std::swap(recs, other);
     }
@@ -1893,10 +1952,17 @@ int fac_stream_open(const fac_engine* engine, float threshold, uint64_t window_b
 
 int fac_stream_open_ex(const fac_engine* engine, float threshold, uint64_t window_bytes, int32_t prefilter,
                        fac_stream** out) {
-  if (!engine || !out) return fail(FAC_E_INVALID, "NULL argument");
+  const fac_stream_options o{threshold, window_bytes, prefilter, 0};
+  return fac_stream_open_opts(engine, &o, out);
+}
+
+int fac_stream_open_opts(const fac_engine* engine, const fac_stream_options* options, fac_stream** out) {
+  if (!engine || !options || !out) return fail(FAC_E_INVALID, "NULL argument");
+  if (options->boundaries < 0 || options->boundaries > FAC_BOUNDARY_WHOLE) return fail(FAC_E_INVALID, "boundaries must be 0..3");
   fac_stream* fs = new (std::nothrow) fac_stream();
   if (!fs) return fail(FAC_E_OOM, "out of host memory");
-  fs->s = fac::stream_open(engine->e, threshold, window_bytes, nullptr, prefilter != 0);
+  fs->s = fac::stream_open(engine->e, options->threshold, options->window_bytes, nullptr, options->prefilter != 0,
+                           options->boundaries);
   *out = fs;
   return FAC_OK;
 }
@@ -1958,13 +2024,21 @@ uint64_t fac_replace_stream_windows_searched(const fac_replace_stream* stream) {
 
 int fac_replace_stream_open_ex(const fac_engine* engine, const fac_replacements* replacements, float threshold,
                                uint64_t window_bytes, int32_t prefilter, fac_replace_stream** out) {
-  if (!engine || !replacements || !out) return fail(FAC_E_INVALID, "NULL argument");
+  const fac_stream_options o{threshold, window_bytes, prefilter, 0};
+  return fac_replace_stream_open_opts(engine, replacements, &o, out);
+}
+
+int fac_replace_stream_open_opts(const fac_engine* engine, const fac_replacements* replacements,
+                                 const fac_stream_options* options, fac_replace_stream** out) {
+  if (!engine || !replacements || !options || !out) return fail(FAC_E_INVALID, "NULL argument");
   *out = nullptr;
+  if (options->boundaries < 0 || options->boundaries > FAC_BOUNDARY_WHOLE) return fail(FAC_E_INVALID, "boundaries must be 0..3");
   if (replacements->t.device != engine->e.device || replacements->t.n_patterns != engine->e.pats.size())
     return fail(FAC_E_INVALID, "the replacement table was built for another engine");
   fac_replace_stream* fs = new (std::nothrow) fac_replace_stream();
   if (!fs) return fail(FAC_E_OOM, "out of host memory");
-  fs->s = fac::stream_open(engine->e, threshold, window_bytes, &replacements->t, prefilter != 0);
+  fs->s = fac::stream_open(engine->e, options->threshold, options->window_bytes, &replacements->t, options->prefilter != 0,
+                           options->boundaries);
   *out = fs;
   return FAC_OK;
 }
@@ -2150,14 +2224,18 @@ namespace fac {
 // the commit cut run on the device, and only the owned records and their index come back.
 int stream_windows_docs(const Engine& e, WindowDocs& wd, const uint8_t* d_text, uint64_t text_len, const uint64_t* wins,
                         uint64_t n_windows, float threshold, bool prefilter, hipStream_t st, std::vector<fac_match>& owned,
-                        std::string& err, std::vector<uint64_t>& win_off, uint64_t* searched) {
+                        std::string& err, std::vector<uint64_t>& win_off, uint64_t* searched, const StreamBoundary* sb) {
   owned.clear();
   win_off.assign(n_windows + 1, 0);
   if (n_windows == 0) return FAC_OK;
   if (n_windows > kBatchMaxDocs) return FAC_E_UNSUPPORTED;
   const uint64_t n = n_windows;
-  // sources [0, n), lengths and their closing entry [n, 2n], commit points, rebase offsets
-  std::vector<uint64_t> tab(4 * n + 1, 0);
+  const bool flagged = sb && sb->sides;
+  // sources [0, n), lengths and their closing entry [n, 2n], commit points, rebase offsets; for
+  // whole-token matches (fac.h fac_stream_open_opts) the carried context travels behind them
+  std::vector<uint64_t> tab(4 * n + 1 + (flagged ? kBoundaryCarry / 8 : 0), 0);
+  const uint32_t cn = flagged ? std::min<uint32_t>(sb->before_len, kBoundaryCarry) : 0;
+  if (cn) std::memcpy(tab.data() + 4 * n + 1, sb->before + (sb->before_len - cn), cn);
   uint64_t total = 0;
   for (uint64_t w = 0; w < n; ++w) {
     const uint64_t off = wins[4 * w], end = wins[4 * w + 1];
@@ -2218,8 +2296,20 @@ int stream_windows_docs(const Engine& e, WindowDocs& wd, const uint8_t* d_text, 
     return rc;
   }
   BatchKept k(st);
+  StreamFilter sf;
+  if (flagged) {  // the window documents never take the batch filter: a document's start is no boundary here
+    sf.sides = sb->sides;
+    sf.d_text = d_text;
+    sf.text_len = text_len;
+    sf.d_src = dt;
+    sf.d_len = dt + n;
+    sf.d_doc_off = b.d_offsets;
+    sf.n_windows = n;
+    sf.d_before = reinterpret_cast<const uint8_t*>(dt + 4 * n + 1);
+    sf.before_len = cn;
+  }
   if ((rc = batch_kept(e, b, threshold, /*Default*/ 1, /*NonOverlapping*/ 1, nullptr, prefilter, st, nullptr, nullptr, k, err,
-                       searched)))
+                       searched, flagged ? &sf : nullptr)))
     return rc;
   return windows_owned_device(k.res, k.n_res, k.d_doc, n, dt + 2 * n + 1, dt + 3 * n + 1, st, owned, win_off, err);
 }

@@ -11,6 +11,13 @@
 // half of the call's record buffer (wave ballot, lane prefix, one atomic per wave); the order of the
 // compacted records is not the order of the raw ones, which no caller relies on (every order the
 // apply produces is a total order; Unsorted + Keep is unspecified within a document).
+//
+// The same pass for the raw records of a stream task (fac.h fac_stream_open_opts; stream.cpp
+// run_window_task), where the document is the stream and not the window: the start side's walk goes
+// on to the left of the window's first byte, into the task's text and then into the up to
+// kBoundaryCarry bytes the task carries over from its predecessor, and only byte 0 of the stream is
+// a boundary by position; the end side is decided inside the window's text. It reads the task's
+// original text, never the gathered per-window copies, which have no left context.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -133,6 +140,81 @@ __global__ __launch_bounds__(kThreads) void boundary_filter_kernel(const uint4* 
   }
 }
 
+// The start side of a stream window's record at byte `start` of the task's text s: the walk of
+// start_is_boundary, going on to the left of s[0] into the cn bytes at ctx (the stream's text just
+// before the task). Positions are relative to s[0]; the context holds [-cn, 0). Its front is the
+// start of the stream, or kBoundaryCarry bytes away, which the walk's kBoundaryMaxSkip code points
+// cannot cross undecided.
+__device__ __forceinline__ bool stream_start_is_boundary(const uint8_t* __restrict__ s, const uint8_t* __restrict__ ctx,
+                                                         int64_t cn, const uint8_t* __restrict__ tab, uint64_t start) {
+  const int64_t front = -cn;
+  int64_t p = (int64_t)start;
+  for (uint32_t skipped = 0; skipped < kBoundaryMaxSkip; ++skipped) {
+    if (p <= front) return true;
+    // the code point that ends at p: its bytes, last first (a commit point is a character boundary,
+    // so no code point has bytes on both sides of s[0]; reading byte by byte needs no such promise)
+    uint32_t b[4];
+    uint32_t k = 0;
+    int64_t q = p;
+    do {
+      --q;
+      b[k++] = q >= 0 ? s[q] : ctx[cn + q];
+    } while (q > front && k < 4 && (b[k - 1] & 0xC0u) == 0x80u);
+    const uint32_t b0 = b[k - 1];
+    uint32_t cp = 0xFFFDu;
+    if (b0 < 0x80u) cp = b0;
+    else if ((b0 & 0xE0u) == 0xC0u && k == 2) cp = ((b0 & 0x1Fu) << 6) | (b[0] & 0x3Fu);
+    else if ((b0 & 0xF0u) == 0xE0u && k == 3) cp = ((b0 & 0x0Fu) << 12) | ((b[1] & 0x3Fu) << 6) | (b[0] & 0x3Fu);
+    else if ((b0 & 0xF8u) == 0xF0u && k == 4)
+      cp = ((b0 & 0x07u) << 18) | ((b[2] & 0x3Fu) << 12) | ((b[1] & 0x3Fu) << 6) | (b[0] & 0x3Fu);
+    const uint32_t c = class_of(tab, cp);
+    if (!(c & 2u)) return (c & 1u) == 0;
+    p = q;
+  }
+  return true;
+}
+
+// One thread per raw record of a stream task (fac_internal.h StreamFilter): start / end tagged with
+// the window; the same compaction as boundary_filter_kernel.
+__global__ __launch_bounds__(kThreads) void stream_boundary_filter_kernel(
+    const uint4* __restrict__ in, uint64_t n, const uint8_t* __restrict__ text, uint64_t text_len,
+    const uint64_t* __restrict__ src, const uint64_t* __restrict__ len, const uint64_t* __restrict__ doc_off,
+    uint64_t n_windows, const uint8_t* __restrict__ ctx, uint32_t ctx_len, const uint8_t* __restrict__ tab, uint32_t sides,
+    uint4* __restrict__ out, unsigned long long* count) {
+  const uint32_t lane = lane_id();
+  for (uint64_t base = (uint64_t)blockIdx.x * kThreads; base < n; base += (uint64_t)gridDim.x * kThreads) {
+    const uint64_t i = base + threadIdx.x;
+    bool keep = false;
+    uint4 a = make_uint4(0, 0, 0, 0), b = a;
+    if (i < n) {
+      a = in[2 * i];
+      b = in[2 * i + 1];
+      const uint64_t ts = ((uint64_t)a.y << 32) | a.x, te = ((uint64_t)a.w << 32) | a.z;
+      const uint64_t w = ts >> kDocTagShift;
+      keep = true;
+      if (w < n_windows) {
+        const uint64_t lo = src[w], hi = lo + len[w];
+        // the record's span in the task's text
+        const uint64_t shift = doc_off ? lo - doc_off[w] : 0;
+        const uint64_t st = (ts & kDocLow) + shift, en = (te & kDocLow) + shift;
+        if (lo <= st && st <= en && en <= hi && hi <= text_len) {  // (always: only such a span is read around)
+          if (sides & FAC_BOUNDARY_END) keep = end_is_boundary(text, tab, en, hi);
+          if (keep && (sides & FAC_BOUNDARY_START)) keep = stream_start_is_boundary(text, ctx, (int64_t)ctx_len, tab, st);
+        }
+      }
+    }
+    const uint64_t m = __ballot(keep);
+    if (m == 0) continue;  // wave-uniform
+    unsigned long long at = 0;
+    if (lane == 0) at = atomicAdd(count, (unsigned long long)__popcll(m));
+    at = shfl_u64(at, 0) + prefix_below(m);
+    if (keep) {
+      out[2 * at] = a;
+      out[2 * at + 1] = b;
+    }
+  }
+}
+
 // the class table of `device`, built on first use (kept for the process)
 int boundary_table(int device, hipStream_t st, const uint8_t*& out, std::string& err) {
   static std::mutex mu;
@@ -169,6 +251,29 @@ int boundary_filter_device(const Batch& b, int sides, const fac_match* d_in, uin
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kThreads - 1) / kThreads, kMaxBlocks);
   hipLaunchKernelGGL(boundary_filter_kernel, dim3(grid), dim3(kThreads), 0, s, reinterpret_cast<const uint4*>(d_in), n,
                      b.h.d_utf8, b.d_offsets, b.n_docs, tab, (uint32_t)sides, reinterpret_cast<uint4*>(d_out), d_count);
+  HIP_TRY(hipGetLastError());
+  unsigned long long kept = 0;
+  HIP_TRY(hipMemcpyAsync(&kept, d_count, sizeof(kept), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_kept = kept;
+  return FAC_OK;
+}
+
+int stream_boundary_filter_device(int device, const StreamFilter& f, const fac_match* d_in, uint64_t n, fac_match* d_out,
+                                  unsigned long long* d_count, hipStream_t s, uint64_t* n_kept, std::string& err) {
+  *n_kept = 0;
+  if (n == 0) return FAC_OK;
+  if (f.before_len > kBoundaryCarry || (f.before_len && !f.d_before)) {
+    err = "a stream task's boundary context is malformed";
+    return FAC_E_INTERNAL;
+  }
+  const uint8_t* tab = nullptr;
+  if (int rc = boundary_table(device, s, tab, err)) return rc;
+  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kThreads - 1) / kThreads, kMaxBlocks);
+  hipLaunchKernelGGL(stream_boundary_filter_kernel, dim3(grid), dim3(kThreads), 0, s, reinterpret_cast<const uint4*>(d_in), n,
+                     f.d_text, f.text_len, f.d_src, f.d_len, f.d_doc_off, f.n_windows, f.d_before, f.before_len, tab,
+                     (uint32_t)f.sides, reinterpret_cast<uint4*>(d_out), d_count);
   HIP_TRY(hipGetLastError());
   unsigned long long kept = 0;
   HIP_TRY(hipMemcpyAsync(&kept, d_count, sizeof(kept), hipMemcpyDeviceToHost, s));

@@ -44,6 +44,14 @@ uint32_t fold_first_char(const uint8_t* s, uint64_t b, uint64_t e, bool ci);
 constexpr uint32_t kBoundaryMaxSkip = 32;  // transparent code points the start side walks over
 uint32_t boundary_class(uint32_t cp);
 bool boundary_ok(const uint8_t* s, uint64_t n, uint64_t start, uint64_t end, int sides);
+// The rule for a stream window (fac.h fac_stream_open_opts): s[0, n) is the window's text and
+// before[0, before_len) the stream's text just before it; the start side's walk goes on into the
+// context, and its front is the stream's start only when !more_before. 1 kept, 0 dropped, -1 when
+// the walk reaches the front of a context that has text before it undecided (never with
+// before_len >= kBoundaryCarry: the walk reads at most kBoundaryMaxSkip code points of 4 bytes).
+constexpr uint32_t kBoundaryCarry = 4 * kBoundaryMaxSkip;
+int boundary_ok_after(const uint8_t* before, uint64_t before_len, bool more_before, const uint8_t* s, uint64_t n,
+                      uint64_t start, uint64_t end, int sides);
 
 // ---------------------------------------------------------------- device layout
 constexpr uint32_t EDGE_SINGLE_BYTE = 1u << 31;
@@ -627,6 +635,36 @@ int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t
 // of device scratch. Reads b.h.d_utf8 inside the record's document only; synchronises once.
 int boundary_filter_device(const Batch& b, int sides, const fac_match* d_in, uint64_t n, fac_match* d_out,
                            unsigned long long* d_count, hipStream_t s, uint64_t* n_kept, std::string& err);
+// The whole-token mask of a stream task (fac.h fac_stream_open_opts) and the stream's text before
+// the task's first byte: the last before_len (<= kBoundaryCarry) bytes of it, on the host;
+// more_before: the stream has text before those.
+struct StreamBoundary {
+  int sides = 0;
+  const uint8_t* before = nullptr;
+  uint32_t before_len = 0;
+  bool more_before = false;
+};
+// boundary_kernels.hip: the same filter for the raw records of a stream task, tagged with their
+// window (bits kWinTagShift and up). Window w is bytes [d_src[w], d_src[w] + d_len[w]) of the task's
+// text_len bytes at d_text. d_doc_off NULL: the records hold offsets of that text (the ASCII union
+// path); else offsets of the expanded text, where window w's copy begins at d_doc_off[w] (the
+// window-documents path). Neighbours are read from d_text -- never from the expanded copies, which
+// have no left context -- and, left of its byte 0, from the before_len bytes at d_before, whose
+// front is the start of the stream or far enough away (StreamBoundary). The end side is decided
+// inside the window: a record that ends at its window's end is kept.
+struct StreamFilter {
+  int sides = 0;
+  const uint8_t* d_text = nullptr;
+  uint64_t text_len = 0;
+  const uint64_t* d_src = nullptr;
+  const uint64_t* d_len = nullptr;
+  const uint64_t* d_doc_off = nullptr;
+  uint64_t n_windows = 0;
+  const uint8_t* d_before = nullptr;
+  uint32_t before_len = 0;
+};
+int stream_boundary_filter_device(int device, const StreamFilter& f, const fac_match* d_in, uint64_t n, fac_match* d_out,
+                                  unsigned long long* d_count, hipStream_t s, uint64_t* n_kept, std::string& err);
 
 // replace_kernels.hip: the splice of a batch (fac.h fac_replace_batch; matches.rs:165-188 per
 // document). A replacement table holds per pattern {offset into d_bytes, byte length}, the length
@@ -951,6 +989,11 @@ struct StreamCore {
   uint64_t read = 64 * 1024;  // the reader's read() size (stream.rs:102-158; FAC_STREAM_READ_BYTES)
   // every window's text is searched as Prefiltered::search (fac_stream_open_ex; prefilter.rs:304-374)
   bool prefilter = false;
+  // whole-token matches (fac.h fac_stream_open_opts): the FAC_BOUNDARY_* mask every window's raw
+  // records are filtered by before they are ranked, 0 = off; `tail`: the stream's last
+  // kBoundaryCarry bytes before buf[0], kept only with a mask (a task's left context)
+  int boundaries = 0;
+  std::vector<uint8_t> tail;
   // start windows of the segments handed to the search launcher, for the windows handed out so far
   uint64_t windows_searched = 0;
   // tasks handed out so far that were searched in one pass (stream_windows_batch or
@@ -973,7 +1016,7 @@ struct StreamCore {
 
 // table: NULL for a search stream; else the stream replaces (the table outlives the stream)
 StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table = nullptr,
-                        bool prefilter = false);
+                        bool prefilter = false, int boundaries = 0);
 int stream_feed(StreamCore& s, const uint8_t* data, uint64_t len, bool eof, std::string& err);
 void stream_close(StreamCore* s);
 uint64_t stream_committed(const StreamCore& s);  // commit point of the windows handed out so far
@@ -1022,7 +1065,8 @@ void windows_owned_host(const Engine& e, std::vector<fac_match>& recs, const std
 // win_off (optional): the CSR index of the windows into `owned`, n_windows + 1 entries
 int stream_windows_batch(const Engine& e, const Haystack& h, const uint64_t* wins, uint64_t n_windows, float threshold,
                          bool prefilter, hipStream_t st, std::vector<fac_match>& owned, fac_stats* stats, std::string& err,
-                         std::vector<uint64_t>* win_off = nullptr, uint64_t* searched = nullptr);
+                         std::vector<uint64_t>* win_off = nullptr, uint64_t* searched = nullptr,
+                         const StreamBoundary* sb = nullptr);  // sb with sides != 0: whole-token matches of a stream
 // stage_kernels.hip: the expanded text of a stream task. Window w is bytes [d_src[w], d_src[w] +
 // d_len[w]) of the text_len bytes at d_text (every range inside the text, checked by the caller;
 // d_len has a closing entry); the n_windows + 1 document offsets go to d_offsets (exclusive sums of
@@ -1050,7 +1094,8 @@ struct WindowDocs {
 // FAC_E_UNSUPPORTED (nothing done): more than 2^24 windows or 2^40 expanded bytes.
 int stream_windows_docs(const Engine& e, WindowDocs& wd, const uint8_t* d_text, uint64_t text_len, const uint64_t* wins,
                         uint64_t n_windows, float threshold, bool prefilter, hipStream_t st, std::vector<fac_match>& owned,
-                        std::string& err, std::vector<uint64_t>& win_off, uint64_t* searched);
+                        std::string& err, std::vector<uint64_t>& win_off, uint64_t* searched,
+                        const StreamBoundary* sb = nullptr);
 // prefilter_kernels.hip: merged bitap windows (prefilter.rs:319-342) of a text view of a staged haystack (view.ascii:
 // bytes [text_base, text_base + n) of h.d_utf8; else graphemes [text_base, text_base + n)); windows
 // in the view's local grapheme coordinates

@@ -30,6 +30,15 @@
 // copies and kernels overlap batch k's (double buffering) while the host cuts the windows of batch
 // k + 2. Finished batches are handed out strictly in window order.
 //
+// Whole-token matches (fac_stream_open_opts, StreamCore::boundaries): with a mask every
+// window's raw records are filtered by the boundary rule before they are ranked, the start side
+// looking to the left of the window into the stream's earlier text. The batched paths filter in HBM
+// (boundary_kernels.hip stream_boundary_filter_kernel) over the task's text; a single window is
+// filtered on the host (boundary_ok_after). The text before a task's first byte has left the
+// buffer by then, so the reader keeps the stream's last kBoundaryCarry bytes as it drops the
+// committed prefix (drop_prefix) and every task carries the kBoundaryCarry bytes before its base:
+// the walk reads at most kBoundaryMaxSkip code points. With the mask 0 nothing of this runs.
+//
 // Replace mode (fac_replace_stream_*; stream.rs:465-517 + ReplaceCursor::emit_window, :645-705): a
 // task's text stays on the device after the search, its owned records go back up, and the plan and
 // copy kernels of replace_kernels.hip splice the task's output, which is copied to the host and
@@ -58,6 +67,10 @@ struct StreamWin {
 struct StreamTask {
   std::vector<uint8_t> text;
   uint64_t base = 0;
+  // whole-token matches (StreamCore::boundaries): the stream's last bytes before `base`, at most
+  // kBoundaryCarry of them, and whether the stream has text before those
+  std::vector<uint8_t> before;
+  bool more_before = false;
   std::vector<StreamWin> wins;
   std::vector<fac_match> res;  // owned matches of every window, in window order, absolute offsets
   std::vector<uint8_t> res_text;
@@ -111,6 +124,35 @@ int search_one_window(const StreamCore& s, StreamWorker& w, StreamTask& t, const
     } else {
       t.searched += seg.w_end - seg.w_begin;
       rc = launch_search(*s.e, h, {seg}, s.threshold, w.stream, res, nullptr, err);
+    }
+    if (!rc && s.boundaries && !res.empty()) {
+      // whole-token matches: the host rule on the raw records, with the text to the window's left
+      // (the task's text before it, then the task's carried context)
+      std::vector<uint8_t> ctx;
+      const uint8_t* before = nullptr;
+      uint64_t bl = 0;
+      if (win.off >= kBoundaryCarry) {
+        before = t.text.data() + (win.off - kBoundaryCarry);
+        bl = kBoundaryCarry;
+      } else {
+        const uint64_t take = std::min<uint64_t>(t.before.size(), kBoundaryCarry - win.off);
+        ctx.assign(t.before.end() - (ptrdiff_t)take, t.before.end());
+        ctx.insert(ctx.end(), t.text.begin(), t.text.begin() + (ptrdiff_t)win.off);
+        before = ctx.data();
+        bl = ctx.size();
+      }
+      const bool more = t.base + win.off > bl;  // else the context's front is byte 0 of the stream
+      size_t kept = 0;
+      for (const fac_match& m : res) {
+        const int ok = boundary_ok_after(before, bl, more, t.text.data() + win.off, win.len, m.start, m.end, s.boundaries);
+        if (ok < 0) {
+          err = "a stream window's boundary context is too short";
+          rc = FAC_E_INTERNAL;
+          break;
+        }
+        if (ok) res[kept++] = m;
+      }
+      res.resize(kept);
     }
     if (!rc) rc = apply_matches(*s.e, res, /*Default*/ 1, /*NonOverlapping*/ 1, nullptr, err);
     if (!rc)
@@ -217,6 +259,11 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
   Haystack h;  // the whole task's text (the ASCII path); resident until the splice is done
   void* up = nullptr;  // the same for the window-documents path
   const bool multi = t.wins.size() > 1;
+  StreamBoundary sb;
+  sb.sides = s.boundaries;
+  sb.before = t.before.data();
+  sb.before_len = (uint32_t)t.before.size();
+  sb.more_before = t.more_before;
   std::vector<uint64_t> wins(multi ? 4 * t.wins.size() : 0);
   for (size_t i = 0; multi && i < t.wins.size(); ++i) {
     wins[4 * i] = t.wins[i].off;
@@ -230,7 +277,7 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
     if (!t.rc) {
       uint64_t searched = 0;
       const int rc = stream_windows_batch(*s.e, h, wins.data(), t.wins.size(), s.threshold, s.prefilter, w.stream, owned,
-                                          nullptr, t.err, &win_off, &searched);
+                                          nullptr, t.err, &win_off, &searched, &sb);
       if (rc != FAC_E_UNSUPPORTED) {  // (unsupported: pre-filter tables that need the packed full scan)
         t.rc = rc;
         t.searched += searched;
@@ -257,7 +304,7 @@ void run_window_task(StreamCore& s, StreamWorker& w, StreamTask& t) {
     if (!t.rc) {
       uint64_t searched = 0;
       const int rc = stream_windows_docs(*s.e, w.docs, d_text, t.text.size(), wins.data(), t.wins.size(), s.threshold,
-                                         s.prefilter, w.stream, owned, t.err, win_off, &searched);
+                                         s.prefilter, w.stream, owned, t.err, win_off, &searched, &sb);
       if (rc != FAC_E_UNSUPPORTED) {  // (unsupported: more windows or bytes than a batch holds)
         t.rc = rc;
         t.searched += searched;
@@ -411,6 +458,20 @@ int flush_batch(StreamCore& s, std::string& err) {
   return dispatch(s, t, err);
 }
 
+// Whole-token matches: s.tail keeps the stream's last kBoundaryCarry bytes before buf[0] as the
+// committed prefix buf[0, at) is dropped, so a task that begins later still has its left context.
+void drop_prefix(StreamCore& s, uint64_t at) {
+  if (s.boundaries && at) {
+    if (at >= kBoundaryCarry) {
+      s.tail.assign(s.buf.begin() + (ptrdiff_t)(at - kBoundaryCarry), s.buf.begin() + (ptrdiff_t)at);
+    } else {
+      s.tail.insert(s.tail.end(), s.buf.begin(), s.buf.begin() + (ptrdiff_t)at);
+      if (s.tail.size() > kBoundaryCarry) s.tail.erase(s.tail.begin(), s.tail.end() - (ptrdiff_t)kBoundaryCarry);
+    }
+  }
+  s.buf.erase(s.buf.begin(), s.buf.begin() + (ptrdiff_t)at);
+}
+
 int pump(StreamCore& s, bool eof, std::string& err) {
   // the buffer's unconsumed bytes start at `at` (the committed prefix is dropped once per call: an
   // erase per window moved the rest of a large feed again for every window)
@@ -440,6 +501,14 @@ int pump(StreamCore& s, bool eof, std::string& err) {
     if (!s.pending) {
       s.pending = new StreamTask();
       s.pending->base = s.base;
+      if (s.boundaries) {  // the last bytes before the task: of buf[0, at), then of the saved tail
+        std::vector<uint8_t>& c = s.pending->before;
+        const uint64_t from_buf = std::min<uint64_t>(at, kBoundaryCarry);
+        const uint64_t from_tail = std::min<uint64_t>(s.tail.size(), kBoundaryCarry - from_buf);
+        c.assign(s.tail.end() - (ptrdiff_t)from_tail, s.tail.end());
+        c.insert(c.end(), s.buf.begin() + (ptrdiff_t)(at - from_buf), s.buf.begin() + (ptrdiff_t)at);
+        s.pending->more_before = s.base > c.size();
+      }
     }
     StreamTask* t = s.pending;
     const uint64_t off = s.base - t->base;  // the window's first byte in the batch text
@@ -454,11 +523,11 @@ int pump(StreamCore& s, bool eof, std::string& err) {
     s.carry = len - commit;
     if (t->text.size() >= s.batch_bytes)
       if (int rc = flush_batch(s, err)) {
-        s.buf.erase(s.buf.begin(), s.buf.begin() + (ptrdiff_t)at);
+        drop_prefix(s, at);
         return rc;
       }
   }
-  s.buf.erase(s.buf.begin(), s.buf.begin() + (ptrdiff_t)at);
+  drop_prefix(s, at);
   if (eof || s.done)
     if (int rc = flush_batch(s, err)) return rc;
   return collect(s, eof, err);
@@ -475,9 +544,11 @@ int stream_feed(StreamCore& s, const uint8_t* data, uint64_t len, bool eof, std:
   return pump(s, eof, err);
 }
 
-StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table, bool prefilter) {
+StreamCore* stream_open(const Engine& e, float threshold, uint64_t window, const ReplaceTable* table, bool prefilter,
+                        int boundaries) {
   StreamCore* s = new StreamCore();
   s->e = &e;
+  s->boundaries = boundaries;
   s->threshold = threshold;
   s->table = table;
   s->prefilter = prefilter;

@@ -369,4 +369,33 @@ bool boundary_ok(const uint8_t* s, uint64_t n, uint64_t start, uint64_t end, int
   return true;
 }
 
+int boundary_ok_after(const uint8_t* before, uint64_t before_len, bool more_before, const uint8_t* s, uint64_t n,
+                      uint64_t start, uint64_t end, int sides) {
+  if ((sides & FAC_BOUNDARY_END) && end < n) {
+    uint64_t i = end;
+    if (boundary_class(utf8_decode(s, n, i)) & 1u) return 0;
+  }
+  if (sides & FAC_BOUNDARY_START) {
+    // positions are relative to s[0]: the context holds [-before_len, 0)
+    const int64_t front = -(int64_t)before_len;
+    auto at = [&](int64_t i) { return i >= 0 ? s[i] : before[(int64_t)before_len + i]; };
+    int64_t p = (int64_t)start;
+    for (uint32_t skipped = 0; skipped < kBoundaryMaxSkip; ++skipped) {
+      if (p <= front) return more_before ? -1 : 1;  // only byte 0 of the stream is a boundary by position
+      int64_t q = p - 1;  // the first byte of the code point that ends at p
+      while (q > front && p - q < 4 && (at(q) & 0xC0) == 0x80) --q;
+      // a context cut inside a code point: its tail bytes are not a code point of their own
+      if (more_before && q == front && (at(q) & 0xC0) == 0x80) return -1;
+      uint8_t cp[4];
+      const uint64_t k = (uint64_t)(p - q);
+      for (uint64_t j = 0; j < k; ++j) cp[j] = at(q + (int64_t)j);
+      uint64_t i = 0;
+      const uint32_t c = boundary_class(utf8_decode(cp, k, i));
+      if (!(c & 2u)) return (c & 1u) ? 0 : 1;
+      p = q;
+    }
+  }
+  return 1;
+}
+
 }  // namespace fac

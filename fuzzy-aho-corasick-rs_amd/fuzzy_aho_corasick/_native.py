@@ -110,6 +110,11 @@ class fac_extract_args(ctypes.Structure):
                 ("device_text_cap", ctypes.c_uint64), ("device_item_offsets", ctypes.c_void_p)]
 
 
+class fac_stream_options(ctypes.Structure):
+    _fields_ = [("threshold", ctypes.c_float), ("window_bytes", ctypes.c_uint64), ("prefilter", ctypes.c_int32),
+                ("boundaries", ctypes.c_int32)]
+
+
 FAC_NO_INSERT = 0xFFFFFFFFFFFFFFFF  # insert_at of a plain entry (fac_replacements_create_templates)
 EXTRACT_TILE = 4096  # output bytes one workgroup of the extraction's copy kernel owns
 REPLACE_TILE = 4096  # output bytes one workgroup of the splice's copy kernel owns (kReplaceTile)
@@ -202,6 +207,9 @@ SIGNATURES = {
     "fac_stream_open": (ctypes.c_int, [_engine_p, ctypes.c_float, ctypes.c_uint64, _P(ctypes.c_void_p)]),
     "fac_stream_open_ex": (ctypes.c_int, [_engine_p, ctypes.c_float, ctypes.c_uint64, ctypes.c_int32,
                                           _P(ctypes.c_void_p)]),
+    "fac_stream_open_opts": (ctypes.c_int, [_engine_p, _P(fac_stream_options), _P(ctypes.c_void_p)]),
+    "fac_replace_stream_open_opts": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_stream_options),
+                                                    _P(ctypes.c_void_p)]),
     "fac_stream_windows_searched": (ctypes.c_uint64, [ctypes.c_void_p]),
     "fac_replace_stream_open_ex": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint64,
                                                   ctypes.c_int32, _P(ctypes.c_void_p)]),
@@ -250,6 +258,8 @@ SIGNATURES = {
     "fac_boundary_class": (ctypes.c_int32, [ctypes.c_uint32]),
     "fac_boundary_ok": (ctypes.c_int32, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_int32]),
+    "fac_boundary_ok_after": (ctypes.c_int32, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_char_p,
+                                               ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32]),
     "fac_batch_grapheme_ids": (ctypes.c_int64, [_engine_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_uint64]),
     "fac_haystack_grapheme_ids": (ctypes.c_int64, [_engine_p, _hay_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -246,10 +246,14 @@ class FuzzyAhoCorasick:
         return self._to_matches(haystack, data, _native.take_matches(out, count))
 
     # -- stream.rs
-    def search_stream(self, reader, threshold: float, on_match, window: int = 0, _prefilter: bool = False) -> int:
+    def search_stream(self, reader, threshold: float, on_match, window: int = 0, _prefilter: bool = False,
+                      boundaries: Boundary = Boundary.NONE) -> int:
         """stream.rs:299-328: search a byte stream (anything with .read(n)) in overlapping windows,
-        calling `on_match(StreamMatch)` with absolute offsets; returns the bytes read."""
-        st = _Stream(self, threshold, window, prefilter=_prefilter)
+        calling `on_match(StreamMatch)` with absolute offsets; returns the bytes read. `boundaries`
+        (here and in the other stream calls; non-zero): only matches whose named sides are word
+        boundaries of the stream's text reach a window's ranking and overlap resolution; the start
+        side looks to the left of the window into the text read before it (fac_stream_open_opts)."""
+        st = _Stream(self, threshold, window, prefilter=_prefilter, boundaries=boundaries)
         while True:
             chunk = reader.read(READ_CHUNK)
             for m in st.feed(chunk or b"", eof=not chunk):
@@ -257,22 +261,24 @@ class FuzzyAhoCorasick:
             if not chunk:
                 return st.total()
 
-    def stream_matches(self, reader, threshold: float, window: int = 0, _prefilter: bool = False):
+    def stream_matches(self, reader, threshold: float, window: int = 0, _prefilter: bool = False,
+                       boundaries: Boundary = Boundary.NONE):
         """stream.rs:330-352: the same, lazily, as an iterator of StreamMatch."""
-        st = _Stream(self, threshold, window, prefilter=_prefilter)
+        st = _Stream(self, threshold, window, prefilter=_prefilter, boundaries=boundaries)
         while True:
             chunk = reader.read(READ_CHUNK)
             yield from st.feed(chunk or b"", eof=not chunk)
             if not chunk:
                 return
 
-    def search_stream_parallel(self, reader, threshold: float, threads: int, on_match) -> int:
+    def search_stream_parallel(self, reader, threshold: float, threads: int, on_match,
+                               boundaries: Boundary = Boundary.NONE) -> int:
         """stream.rs:378-429. The device path already searches two windows at a time (one HIP
         stream each, fac_stream); `threads` is accepted for API parity."""
-        return self.search_stream(reader, threshold, on_match)
+        return self.search_stream(reader, threshold, on_match, boundaries=boundaries)
 
     def replace_stream(self, reader, writer, threshold: float, callback, window: int = 0,
-                       _prefilter: bool = False) -> int:
+                       _prefilter: bool = False, boundaries: Boundary = Boundary.NONE) -> int:
         """stream.rs:462-503 + ReplaceCursor::emit_window (:645-705): streaming find-and-replace.
         Every owned match (per window: sorted().non_overlapping(), start < commit, ordered by
         (start, end)) is replaced by `callback(m)` (a str; None keeps the matched text) unless it
@@ -283,7 +289,7 @@ class FuzzyAhoCorasick:
         callable is called per match on the host."""
         if not callable(callback):
             table = callback if isinstance(callback, ReplacementTable) else ReplacementTable(self, callback)
-            st = _ReplaceStream(self, table, threshold, window, prefilter=_prefilter)
+            st = _ReplaceStream(self, table, threshold, window, prefilter=_prefilter, boundaries=boundaries)
             while True:
                 chunk = reader.read(READ_CHUNK)
                 out = st.feed(chunk or b"", eof=not chunk)
@@ -291,7 +297,7 @@ class FuzzyAhoCorasick:
                     writer.write(out)
                 if not chunk:
                     return st.written()
-        st = _Stream(self, threshold, window, prefilter=_prefilter)
+        st = _Stream(self, threshold, window, prefilter=_prefilter, boundaries=boundaries)
         pending = bytearray()  # stream bytes [emitted, read) not yet written
         emitted = written = 0
 
@@ -325,10 +331,11 @@ class FuzzyAhoCorasick:
                 return written
             emit(ms, max(emitted, st.committed()))
 
-    def replace_stream_parallel(self, reader, writer, threads: int, threshold: float, callback) -> int:
+    def replace_stream_parallel(self, reader, writer, threads: int, threshold: float, callback,
+                                boundaries: Boundary = Boundary.NONE) -> int:
         """stream.rs:533-638: same output as replace_stream (windows are pipelined on the device);
         `callback` as there."""
-        return self.replace_stream(reader, writer, threshold, callback)
+        return self.replace_stream(reader, writer, threshold, callback, boundaries=boundaries)
 
     def apply_on_device(self, matches: FuzzyMatches, order: Order, overlap: Overlap) -> FuzzyMatches:
         """FuzzyMatches::apply of an existing match list through fac_matches_apply (same input
@@ -500,23 +507,28 @@ class Prefiltered:
 
     # -- stream.rs over Prefiltered::search: every window's text goes through the bitap pre-filter on
     # the device (fac_stream_open_ex / fac_replace_stream_open_ex); signatures as the engine's
-    def search_stream(self, reader, threshold: float, on_match, window: int = 0) -> int:
-        return self.engine.search_stream(reader, threshold, on_match, window, _prefilter=True)
+    def search_stream(self, reader, threshold: float, on_match, window: int = 0,
+                      boundaries: Boundary = Boundary.NONE) -> int:
+        return self.engine.search_stream(reader, threshold, on_match, window, _prefilter=True, boundaries=boundaries)
 
-    def stream_matches(self, reader, threshold: float, window: int = 0):
-        return self.engine.stream_matches(reader, threshold, window, _prefilter=True)
+    def stream_matches(self, reader, threshold: float, window: int = 0, boundaries: Boundary = Boundary.NONE):
+        return self.engine.stream_matches(reader, threshold, window, _prefilter=True, boundaries=boundaries)
 
-    def search_stream_parallel(self, reader, threshold: float, threads: int, on_match) -> int:
+    def search_stream_parallel(self, reader, threshold: float, threads: int, on_match,
+                               boundaries: Boundary = Boundary.NONE) -> int:
         """As the engine's: two windows are in flight on the device; `threads` is accepted for API parity."""
-        return self.search_stream(reader, threshold, on_match)
+        return self.search_stream(reader, threshold, on_match, boundaries=boundaries)
 
-    def replace_stream(self, reader, writer, threshold: float, callback, window: int = 0) -> int:
+    def replace_stream(self, reader, writer, threshold: float, callback, window: int = 0,
+                       boundaries: Boundary = Boundary.NONE) -> int:
         """A table or list `callback` is spliced on the device; a callable runs over the pre-filtered
         search stream on the host."""
-        return self.engine.replace_stream(reader, writer, threshold, callback, window, _prefilter=True)
+        return self.engine.replace_stream(reader, writer, threshold, callback, window, _prefilter=True,
+                                          boundaries=boundaries)
 
-    def replace_stream_parallel(self, reader, writer, threads: int, threshold: float, callback) -> int:
-        return self.replace_stream(reader, writer, threshold, callback)
+    def replace_stream_parallel(self, reader, writer, threads: int, threshold: float, callback,
+                                boundaries: Boundary = Boundary.NONE) -> int:
+        return self.replace_stream(reader, writer, threshold, callback, boundaries=boundaries)
 
     def _batch_parts(self, enc):
         """Indices of the documents one pre-filtered batch takes: all of them where the filter is
@@ -751,9 +763,11 @@ class StreamMatch:
 class _Stream:
     """fac_stream: WindowReader + per-window search on the GPU (stream.rs:77-297)."""
 
-    def __init__(self, engine: "FuzzyAhoCorasick", threshold: float, window: int = 0, prefilter: bool = False):
+    def __init__(self, engine: "FuzzyAhoCorasick", threshold: float, window: int = 0, prefilter: bool = False,
+                 boundaries: Boundary = Boundary.NONE):
         h = ctypes.c_void_p()
-        rc = _native.lib.fac_stream_open_ex(engine._h, f32(threshold), window, int(bool(prefilter)), ctypes.byref(h))
+        o = _native.fac_stream_options(f32(threshold), window, int(bool(prefilter)), int(boundaries))
+        rc = _native.lib.fac_stream_open_opts(engine._h, ctypes.byref(o), ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h
@@ -806,10 +820,10 @@ class _ReplaceStream:
     (stream.rs:465-517, 645-705) against a ReplacementTable."""
 
     def __init__(self, engine: "FuzzyAhoCorasick", table: "ReplacementTable", threshold: float, window: int = 0,
-                 prefilter: bool = False):
+                 prefilter: bool = False, boundaries: Boundary = Boundary.NONE):
         h = ctypes.c_void_p()
-        rc = _native.lib.fac_replace_stream_open_ex(engine._h, table._h, f32(threshold), window, int(bool(prefilter)),
-                                                    ctypes.byref(h))
+        o = _native.fac_stream_options(f32(threshold), window, int(bool(prefilter)), int(boundaries))
+        rc = _native.lib.fac_replace_stream_open_opts(engine._h, table._h, ctypes.byref(o), ctypes.byref(h))
         if rc:
             _raise(rc)
         self._h = h
@@ -1720,7 +1734,10 @@ class FuzzyReplacer:
         """`[self.replace(t, opts) for t in texts]` as one device pass (fac_replace_batch)."""
         return self.engine.replace_batch(texts, opts, self._device_table(), boundaries=boundaries)
 
-    def replace_stream(self, reader, writer, threshold: float, prefilter: bool = False) -> int:
+    def replace_stream(self, reader, writer, threshold: float, prefilter: bool = False,
+                       boundaries: Boundary = Boundary.NONE) -> int:
         """replacer.rs:35-44, spliced on the device (fac_replace_stream_*); `prefilter`: every window
-        is searched through the bitap pre-filter (Prefiltered::search)."""
-        return self.engine.replace_stream(reader, writer, threshold, self._device_table(), _prefilter=prefilter)
+        is searched through the bitap pre-filter (Prefiltered::search); `boundaries`: as
+        engine.search_stream's."""
+        return self.engine.replace_stream(reader, writer, threshold, self._device_table(), _prefilter=prefilter,
+                                          boundaries=boundaries)

@@ -484,8 +484,30 @@ int fac_batch_allow_unicode_mappings(fac_batch* batch, int32_t on);
  * batch, plain or pre-filtered (fac_search_batch, fac_replace_batch, fac_extract_batch,
  * fac_segment_batch, fac_render_batch and their _prefiltered forms), then returns for every document
  * apply(order, overlap) of the document's raw records with the rule applied first. With the mask
- * off the calls launch and allocate nothing for it. Streams, fac_search_staged* and
- * fac_matches_apply (which have no text) are not covered. */
+ * off the calls launch and allocate nothing for it.
+ *
+ * Streams are covered: fac_stream_open_opts / fac_replace_stream_open_opts take the same mask in
+ * fac_stream_options::boundaries. The rule is applied per window, to the window's raw records,
+ * before that window's sorted().non_overlapping() and before the ownership cut (start < commit),
+ * as the batch calls apply it per document. What a window counts as "the document":
+ *  - Start side: the walk to the left runs over the stream's text, not the window's. It goes on
+ *    past the window's first byte into the bytes the stream read before it (a window begins at its
+ *    predecessor's commit point, a grapheme boundary in the middle of the text). Only byte 0 of the
+ *    stream is a boundary by position. The walk reads at most 32 code points, so the last 4 x 32 =
+ *    128 bytes before a window always decide it, and that is all a device task carries over from
+ *    its predecessor.
+ *  - End side: decided inside the window's text. end == the window text's length is a boundary
+ *    (the final window's end is the stream's end); otherwise the code point at `end` decides. A
+ *    window's result is therefore a function of the window and the text before it alone, whatever
+ *    the grouping of windows into device tasks or the feeding. A record that ends at a non-final
+ *    window's end is never owned by that window: an owned record starts before the commit point
+ *    and spans at most max_match_graphemes graphemes, and the overlap is one more than that, so at
+ *    least two graphemes of the window follow it. Such a record only takes part in that window's
+ *    overlap walk; the next window owns it and judges it with its real right-hand neighbour.
+ *  - With the mask 0 a stream launches, allocates, uploads and carries nothing for the feature.
+ * Not covered: fac_search_staged*, fac_matches_apply (which have no text) and the staged-window
+ * calls of the multi-GPU C5 path, fac_stream_window[s]_staged[_device] and
+ * fac_replace_windows_staged_device. */
 #define FAC_BOUNDARY_START 1
 #define FAC_BOUNDARY_END 2
 #define FAC_BOUNDARY_WHOLE 3
@@ -498,6 +520,15 @@ int32_t fac_boundary_class(uint32_t cp);
  * start > end, end > len, or an offset inside a code point (on a continuation byte). The text is
  * taken as valid UTF-8 and not checked beyond that; no byte outside [0, len) is read. */
 int32_t fac_boundary_ok(const uint8_t* utf8, uint64_t len, uint64_t start, uint64_t end, int32_t sides);
+/* Tests and hosts: the stream rule above on the host. utf8[0, len) is a window's text and
+ * before[0, before_len) the stream's text that precedes it; more_before != 0 says the stream has
+ * text before `before`, so reaching its front is not the stream's start. Returns and errors as
+ * fac_boundary_ok (before == NULL with before_len > 0 included); also -FAC_E_INVALID when the
+ * start side's walk reaches the front of `before` undecided while more_before != 0, which cannot
+ * happen with before_len >= 128. `before` may begin inside a code point: its leading continuation
+ * bytes are never read as a code point. */
+int32_t fac_boundary_ok_after(const uint8_t* before, uint64_t before_len, int32_t more_before, const uint8_t* utf8,
+                              uint64_t len, uint64_t start, uint64_t end, int32_t sides);
 /* Tests and hosts: as fac_haystack_grapheme_ids for the graphemes of the batch's non-ASCII documents,
  * in document order (fac_batch_doc_graphemes of those documents, concatenated). An all-ASCII batch
  * writes nothing and returns 0. Needs no opt-in. */
@@ -758,6 +789,16 @@ int fac_stream_open(const fac_engine* engine, float threshold, uint64_t window_b
  * filter, or an edit budget over 24 at this threshold) the stream is the unfiltered stream. */
 int fac_stream_open_ex(const fac_engine* engine, float threshold, uint64_t window_bytes, int32_t prefilter,
                        fac_stream** out);
+/* The options form of the two calls above, and the one that takes the whole-token mask ("Whole-token
+ * matches" above, the rule for a stream). FAC_E_INVALID for a NULL argument or a mask outside 0..3;
+ * boundaries == 0 is fac_stream_open_ex. */
+typedef struct fac_stream_options {
+  float threshold;
+  uint64_t window_bytes; /* 0 = the crate's 256 KiB */
+  int32_t prefilter;     /* as fac_stream_open_ex */
+  int32_t boundaries;    /* FAC_BOUNDARY_* mask, 0 = off */
+} fac_stream_options;
+int fac_stream_open_opts(const fac_engine* engine, const fac_stream_options* options, fac_stream** out);
 /* Tests and hosts: the start windows of the segments handed to the search launcher, for the windows
  * handed out so far: the graphemes of every window's text for a plain stream (bytes where a window's
  * text is ASCII), the lengths of every window's merged bitap windows for a pre-filtered one. */
@@ -794,6 +835,10 @@ int fac_replace_stream_open(const fac_engine* engine, const fac_replacements* re
 /* fac_replace_stream_open with fac_stream_open_ex's `prefilter`; the replace cursor does not change. */
 int fac_replace_stream_open_ex(const fac_engine* engine, const fac_replacements* replacements, float threshold,
                                uint64_t window_bytes, int32_t prefilter, fac_replace_stream** out);
+/* fac_replace_stream_open_ex with fac_stream_options (its whole-token mask included): only the set
+ * of owned records changes; the splice, the cursor and its guard do not. */
+int fac_replace_stream_open_opts(const fac_engine* engine, const fac_replacements* replacements,
+                                 const fac_stream_options* options, fac_replace_stream** out);
 uint64_t fac_replace_stream_windows_searched(const fac_replace_stream* stream);
 /* fac_stream_task_counts of a replace stream. */
 void fac_replace_stream_task_counts(const fac_replace_stream* stream, uint64_t* batched, uint64_t* single);
