@@ -2166,6 +2166,15 @@ uint32_t fac_diag_rc_store_gate(uint64_t carried, uint64_t built, uint32_t backo
   return fac::rc_store_gate(carried, built, backoff, gate_min);
 }
 
+uint32_t fac_diag_rc_emptied_gate(int32_t decision, int32_t after_fill, uint32_t backoff) {
+  return fac::rc_store_emptied_gate(decision, after_fill != 0, backoff);
+}
+
+int32_t fac_diag_rc_direct_decide(uint32_t unknown_pm, int32_t floor_pm, uint32_t margin_pm, uint64_t sampled,
+                                  uint64_t windows, uint64_t min_windows) {
+  return fac::rc_direct_decide(unknown_pm, floor_pm, margin_pm, sampled, windows, min_windows) ? 1 : 0;
+}
+
 int fac_diag_stream_gather(const fac_engine* engine, const uint8_t* utf8, uint64_t len, const uint64_t* windows,
                            uint64_t n_windows, uint8_t* out, uint64_t cap, uint64_t* offsets) {
   if (!engine || !offsets || (len && !utf8) || (n_windows && !windows) || (cap && !out))

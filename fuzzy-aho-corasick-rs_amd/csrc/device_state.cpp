@@ -95,6 +95,25 @@ uint32_t rc_store_gate(uint64_t carried, uint64_t built, uint32_t backoff, uint6
   return backoff ? std::min<uint32_t>(64, 2 * backoff) : 1;
 }
 
+// Fresh-word text fills the pool in one call, so every call after it starts the store empty for `pool`
+// or `directory` and pays the clears and inserts for nothing, and the gate above, which judges carrying
+// calls only, never sees one. A call that empties the store for either reason right after the call that
+// filled it from empty doubles the back-off as a carrying call under a tenth does, and goes without the
+// store itself. (A signature reset is the caller's doing, not the text's: it does not count.)
+uint32_t rc_store_emptied_gate(int decision, bool after_fill, uint32_t backoff) {
+  if (!after_fill || (decision != kRcPool && decision != kRcDirectory)) return 0;
+  return backoff ? std::min<uint32_t>(64, 2 * backoff) : 1;
+}
+
+// Keys seen once are never selected, so some share of a text's windows is unknown even on the call
+// after a full one over the same text: the floor. A call within margin_pm of it would build next to
+// nothing. Below min_windows the sample says little (and few windows cost little either way).
+bool rc_direct_decide(uint32_t unknown_pm, int32_t floor_pm, uint32_t margin_pm, uint64_t sampled, uint64_t windows,
+                      uint64_t min_windows) {
+  if (floor_pm < 0 || sampled == 0 || windows < min_windows) return false;
+  return (uint64_t)unknown_pm <= (uint64_t)floor_pm + margin_pm;
+}
+
 int rc_store_decide(const RcStore& s, const uint32_t sig[kRcSigWords], uint64_t want_cap, uint64_t cap_limit) {
   if (s.sleep) return kRcGated;  // (the caller counts the call and goes without the store)
   if (!s.valid || s.used == 0) return kRcFresh;
@@ -119,9 +138,11 @@ int rc_store_prepare(RcStore& s, int decision, const uint32_t sig[kRcSigWords], 
   if (decision == kRcKeep) {  // this call's carried counts start at zero
     HIP_TRY(hipMemsetAsync(s.dev + 1, 0, 9 * sizeof(unsigned long long), st));
     ++s.calls;
+    s.filled = false;
     return FAC_OK;
   }
   s.valid = false;
+  s.filled = true;
   if (!s.pool || s.cap < want_cap) {
     if (s.pool) HIP_TRY(hipFree(s.pool));
     s.pool = nullptr;
@@ -140,8 +161,17 @@ int rc_store_prepare(RcStore& s, int decision, const uint32_t sig[kRcSigWords], 
   s.pending = kRcKeep;
   std::memset(s.last_built, 0, sizeof(s.last_built));
   std::memset(s.carried, 0, sizeof(s.carried));
+  s.lv_n = 0;
+  s.kstart = 0;
+  s.floor_pm = -1;
+  s.has_dense = false;
   s.calls = 1;
   s.valid = true;
+  return FAC_OK;
+}
+
+int rc_store_dense(RcStore& s, size_t words, std::string& err) {
+  if (!s.dense) HIP_TRY(hipMalloc((void**)&s.dense, words * sizeof(uint32_t)));
   return FAC_OK;
 }
 
@@ -196,12 +226,20 @@ void rc_store_drop(RcStore& s) {
     d.peak = peak;
   }
   if (s.last) (void)hipEventDestroy(s.last);
+  if (s.dense) (void)hipFree(s.dense);
   s.pool = nullptr;
   s.dev = nullptr;
   s.last = nullptr;
+  s.dense = nullptr;
   s.cap = s.used = s.last_call = 0;
   s.valid = false;
   s.pending = kRcKeep;
+  std::memset(s.sig, 0, sizeof(s.sig));
+  s.lv_n = 0;
+  s.kstart = 0;
+  s.floor_pm = -1;
+  s.has_dense = false;
+  s.filled = false;
 }
 
 void free_engine_device(Engine& e) {

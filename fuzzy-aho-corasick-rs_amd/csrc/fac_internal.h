@@ -369,6 +369,9 @@ struct GraphemeTable {
 // from call scratch and no carry-over). Host state only here: device_state.cpp owns the allocations.
 constexpr int kRcSigWords = 16;
 constexpr uint32_t RC_TOBUILD = 0xFFFFFFFDu;  // rc_off of an entry rc_carry_kernel did not find
+// a call goes direct with an unknown share up to this far (per mille) above the store's floor
+// (FAC_RC_DIRECT_PM; the sweep is in DESIGN.md §6)
+constexpr uint32_t kRcDirectPm = 20;
 enum RcReset { kRcKeep = 0, kRcFresh, kRcSignature, kRcPool, kRcDirectory, kRcBusy, kRcOff, kRcGated };
 const char* rc_reset_name(int r);
 struct RcStoreDir {
@@ -393,11 +396,22 @@ struct RcStore {
   uint64_t last_built[9] = {};   // entries the previous call built, by key length (sizes the waves' pool chunks)
   uint64_t carried[9] = {};      // entries the last call carried over, by key length
   // device words: [0] pool words used, [1 + k] entries carried at key length k (this call),
-  // [10 + k] keys in directory k
+  // [10 + k] keys in directory k, [20] rc_store_sample_kernel's counts
   unsigned long long* dev = nullptr;
-  static constexpr int kDevWords = 20;
+  static constexpr int kDevWords = 21;
   hipEvent_t last = nullptr;     // the previous user's last work on the store
   uint64_t calls = 0;
+  // Direct calls: what the last full call left for a call that searches from the
+  // directories alone. Reset with the directories (rc_store_prepare, rc_store_drop).
+  uint32_t lv_k[kRcLevels] = {}; // that call's levels, deepest first (key lengths)
+  uint32_t lv_n = 0;
+  uint32_t kstart = 0;           // its SearchParams::rc_kstart
+  uint64_t lv_knobs = 0;         // a hash of the level knobs it ran under (FAC_RC_K, FAC_RC_LEVELS, ...)
+  int32_t floor_pm = -1;         // the unknown share (per mille of sampled windows) it left; < 0: none yet
+  uint32_t* dense = nullptr;     // its dense start-level bitmaps (RC_DENSE_WORDS words, allocated on first use)
+  bool has_dense = false;
+  // the emptied-store gate: the last call that used the store started it empty (rc_store_emptied_gate)
+  bool filled = false;
 };
 // what a call does with the store it has locked (no device work): kRcKeep carries over, every other
 // value starts from an empty store (kRcFresh: it was empty already)
@@ -412,6 +426,16 @@ int rc_store_dir(RcStore& s, uint32_t k, uint64_t n_ent, hipStream_t st, std::st
 int rc_store_finish(RcStore& s, uint64_t cap_limit, bool carrying, uint64_t gate_min, std::string& err);
 // the gate alone: the back-off after a carrying call with these totals (0: the store stays in use)
 uint32_t rc_store_gate(uint64_t carried, uint64_t built, uint32_t backoff, uint64_t gate_min);
+// the gate for a store that every call empties: the calls that go without the store, this one included,
+// when `decision` (rc_store_decide) empties the store for its pool or a directory right after the call
+// that filled it from empty (after_fill); 0: the rule does not apply and the call goes on as decided
+uint32_t rc_store_emptied_gate(int decision, bool after_fill, uint32_t backoff);
+// a call searches from the store's directories alone (no counts, selections or builds): unknown_pm of
+// its `sampled` windows ended on a key no directory holds, against the share the last full call left
+// (floor_pm, < 0: none) plus margin_pm; calls of fewer than min_windows windows never do
+bool rc_direct_decide(uint32_t unknown_pm, int32_t floor_pm, uint32_t margin_pm, uint64_t sampled, uint64_t windows,
+                      uint64_t min_windows);
+int rc_store_dense(RcStore& s, size_t words, std::string& err);  // s.dense allocated (contents untouched)
 void rc_store_drop(RcStore& s);  // frees everything (the caller holds mu)
 
 struct Engine {

@@ -2528,7 +2528,9 @@ __device__ __forceinline__ uint32_t rc_probe(const RcTable& T, const uint32_t* c
       break;
     }
   }
-  if (!hit) return 0u;
+  // (a direct call probes the store's directories, which also hold the keys a build left uncached,
+  // offset EMPTY: a miss that ends the deeper walk, as an absent key is)
+  if (!hit || val.x == EMPTY) return 0u;
   const uint32_t nq = val.z & 0xFFFFu;
   if (nq + 1u > QCAP) return 3u;
   h = RcHit{val.x, val.y, val.y + nq, ((val.w >> 22) & 0x1FFu) | (val.z & 0xFFFF0000u), val.w & RC_POPS_MASK, t};
@@ -2796,6 +2798,56 @@ __global__ __launch_bounds__(256) void rc_store_insert_kernel(SearchParams P, co
     }
   }
   rc_wave_count(n_keys, n_new);
+}
+// Direct calls: how much of a call's text the store knows, from one thread per sampled window -- the
+// launch's threads spread evenly over the call's windows (all of them if there are fewer; a key part
+// through its list), skipped windows left out. P.rc_tab holds the store's directories, deepest first
+// (P.rc_ntab, P.rc_kstart, P.rc_qcap as the lookups take them). A window takes rc_lookup_deep's walk:
+// the start level, deeper while the hit is an open snapshot. It is unknown when the walk ends on a key
+// the directory of that length does not hold at all; a snapshot, a key stored as uncached, or a level
+// the window's text cannot be probed at all leave it known. out += unknown | sampled << 16 per wave
+// (at most 16384 threads in all).
+__global__ __launch_bounds__(256) void rc_store_sample_kernel(SearchParams P, uint64_t windows, unsigned long long* out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, ns = (uint64_t)gridDim.x * blockDim.x;
+  bool sampled = false, unknown = false;
+  if (g < min(windows, ns)) {
+    const uint64_t i = windows <= ns ? g : g * windows / ns;
+    const uint64_t v = P.kp_wlist ? P.kp_wlist[i] : i;
+    const uint32_t kl = find_seg(P, v);
+    const SegDesc S = P.segs[kl];
+    const uint64_t start = S.w_begin + (v - P.seg_prefix[kl]);
+    unsigned err = 0;
+    if (!window_skipped(P, S, start, err)) {
+      sampled = true;
+      RcKey K;
+      rc_key_of(P, S, start, K);
+      const uint32_t st = rc_start_level(P);
+      bool up = true;
+#pragma unroll
+      for (int t = kRcLevels - 1; t >= 0; --t) {
+        if (!up || (uint32_t)t > st || (uint32_t)t >= P.rc_ntab) continue;
+        const RcTable& T = P.rc_tab[t];
+        up = false;
+        unknown = false;
+        if (!(T.k <= K.enc && (K.ok || start + T.k <= S.avail))) continue;  // rc_probe does not probe either
+        const uint4 want = rc_exact_key(K.c, T.k);
+        uint32_t slot = rc_key_hash(want) & T.ct_mask;
+        unknown = true;
+        for (uint32_t p = 0; p < RC_PROBES; ++p, slot = (slot + 1) & T.ct_mask) {
+          const uint4* e = T.ct + 2 * (size_t)slot;
+          const uint4 val = e[1];
+          if (!(val.w & RC_OCC)) break;
+          if (!rc_same_key(e[0], want)) continue;
+          unknown = false;
+          const uint32_t nq = val.z & 0xFFFFu;
+          up = val.x != EMPTY && nq != 0u && nq + 1u <= P.rc_qcap;
+          break;
+        }
+      }
+    }
+  }
+  const unsigned long long ms = __ballot(sampled), mu = __ballot(unknown);
+  if (lane_id() == 0 && ms) atomicAdd(out, (unsigned long long)__popcll(mu) | ((unsigned long long)__popcll(ms) << 16));
 }
 
 // Dense start-level bitmaps (P.rc_dense). Most windows' start-level snapshot is final without
@@ -4946,8 +4998,11 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   uint64_t ct_mult = 4, ct_mult2 = 4;  // lookup slots per entry: levels 0/1 by entries, sampled levels by kept snapshots
   unsigned int* dense_w_host = nullptr;  // the dense bitmaps' sampled share of finished windows
   unsigned int* dense_w_dev = nullptr;
+  unsigned int* floor_w_host = nullptr;  // a full call's rc_store_sample_kernel counts (word 1 of the pinned line)
+  unsigned int* floor_w_dev = nullptr;
   uint32_t dense_pm = 0;
-  bool dense_list = false, dense_built = false;
+  bool dense_list = false;
+  const uint32_t* dense_buf = nullptr;  // the bitmaps the call built or took from the store (P.rc_dense may drop them)
   // after its build a level's entries are published into an exact-key lookup table (4 slots per
   // entry: a miss usually ends at the first probe)
   auto ct_slots = [&](uint32_t n_ent, uint64_t mult) {
@@ -4963,18 +5018,127 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
   };
   // (segments of < 1024 windows on average -- the pre-filter's merged windows -- share too few keys
   // for the cache's counts and builds: C5 212.7 vs 241.5 Gchars/s with it off, round 5 profiles/r05s)
-  if (!root_out && !e.has_map && fan_root + 1 <= 4096 && kVariants[vi].qcap <= 4096 &&
-      windows >= (rc_min ? std::strtoull(rc_min, nullptr, 10) : 4096ull) &&
-      (rc_min || windows >= rc_seg_windows * n_segs) && !diag_env("FAC_NO_RC")) {
-    auto env_u = [](const char* name, uint64_t dflt) {
-      const char* v = diag_env(name);
-      return v ? std::strtoull(v, nullptr, 10) : dflt;
-    };
-    const uint32_t kpin = kenv ? (uint32_t)std::min<unsigned long>(4, std::max<unsigned long>(2, std::strtoul(kenv, nullptr, 10))) : 0u;
-    const uint32_t qmain = kVariants[vi].qcap, vmain = kVariants[vi].vcap;
+  const bool rc_on = !root_out && !e.has_map && fan_root + 1 <= 4096 && kVariants[vi].qcap <= 4096 &&
+                     windows >= (rc_min ? std::strtoull(rc_min, nullptr, 10) : 4096ull) &&
+                     (rc_min || windows >= rc_seg_windows * n_segs) && !diag_env("FAC_NO_RC");
+  auto env_u = [](const char* name, uint64_t dflt) {
+    const char* v = diag_env(name);
+    return v ? std::strtoull(v, nullptr, 10) : dflt;
+  };
+  const uint32_t qmain = kVariants[vi].qcap, vmain = kVariants[vi].vcap;
+  // The engine's store is taken here, ahead of the counts: a call whose text the store already knows
+  // goes direct -- its lookups probe the store's directories, which hold what the
+  // per-call tables would (rc_publish_kernel's slots), and nothing is counted, selected, built or
+  // published. Any snapshot whose key is a prefix of a window resumes it exactly, so records do not
+  // depend on which keys are cached. FAC_RC_NO_CARRY=1 (A/B, tests), the auto-beam counting pass (its
+  // other dedup mode would empty the store before each main pass) and a store another call holds: no
+  // store, the pool from call scratch and every key built.
+  uint32_t sig[kRcSigWords] = {};
+  const uint64_t pool_limit = env_u("FAC_RC_POOL_WORDS", UINT64_MAX);  // (tests) fewer pool words than allocated
+  bool direct = false, rc_timed = false;
+  // the knobs that choose a call's levels (tests, A/B): a direct call takes the store's level set, so it
+  // needs a floor left under the same ones
+  uint64_t lv_knobs = 0xcbf29ce484222325ull;
+  for (const char* name : {"FAC_RC_K", "FAC_RC_K2", "FAC_RC_LEVELS", "FAC_RC_DEEPEST", "FAC_NO_RC_L0", "FAC_RC_L0K"}) {
+    const char* v = diag_env(name);
+    for (const char* c = v ? v : "\x01"; *c; ++c) lv_knobs = (lv_knobs ^ (uint8_t)*c) * 0x100000001b3ull;
+    lv_knobs = (lv_knobs ^ 0xFFu) * 0x100000001b3ull;
+  }
+  const char* direct_why = "off";  // FAC_RC_DEBUG: why the call did not go direct
+  int unknown_pm = -1;             // the sampled windows' unknown share (-1: not sampled)
+  if (rc_on) {
     qbuild = std::max<uint32_t>((uint32_t)fan_root + 1, qmain);
     P.rc_vmax = vmain ? std::min<uint32_t>(256, vmain / 2) : 256;
     P.rc_emax = 64;
+    std::memcpy(&sig[0], &P.thr, 4);
+    std::memcpy(&sig[1], &P.max_penalties, 4);
+    sig[2] = P.beam;
+    sig[3] = (uint32_t)P.exact_dedup | (uint32_t)P.beam_canonical << 1 | (uint32_t)P.gt_fast << 2 |
+             (uint32_t)P.dup_cut << 3 | (uint32_t)P.rc_full_sweep << 4 | (uint32_t)P.case_insensitive << 5 |
+             (uint32_t)P.window_skip << 6;
+    sig[4] = P.sel_limit;
+    sig[5] = P.rc_vmax;
+    sig[6] = P.rc_emax;
+    sig[7] = qbuild;
+    sig[8] = qmain;
+    sig[9] = vmain;
+  }
+  if (rc_on && !diag_env("FAC_RC_NO_CARRY") && !counts) {
+    RcStore& S = e.rc_store;
+    store.lk = std::unique_lock<std::mutex>(S.mu, std::try_to_lock);
+    store_reset = kRcBusy;
+    if (diag_env("FAC_RC_NO_DIRECT")) direct_why = "off";
+    else if (!store.lk.owns_lock() || rc_store_decide(S, sig, 0, pool_limit) != kRcKeep) direct_why = "reset";
+    else if (windows < env_u("FAC_RC_DIRECT_MIN", 1ull << 20)) direct_why = "min";
+    else if (S.floor_pm < 0 || S.lv_n == 0 || S.lv_knobs != lv_knobs) direct_why = "floor";
+    else {
+      // the store's level set as lookup tables, deepest first
+      SearchParams Q = P;
+      Q.rc_ntab = 0;
+      for (uint32_t t = 0; t < S.lv_n; ++t) {
+        const RcStoreDir& D = S.dir[S.lv_k[t]];
+        Q.rc_tab[Q.rc_ntab++] = RcTable{S.lv_k[t], 0u, nullptr, nullptr, nullptr, nullptr, D.slots, D.n_slots - 1};
+      }
+      Q.rc_kstart = S.kstart;
+      Q.rc_qcap = qmain;
+      Q.rc_pool = S.pool;
+      Q.rc_pool_cap = std::min(S.cap, pool_limit);
+      Q.rc_pool_used = S.dev;
+      // Dense bitmaps are built from a call's entries, which a direct call does not have: it takes the
+      // last full call's. Stale bitmaps are correct -- bit F (final without records) is exact and a
+      // property of the key, bit C is a hint (clear: the window goes to the shallower levels, whose
+      // snapshots resume it as exactly), and the ranks only choose which keys have an index.
+      Q.rc_dense = (S.has_dense && P.rc_lane_flush && !diag_env("FAC_RC_NO_DENSE")) ? S.dense : nullptr;
+      unsigned int* w_host = nullptr;
+      unsigned int* w_dev = nullptr;
+      if (int hrc = pinned_word(w_host, w_dev, err)) return hrc;
+      if (S.last) HIP_TRY(hipStreamWaitEvent(stream, S.last, 0));  // the previous user's last work
+      HIP_TRY(hipEventRecord(ev.a, stream));
+      rc_timed = true;
+      HIP_TRY(hipMemsetAsync(S.dev + 20, 0, sizeof(unsigned long long), stream));
+      hipLaunchKernelGGL(rc_store_sample_kernel, dim3(64), dim3(256), 0, stream, Q, windows, S.dev + 20);
+      hipLaunchKernelGGL(word_kernel, dim3(1), dim3(1), 0, stream, S.dev + 20, w_dev + 1);
+      if (Q.rc_dense) {  // the share of windows the bitmaps finish (the off / list decision below), in the same sync
+        HIP_TRY(hipMemsetAsync(S.dense + 34, 0, 2 * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(rc_dense_sample_kernel, dim3(64), dim3(256), 0, stream, Q, windows);
+        hipLaunchKernelGGL(word_kernel, dim3(1), dim3(1), 0, stream, reinterpret_cast<const unsigned long long*>(S.dense + 34), w_dev);
+      }
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(ev.b, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      const uint32_t w = *reinterpret_cast<volatile unsigned int*>(w_host + 1);
+      const uint32_t n_samp = w >> 16, n_unk = w & 0xFFFFu;
+      unknown_pm = n_samp ? (int)((uint64_t)n_unk * 1000 / n_samp) : 0;
+      direct = rc_direct_decide((uint32_t)unknown_pm, S.floor_pm, (uint32_t)env_u("FAC_RC_DIRECT_PM", kRcDirectPm), n_samp,
+                                windows, env_u("FAC_RC_DIRECT_MIN", 1ull << 20));
+      direct_why = direct ? "" : "share";
+      if (direct) {
+        // nothing is inserted: used, last_call, last_built and the directory counts stay, and the gate
+        // does not judge the call; the lease records the store's event like any user's
+        store.s = &S;
+        store.st = stream;
+        store.finished = true;
+        store_reset = kRcKeep;
+        P = Q;
+        P.rc_mode = 1;
+        dense_w_host = w_host;
+        dense_buf = P.rc_dense;
+        HIP_TRY(hipEventElapsedTime(&cache_ms, ev.a, ev.b));
+        if (diag_env("FAC_RC_DEBUG")) {  // a direct call has no levels of its own: no k= carried= built= items
+          uint64_t keys = 0, dslots = 0;
+          for (int k = 0; k < 9; ++k) keys += S.dir[k].count, dslots += S.dir[k].n_slots;
+          std::string lv;
+          for (uint32_t t = 0; t < P.rc_ntab; ++t) lv += (t ? "," : "") + std::to_string(P.rc_tab[t].k);
+          std::fprintf(stderr, "FAC_RC windows=%llu levels=%s | carry direct=1 unknown_pm=%d floor_pm=%d | store pool_words=%llu "
+                       "dir_keys=%llu dir_slots=%llu reset=%s\n", (unsigned long long)windows, lv.c_str(), unknown_pm,
+                       (int)S.floor_pm, (unsigned long long)S.used, (unsigned long long)keys, (unsigned long long)dslots,
+                       rc_reset_name(store_reset));
+        }
+      }
+    }
+  }
+  if (rc_on && !direct) {
+    const uint32_t kpin = kenv ? (uint32_t)std::min<unsigned long>(4, std::max<unsigned long>(2, std::strtoul(kenv, nullptr, 10))) : 0u;
     // entries per level: fresh-word C3 selects more than 16 M 5-char keys (32 M: 448.7 -> 445.8 ms per
     // step, the vocabulary C3 unchanged, profiles/r04t)
     const uint64_t ent_cap = std::max<uint64_t>(1, env_u("FAC_RC_ENTRIES", 32ull << 20));
@@ -4994,7 +5158,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     L1 = RcTable{0u, slots - 1, static_cast<const unsigned long long*>(d_rck.p), static_cast<const uint32_t*>(d_rcv.p),
                  static_cast<uint32_t*>(d_rcc.p) + max_ent, static_cast<uint32_t*>(d_rcc.p)};
     P.rc_pool_used = static_cast<unsigned long long*>(d_rcn.p) + 1;
-    HIP_TRY(hipEventRecord(ev.a, stream));
+    if (!rc_timed) HIP_TRY(hipEventRecord(ev.a, stream));  // (a call that sampled the store and stayed full: from the sample on)
     HIP_TRY(hipMemsetAsync(d_rcn.p, 0, 4 * sizeof(unsigned long long), stream));
     const uint32_t cgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((windows + 255) / 256, (uint64_t)cus * env_u("FAC_RC_CGRID", 8)));
 
@@ -5249,42 +5413,28 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       P.rc_pool_chunk = (uint32_t)std::max<uint64_t>(worst, std::min<uint64_t>(RC_POOL_CHUNK, n_all * 40 / (4 * grids)));
       const uint64_t pool_words = std::max<uint64_t>(1024, std::min<uint64_t>(n_all * worst, budget / sizeof(uint4))) +
                                   grids * P.rc_pool_chunk;
-      // The pool: the engine's store, with the snapshots of earlier calls, unless FAC_RC_NO_CARRY=1 (A/B,
-      // tests) or another call holds it; then call scratch, every key built, as before the store.
-      // (not for the auto-beam counting pass: its other dedup mode would empty the store before each main pass)
-      if (!diag_env("FAC_RC_NO_CARRY") && !counts) {
+      // The pool: the engine's store (locked above), with the snapshots of earlier calls; without it
+      // call scratch, every key built, as before the store.
+      if (store.lk.owns_lock()) {
         RcStore& S = e.rc_store;
-        store.lk = std::unique_lock<std::mutex>(S.mu, std::try_to_lock);
-        store_reset = kRcBusy;
-        if (store.lk.owns_lock()) {
-          uint32_t sig[kRcSigWords] = {};
-          std::memcpy(&sig[0], &P.thr, 4);
-          std::memcpy(&sig[1], &P.max_penalties, 4);
-          sig[2] = P.beam;
-          sig[3] = (uint32_t)P.exact_dedup | (uint32_t)P.beam_canonical << 1 | (uint32_t)P.gt_fast << 2 |
-                   (uint32_t)P.dup_cut << 3 | (uint32_t)P.rc_full_sweep << 4 | (uint32_t)P.case_insensitive << 5 |
-                   (uint32_t)P.window_skip << 6;
-          sig[4] = P.sel_limit;
-          sig[5] = P.rc_vmax;
-          sig[6] = P.rc_emax;
-          sig[7] = qbuild;
-          sig[8] = qmain;
-          sig[9] = vmain;
-          // FAC_RC_POOL_WORDS (tests): fewer pool words than allocated, so a small case can fill the pool
-          const uint64_t limit = env_u("FAC_RC_POOL_WORDS", UINT64_MAX);
-          store_reset = rc_store_decide(S, sig, pool_words, limit);
-          if (store_reset == kRcGated) {  // unlike text: this call goes without the store
-            --S.sleep;
-            store.lk.unlock();
-          } else {
-            if (S.last) HIP_TRY(hipStreamWaitEvent(stream, S.last, 0));  // the previous user's last work
-            store.s = &S;
-            store.st = stream;
-            if (int prc = rc_store_prepare(S, store_reset, sig, pool_words, stream, err)) return prc;
-            P.rc_pool = S.pool;
-            P.rc_pool_cap = std::min(S.cap, limit);
-            P.rc_pool_used = S.dev;
-          }
+        store_reset = rc_store_decide(S, sig, pool_words, pool_limit);
+        // text that fills the store in every call: like unlike text, some calls go without it
+        if (const uint32_t g = rc_store_emptied_gate(store_reset, S.filled, S.backoff)) {
+          S.backoff = S.sleep = g;
+          S.valid = false;  // empty when the store is used again
+          store_reset = kRcGated;
+        }
+        if (store_reset == kRcGated) {  // unlike text: this call goes without the store
+          --S.sleep;
+          store.lk.unlock();
+        } else {
+          if (S.last) HIP_TRY(hipStreamWaitEvent(stream, S.last, 0));  // the previous user's last work
+          store.s = &S;
+          store.st = stream;
+          if (int prc = rc_store_prepare(S, store_reset, sig, pool_words, stream, err)) return prc;
+          P.rc_pool = S.pool;
+          P.rc_pool_cap = std::min(S.cap, pool_limit);
+          P.rc_pool_used = S.dev;
         }
       }
       if (!store.s) {
@@ -5347,8 +5497,14 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     // the sampled levels' counts run beside the level-0/1 builds and have slack until the level-1
     // build ends: fewer workgroups leave the builds more of the CUs. Measured: two sampled levels
     // (C3) 2 per CU (-2 ms against 8), one level (C2, whose builds are shorter) 4 per CU (-2 ms)
+    // With the store the level-0/1 builds take about 1 ms once the short keys are known, and the count
+    // (a latency-bound random-access kernel, 10.7 ms at 2 per CU) is the critical path: 4 per CU when
+    // the previous call built under an eighth of this call's level-1 entries (C3, different haystacks:
+    // -2.3 ms per carrying call, 8 per CU -1.8 ms). A call that starts the store empty
+    // builds every key and keeps 2.
+    const bool l1_known = store.s && store_reset == kRcKeep && 8 * store.s->last_built[L1.k] <= n_ent1;
     const uint32_t cgrid2 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((windows + 255) / 256,
-        (uint64_t)cus * env_u("FAC_RC_CGRID2", ks.size() >= 2 ? 2 : 4)));
+        (uint64_t)cus * env_u("FAC_RC_CGRID2", ks.size() >= 2 && !l1_known ? 2 : 4)));
     // (beamed engines: keys seen >= 4 times while the selects were inlined into the window loop and
     // the builds spilled registers; >= 2 since: C3 162.0 -> 151.8 ms, profiles/r03/sweep_levels.txt)
     // (keys seen >= 3 times measured slower once the small build variant made the builds cheaper:
@@ -5424,9 +5580,14 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
                            kept, ct_mult2))) return brc;
         // the first sampled level is where the main lookups start (P.rc_kstart = level 1's k + 1)
         if (x == 0 && P.rc_kstart == L1.k + 1 && !P.win_counts && P.rc_lane_flush && !diag_env("FAC_RC_NO_DENSE")) {
-          HIP_TRY(d_dense.alloc(RC_DENSE_WORDS * sizeof(uint32_t), stream));
-          HIP_TRY(hipMemsetAsync(d_dense.p, 0, RC_DENSE_WORDS * sizeof(uint32_t), stream));
-          uint32_t* dn = static_cast<uint32_t*>(d_dense.p);
+          // (with the store: built in the store's buffer, where direct calls find them)
+          if (store.s) {
+            if (int drc = rc_store_dense(*store.s, RC_DENSE_WORDS, err)) return drc;
+          } else {
+            HIP_TRY(d_dense.alloc(RC_DENSE_WORDS * sizeof(uint32_t), stream));
+          }
+          uint32_t* dn = store.s ? store.s->dense : static_cast<uint32_t*>(d_dense.p);
+          HIP_TRY(hipMemsetAsync(dn, 0, RC_DENSE_WORDS * sizeof(uint32_t), stream));
           const uint64_t* reps = static_cast<const uint64_t*>(d_xrep[xbuf[x]].p);
           const dim3 dg(std::max<uint32_t>(1, std::min<uint32_t>((n_entx[x] + 255) / 256, cus * 4)));
           hipLaunchKernelGGL(rc_dense_hist_kernel, dg, dim3(256), 0, stream, P, reps, static_cast<const uint4*>(P.rc_pool),
@@ -5442,7 +5603,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
                                static_cast<const uint4*>(P.rc_pool), L1.off, L1.count, n_ent1, L1.k, dn, RC_DENSE_F4, 0u);
           HIP_TRY(hipGetLastError());
           P.rc_dense = dn;
-          dense_built = true;
+          dense_buf = dn;
         }
         tabs.push_back(Lx[x]);
       }
@@ -5458,6 +5619,28 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       P.rc_ntab = 0;
       for (size_t t = tabs.size(); t-- > 0;) P.rc_tab[P.rc_ntab++] = tabs[t];
       P.rc_mode = 1;
+      // The floor for direct calls: the unknown share this call leaves on its own text, now that its
+      // keys are inserted (keys seen once are never selected, so it is not zero), from the same sample
+      // over the directories of its levels. Read after the sync below.
+      if (store.s) {
+        RcStore& S = *store.s;
+        SearchParams Q = P;
+        bool dirs = true;
+        for (uint32_t t = 0; t < Q.rc_ntab; ++t) {
+          const RcStoreDir& D = S.dir[Q.rc_tab[t].k];
+          dirs = dirs && D.n_slots != 0;
+          Q.rc_tab[t].ct = D.slots;
+          Q.rc_tab[t].ct_mask = D.n_slots - 1;
+        }
+        Q.rc_qcap = qmain;
+        if (dirs) {
+          if (int hrc = pinned_word(floor_w_host, floor_w_dev, err)) return hrc;
+          HIP_TRY(hipMemsetAsync(S.dev + 20, 0, sizeof(unsigned long long), stream));
+          hipLaunchKernelGGL(rc_store_sample_kernel, dim3(64), dim3(256), 0, stream, Q, windows, S.dev + 20);
+          hipLaunchKernelGGL(word_kernel, dim3(1), dim3(1), 0, stream, S.dev + 20, floor_w_dev + 1);
+          HIP_TRY(hipGetLastError());
+        }
+      }
     }
     HIP_TRY(hipEventRecord(ev.b, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -5466,16 +5649,19 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       // FAC_RC_GATE_MIN (tests): the fewest entries of a call the gate for unlike text judges
       if (int frc = rc_store_finish(*store.s, P.rc_pool_cap, store_reset == kRcKeep, env_u("FAC_RC_GATE_MIN", 1ull << 16), err))
         return frc;
+      // what a direct call needs of this one: its levels, where its lookups start, its bitmaps, its floor
+      RcStore& S = *store.s;
+      S.lv_n = 0;
+      S.floor_pm = -1;
+      S.has_dense = dense_buf != nullptr;
+      S.kstart = P.rc_kstart;
+      S.lv_knobs = lv_knobs;
+      if (floor_w_host && S.valid) {
+        for (uint32_t t = 0; t < P.rc_ntab; ++t) S.lv_k[S.lv_n++] = P.rc_tab[t].k;
+        const uint32_t w = *reinterpret_cast<volatile unsigned int*>(floor_w_host + 1);
+        if (w >> 16) S.floor_pm = (int32_t)((uint64_t)(w & 0xFFFFu) * 1000 / (w >> 16));
+      }
       store.finished = true;
-    }
-    if (P.rc_dense) {
-      // F-done windows among 16384 sampled: below FAC_RC_DENSE_OFF per mille the bitmaps are dropped
-      // (their test costs the lookup more than it saves), from FAC_RC_DENSE_LIST per mille the lookups
-      // walk the list of the others (dl_*_kernel)
-      dense_pm = (uint32_t)((uint64_t)*reinterpret_cast<volatile unsigned int*>(dense_w_host) * 1000 / 16384);
-      const uint32_t off_pm = (uint32_t)env_u("FAC_RC_DENSE_OFF", 50), list_pm = (uint32_t)env_u("FAC_RC_DENSE_LIST", 250);
-      if (dense_pm < off_pm) P.rc_dense = nullptr;
-      dense_list = dense_pm >= list_pm;
     }
     if (P.rc_mode == 1 && diag_env("FAC_RC_DEBUG")) {  // diagnostics: keys, pool use, cached entries
       unsigned long long rcn[2] = {0, 0};
@@ -5515,6 +5701,10 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
       // the store's pool words, its directories' keys over their slots, and why the call started it empty
       std::string cs = " | carry";
       {
+        char d[96];  // the direct decision: the share sampled (-1: not sampled), the floor this call leaves, the reason
+        std::snprintf(d, sizeof(d), " direct=0 unknown_pm=%d floor_pm=%d why=%s", unknown_pm,
+                      store.s ? (int)store.s->floor_pm : -1, direct_why);
+        cs += d;
         auto level = [&](uint32_t k, uint32_t ne) {
           const uint64_t got = store.s ? std::min<uint64_t>(ne, store.s->carried[k]) : 0;
           char b[96];
@@ -5540,6 +5730,15 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
                    (unsigned long long)c1, (unsigned long long)f1, (unsigned long long)(c1 - f1),
                    c1 ? (double)q1 / c1 : 0.0, lv.c_str(), rcn[1] * 16.0 / 1e6);
     }
+  }
+  if (P.rc_dense) {
+    // F-done windows among 16384 sampled: below FAC_RC_DENSE_OFF per mille the bitmaps are dropped
+    // (their test costs the lookup more than it saves), from FAC_RC_DENSE_LIST per mille the lookups
+    // walk the list of the others (dl_*_kernel)
+    dense_pm = (uint32_t)((uint64_t)*reinterpret_cast<volatile unsigned int*>(dense_w_host) * 1000 / 16384);
+    const uint32_t off_pm = (uint32_t)env_u("FAC_RC_DENSE_OFF", 50), list_pm = (uint32_t)env_u("FAC_RC_DENSE_LIST", 250);
+    if (dense_pm < off_pm) P.rc_dense = nullptr;
+    dense_list = dense_pm >= list_pm;
   }
   const double t_cache = host_ms();
   double t_dev = 0.0;
@@ -5679,7 +5878,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
           lv += b;
         }
         uint32_t dk[2] = {0, 0};  // the start level's cached keys: ASCII and final without records, all
-        if (dense_built) HIP_TRY(hipMemcpy(dk, static_cast<uint32_t*>(d_dense.p) + 36, sizeof(dk), hipMemcpyDeviceToHost));
+        if (dense_buf) HIP_TRY(hipMemcpy(dk, dense_buf + 36, sizeof(dk), hipMemcpyDeviceToHost));
         std::fprintf(stderr, "FAC_LK%s miss %llu skipped %llu dense-final %llu unlisted %llu (sampled %u per mille; keys %u of %u)\n",
                      lv.c_str(), d[12], d[13], d[14], (unsigned long long)dense_done, dense_pm, dk[0], dk[1]);
         std::memset(d, 0, sizeof(d));

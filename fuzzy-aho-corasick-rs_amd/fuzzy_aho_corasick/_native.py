@@ -160,6 +160,9 @@ SIGNATURES = {
                                                 ctypes.c_int32, ctypes.c_uint32]),
     "fac_diag_rc_reset_name": (ctypes.c_char_p, [ctypes.c_int32]),
     "fac_diag_rc_store_gate": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64]),
+    "fac_diag_rc_emptied_gate": (ctypes.c_uint32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32]),
+    "fac_diag_rc_direct_decide": (ctypes.c_int32, [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64,
+                                                   ctypes.c_uint64, ctypes.c_uint64]),
     "fac_trim_scratch": (None, []),
     "fac_search_raw": (ctypes.c_int, [_engine_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_float,
                                       _P(_P(fac_match)), _u64p, _u64p]),

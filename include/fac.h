@@ -899,6 +899,16 @@ const char* fac_diag_rc_reset_name(int32_t reset);
  * carrying call that found `carried` of its carried + built entries: 0 from a tenth on or below gate_min
  * entries, else twice `backoff` (1 at first, at most 64). */
 uint32_t fac_diag_rc_store_gate(uint64_t carried, uint64_t built, uint32_t backoff, uint64_t gate_min);
+/* The gate for a store that every call empties (fresh-word text fills the pool in one call): the calls
+ * that go without the store, the deciding one included, when `decision` (fac_diag_rc_store_decide) is
+ * 3 pool or 4 directory right after the call that filled the store from empty (after_fill != 0): twice
+ * `backoff` (1 at first, at most 64); 0: the rule does not apply. */
+uint32_t fac_diag_rc_emptied_gate(int32_t decision, int32_t after_fill, uint32_t backoff);
+/* Whether a call searches from the store's directories alone: unknown_pm per mille of its `sampled`
+ * windows ended on a key no directory holds; floor_pm: the share the last full call left (< 0: none);
+ * 1 when unknown_pm <= floor_pm + margin_pm, sampled > 0 and windows >= min_windows. */
+int32_t fac_diag_rc_direct_decide(uint32_t unknown_pm, int32_t floor_pm, uint32_t margin_pm, uint64_t sampled,
+                                  uint64_t windows, uint64_t min_windows);
 
 /* Diagnostics (tests): the expanded text of a stream task alone. Window w is bytes
  * [windows[2w], windows[2w] + windows[2w + 1]) of the len bytes at utf8 (ranges may overlap); the
