@@ -1351,6 +1351,21 @@ int fac_batch_require_boundaries(fac_batch* batch, int32_t sides) {
   return FAC_OK;
 }
 
+int fac_batch_require_anchors(fac_batch* batch, int32_t sides) {
+  if (!batch) return fail(FAC_E_INVALID, "NULL argument");
+  if (sides < 0 || sides > FAC_ANCHOR_WHOLE) return fail(FAC_E_INVALID, "sides must be 0..3");
+  batch->b.anchors = sides;
+  return FAC_OK;
+}
+
+int32_t fac_anchor_ok(uint64_t doc_len, uint64_t start, uint64_t end, int32_t sides) {
+  if (sides < 0 || sides > FAC_ANCHOR_WHOLE) return -(int32_t)fail(FAC_E_INVALID, "sides must be 0..3");
+  if (start > end || end > doc_len) return -(int32_t)fail(FAC_E_INVALID, "span outside the document");
+  if ((sides & FAC_ANCHOR_START) && start != 0) return 0;
+  if ((sides & FAC_ANCHOR_END) && end != doc_len) return 0;
+  return 1;
+}
+
 int32_t fac_boundary_class(uint32_t cp) { return (int32_t)fac::boundary_class(cp); }
 
 int32_t fac_boundary_ok(const uint8_t* utf8, uint64_t len, uint64_t start, uint64_t end, int32_t sides) {
@@ -1442,16 +1457,27 @@ struct BatchKept {
 };
 
 // d_doc_user: where the index goes instead of the call's own scratch (may be NULL); searched
-// (optional): += the start windows handed to the search launcher
+// (optional): += the start windows handed to the search launcher; anchors: the FAC_ANCHOR_* mask of
+// the call (-1: the batch's own, fac_batch_require_anchors)
 static int batch_kept(const fac::Engine& e, const fac::Batch& b, float threshold, int order, int overlap,
                       const uint64_t* unique_ids, bool prefilter, hipStream_t st, uint64_t* d_doc_user, fac_stats* stats,
-                      BatchKept& k, std::string& err, uint64_t* searched = nullptr, const fac::StreamFilter* sf = nullptr) {
+                      BatchKept& k, std::string& err, uint64_t* searched = nullptr, const fac::StreamFilter* sf = nullptr,
+                      int anchors = -1) {
   const uint64_t nd = b.n_docs;
+  if (anchors < 0) anchors = b.anchors;
   fac::BatchWindows pw;  // pre-filtered: every document's merged windows, found once
   bool filtered = false;
   if (int rc = batch_prefilter(e, b, threshold, prefilter, st, pw, filtered, stats, err)) return rc;
+  // anchored matches (fac.h fac_batch_require_anchors): a plain call searches only the start windows
+  // a kept record can come from, through descriptors of its own (the batch's stay as they are). An
+  // auto-beam-only engine's running total needs every window in order, and a pre-filtered call keeps
+  // its merged windows: both get the filter below and nothing else.
+  if (anchors && !prefilter && !(e.has_auto_beam && e.beam_width == 0) && b.n_segs) {
+    if (int rc = fac::anchor_windows_device(e, b, anchors, st, pw, err)) return rc;
+    filtered = true;
+  }
   if (searched) *searched += filtered ? pw.windows : b.windows;
-  uint64_t cap = std::max<uint64_t>(4096, (filtered ? pw.windows : b.windows) / 64);
+  uint64_t cap = std::max<uint64_t>({4096, (filtered ? pw.windows : b.windows) / 64, filtered ? pw.out_hint : 0});
   for (;;) {
     if (int rc = k.raw.alloc(2 * cap * sizeof(fac_match), err)) return rc;
     if (int rc = k.doff.alloc((nd + 1) * 8, err)) return rc;
@@ -1483,6 +1509,15 @@ static int batch_kept(const fac::Engine& e, const fac::Batch& b, float threshold
       // context (a document's start is no boundary there)
       if (int rc = fac::stream_boundary_filter_device(b.h.device, *sf, recs, n, other,
                                                       static_cast<unsigned long long*>(k.doff.p), st, &n, err))
+        return rc;
+      std::swap(recs, other);
+    }
+    if (anchors && n) {
+      // the anchor rule on the complete raw set, at the same point and in the same way (a pure
+      // predicate like the whole-token rule, so the order of the two passes does not matter); for a
+      // narrowed START search it only drops what window 0 found away from byte 0
+      if (int rc = fac::anchor_filter_device(b, anchors, recs, n, other, static_cast<unsigned long long*>(k.doff.p), st, &n,
+                                             err))
         return rc;
       std::swap(recs, other);
     }
@@ -1548,6 +1583,57 @@ int fac_search_batch(const fac_engine* engine, const fac_batch* batch, const fac
 int fac_search_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_batch_args* args,
                                  fac_match** out, uint64_t* n_out, uint64_t* doc_offsets, fac_stats* stats) {
   return search_batch_impl(engine, batch, args, out, n_out, doc_offsets, stats, true);
+}
+
+// fac.h "Dictionary lookup of a batch": fac_search_batch's search with the WHOLE anchor and
+// apply(order, Keep), then the dense table from the kept records in HBM
+int fac_lookup_batch(const fac_engine* engine, const fac_batch* batch, const fac_lookup_args* args, fac_match** out,
+                     uint32_t* found, fac_stats* stats) {
+  if (!args) return fail(FAC_E_INVALID, "NULL argument");
+  if (args->k == 0) return fail(FAC_E_INVALID, "k must be at least 1");
+  if (args->order < 0 || args->order > 3) return fail(FAC_E_INVALID, "bad order");
+  if (!engine || !batch || (!out && !args->device_out)) return fail(FAC_E_INVALID, "NULL argument");
+  if (out) *out = nullptr;
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
+  if (e.has_map && !b.h.ascii && !b.unicode_map)
+    return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
+  const uint64_t nd = b.n_docs, total = nd * (uint64_t)args->k;  // (nd <= 2^24, k < 2^32: no overflow)
+  if (total >= (1ull << fac::kDocTagShift)) return fail(FAC_E_UNSUPPORTED, "a lookup table holds fewer than 2^40 records");
+  if (args->device_out && args->device_cap < total)
+    return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (n_docs * k records needed)");
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
+  const int order = args->order == 0 ? 1 : args->order;
+  std::string err;
+  BatchKept k(st);
+  if (int rc = batch_kept(e, b, args->threshold, order, /*Keep*/ 0, nullptr, false, st, nullptr, stats, k, err, nullptr, nullptr,
+                          FAC_ANCHOR_WHOLE))
+    return fail(rc, err);
+  DevMem tab(st), fnd(st);
+  if (int rc = fnd.alloc(std::max<uint64_t>(nd, 1) * sizeof(uint32_t), err)) return fail(rc, err);
+  fac_match* d_tab = static_cast<fac_match*>(args->device_out);
+  if (!d_tab) {
+    if (int rc = tab.alloc(std::max<uint64_t>(total, 1) * sizeof(fac_match), err)) return fail(rc, err);
+    d_tab = static_cast<fac_match*>(tab.p);
+  }
+  if (int rc = fac::lookup_table_device(k.res, k.d_doc, nd, args->k, d_tab, static_cast<uint32_t*>(fnd.p), st, err))
+    return fail(rc, err);
+  fac::MatchSink fin;  // the host form: a pinned buffer handed out as *out
+  if (!args->device_out)
+    if (int rc = fac::sink_append_device(fin, d_tab, total, st, err)) {
+      fac::result_free(fin.pinned);
+      return fail(rc, err);
+    }
+  if ((found && nd && hipMemcpyAsync(found, fnd.p, nd * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    fac::result_free(fin.pinned);
+    return fail(FAC_E_HIP, "copy of the lookup table failed");
+  }
+  if (args->device_out) return FAC_OK;
+  uint64_t n_out = 0;
+  return hand_out(fin, out, &n_out);
 }
 
 int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* batch, float threshold, void* stream,

@@ -627,6 +627,10 @@ struct Batch {
   // boundaries of its document for the record to reach the apply; 0 = off. Kept across a restage
   // like the opt-ins above. The window batches of stream.cpp never set it.
   int boundaries = 0;
+  // fac_batch_require_anchors: the sides (FAC_ANCHOR_*) at which every raw record must touch its
+  // document's ends to reach the apply; 0 = off. Kept across a restage like the boundary mask and
+  // independent of it. The window batches of stream.cpp never set it.
+  int anchors = 0;
   // stream_windows_docs: the documents are long (256 KiB windows), so stage_batch_device segments
   // the non-ASCII ones by chunks of the text (batch_seg_chunk_kernel) instead of one thread each.
   // The staged batch is the same either way.
@@ -659,6 +663,16 @@ int apply_batch_device(const Engine& e, fac_match* d_a, fac_match* d_b, uint64_t
 // of device scratch. Reads b.h.d_utf8 inside the record's document only; synchronises once.
 int boundary_filter_device(const Batch& b, int sides, const fac_match* d_in, uint64_t n, fac_match* d_out,
                            unsigned long long* d_count, hipStream_t s, uint64_t* n_kept, std::string& err);
+// anchor_kernels.hip (fac.h "Anchored matches"). anchor_filter_device: boundary_filter_device's contract
+// with the anchor rule (start == the document's first byte for FAC_ANCHOR_START, end == its end for
+// FAC_ANCHOR_END); it reads b.d_offsets and never the text. lookup_table_device: row d of the
+// n_docs x k table at d_table takes the first min(k, m_d) of document d's applied records (d_recs
+// with the CSR index d_doc_off), the other slots the filler (pattern_index = FAC_UNMATCHED, all else
+// 0); d_found[d] = min(k, m_d). Asynchronous on s.
+int anchor_filter_device(const Batch& b, int sides, const fac_match* d_in, uint64_t n, fac_match* d_out,
+                         unsigned long long* d_count, hipStream_t s, uint64_t* n_kept, std::string& err);
+int lookup_table_device(const fac_match* d_recs, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t k, fac_match* d_table,
+                        uint32_t* d_found, hipStream_t s, std::string& err);
 // The whole-token mask of a stream task (fac.h fac_stream_open_opts) and the stream's text before
 // the task's first byte: the last before_len (<= kBoundaryCarry) bytes of it, on the host;
 // more_before: the stream has text before those.
@@ -927,6 +941,10 @@ struct BatchWindows {
   uint64_t* d_prefix = nullptr;  // n + 1 entries
   uint64_t n = 0;        // merged windows of all documents
   uint64_t windows = 0;  // their lengths summed: the start windows to search
+  // records the search is expected to return, where the caller knows better than the launcher's
+  // windows / 64 (anchored windows: one window per document, a record or more each); 0 = no hint.
+  // A first buffer too small costs a second search, never a record.
+  uint64_t out_hint = 0;
   // want_tri (a batch with non-ASCII documents, fac_batch_prefilter_windows): d_tri receives per
   // window {document, start, end} in document-relative symbols (bytes of an ASCII document,
   // graphemes of any other), which the descriptor of a slice no longer tells
@@ -942,6 +960,12 @@ int batch_prefilter_windows(const Engine& e, const Batch& b, const std::vector<u
                             BatchWindows& out, fac_stats* stats, std::string& err);
 int launch_search_batch_windows(const Engine& e, const Batch& b, const BatchWindows& w, float thr, hipStream_t stream,
                                 MatchSink& sink, fac_stats* stats, std::string& err);
+// anchor_kernels.hip: the batch's own descriptors (Batch::d_segs, untouched) copied with the window
+// range narrowed to the start windows an anchored record can come from: [0, 1) when `sides` holds
+// FAC_ANCHOR_START, the last min(n, max_match_graphemes + 2) for FAC_ANCHOR_END alone. n, hay_len,
+// avail, text_base and the tagged byte_base stay the document's. One segment per non-empty document,
+// never empty; synchronises once (the window total).
+int anchor_windows_device(const Engine& e, const Batch& b, int sides, hipStream_t st, BatchWindows& out, std::string& err);
 // auto-beam pass 1 alone: sum of queue.len() over the windows of `segs` searched unbeamed
 int auto_beam_total(const Engine& e, const Haystack& h, const std::vector<SegDesc>& segs, float thr,
                     hipStream_t stream, uint64_t& total, std::string& err);

@@ -4777,6 +4777,7 @@ struct DevSegs {
   uint32_t n;
   uint64_t windows;
   uint64_t rc_seg_windows;
+  uint64_t out_cap0 = 0;  // records the caller expects (BatchWindows::out_hint); 0: windows / 64 as for everyone
 };
 int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& segs_in, float thr,
                 hipStream_t stream, uint32_t beam, bool exact_dedup, std::vector<uint32_t>* counts,
@@ -4870,7 +4871,7 @@ int launch_pass(const Engine& e, const Haystack& h, const std::vector<SegDesc>& 
     HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d_prefix.p, prefix.data(), prefix.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
   }
-  uint64_t out_cap = std::max<uint64_t>(4096, windows / 64);
+  uint64_t out_cap = std::max<uint64_t>({4096, windows / 64, dsegs ? dsegs->out_cap0 : 0});
   // beamed passes spill every window whose pending count passes 2 bw from the dedup-free first pass
   // (C3: ~5 % of its windows): a list too short re-runs the whole pass
   uint64_t spill_cap = std::max<uint64_t>(4096, windows / (P.beam ? 8 : 32));
@@ -6200,7 +6201,7 @@ int launch_search_batch_windows(const Engine& e, const Batch& b, const BatchWind
   }
   uint64_t seg_windows = kBatchRcSegWindows;  // the batch's prefix-cache rule, as launch_search_batch
   if (const char* v = diag_env("FAC_BATCH_RC_SEG")) seg_windows = std::strtoull(v, nullptr, 10);
-  const DevSegs ds{w.d_segs, w.d_prefix, (uint32_t)w.n, w.windows, seg_windows};
+  const DevSegs ds{w.d_segs, w.d_prefix, (uint32_t)w.n, w.windows, seg_windows, w.out_hint};
   const uint32_t beam = (uint32_t)std::min<uint64_t>(e.beam_width, 0xFFFFFFFFull);
   return launch_pass(e, b.h, {}, thr, stream, beam, beam != 0, nullptr, sink, stats, err, &ds);
 }

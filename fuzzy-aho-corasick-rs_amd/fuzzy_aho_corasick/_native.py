@@ -95,6 +95,11 @@ class fac_batch_args(ctypes.Structure):
                 ("device_doc_offsets", ctypes.c_void_p)]
 
 
+class fac_lookup_args(ctypes.Structure):
+    _fields_ = [("threshold", ctypes.c_float), ("order", ctypes.c_int32), ("k", ctypes.c_uint32),
+                ("stream", ctypes.c_void_p), ("device_out", ctypes.c_void_p), ("device_cap", ctypes.c_uint64)]
+
+
 class fac_replace_args(ctypes.Structure):
     _fields_ = [("threshold", ctypes.c_float), ("order", ctypes.c_int32), ("overlap", ctypes.c_int32),
                 ("unique_ids", ctypes.POINTER(ctypes.c_uint64)), ("stream", ctypes.c_void_p),
@@ -126,6 +131,9 @@ FAC_RENDER_SEGMENT_TEXT = 2
 FAC_BOUNDARY_START = 1  # sides of fac_batch_require_boundaries / fac_boundary_ok
 FAC_BOUNDARY_END = 2
 FAC_BOUNDARY_WHOLE = 3
+FAC_ANCHOR_START = 1  # sides of fac_batch_require_anchors / fac_anchor_ok
+FAC_ANCHOR_END = 2
+FAC_ANCHOR_WHOLE = 3
 
 assert ctypes.sizeof(fac_match) == 32
 
@@ -258,6 +266,10 @@ SIGNATURES = {
     "fac_batch_allow_unicode_prefilter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "fac_batch_allow_unicode_mappings": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "fac_batch_require_boundaries": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "fac_batch_require_anchors": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "fac_anchor_ok": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32]),
+    "fac_lookup_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_lookup_args), _P(_P(fac_match)),
+                                        _P(ctypes.c_uint32), _P(fac_stats)]),
     "fac_boundary_class": (ctypes.c_int32, [ctypes.c_uint32]),
     "fac_boundary_ok": (ctypes.c_int32, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_int32]),

@@ -12,7 +12,7 @@ from . import _native
 
 _TIMING = bool(os.environ.get("FAC_TIMING"))  # diagnostics: host-side phase times
 from .matches import FuzzyMatch, FuzzyMatches, Segment, UnmatchedSegment
-from .structs import (Boundary, DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge, Order, Overlap,
+from .structs import (Anchor, Boundary, DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge, Order, Overlap,
                       Pattern, SearchError, SearchOptions, Similarity, UnsupportedConfiguration, f32)
 
 
@@ -355,22 +355,25 @@ class FuzzyAhoCorasick:
         return self._to_matches(matches.haystack, matches.haystack.encode("utf-8"), rows)
 
     # -- query.rs
-    def search(self, haystack: str, opts: SearchOptions = None, boundaries: Boundary = Boundary.NONE) -> FuzzyMatches:
+    def search(self, haystack: str, opts: SearchOptions = None, boundaries: Boundary = Boundary.NONE,
+               anchors: Anchor = Anchor.NONE) -> FuzzyMatches:
         """`boundaries` (non-zero): only matches whose named sides are word boundaries take part in
         ranking and overlap resolution (DESIGN.md 6a "Whole-token matches"); the haystack then runs
-        as a one-document batch, where that filter is on the device."""
+        as a one-document batch, where that filter is on the device. `anchors` (non-zero): only
+        matches that touch the named ends of the haystack do (DESIGN.md 6a "Anchored matches"), by
+        the same route."""
         opts = opts or SearchOptions()
-        if int(boundaries):
-            return self.search_batch([haystack], opts, unicode_mappings=True, boundaries=boundaries)[0]
+        if int(boundaries) or int(anchors):
+            return self.search_batch([haystack], opts, unicode_mappings=True, boundaries=boundaries, anchors=anchors)[0]
         return self._search_ranked(haystack, opts.threshold_, opts.order_, opts.overlap_)
 
     def _search_bounded(self, haystack: str, threshold: float, order: Order, overlap: Overlap, prefilter: bool,
-                        boundaries) -> FuzzyMatches:
-        """One haystack on the host route: search_raw, FuzzyMatches.retain_boundaries, then apply (the
-        per-document form the batch conveniences fall back to)."""
-        if not int(boundaries):
+                        boundaries, anchors=Anchor.NONE) -> FuzzyMatches:
+        """One haystack on the host route: search_raw, FuzzyMatches.retain_boundaries and
+        retain_anchors, then apply (the per-document form the batch conveniences fall back to)."""
+        if not int(boundaries) and not int(anchors):
             return self._search_ranked(haystack, threshold, order, overlap, prefilter=prefilter)
-        ms = self.search_raw(haystack, threshold, prefilter=prefilter).retain_boundaries(boundaries)
+        ms = self.search_raw(haystack, threshold, prefilter=prefilter).retain_boundaries(boundaries).retain_anchors(anchors)
         if order == Order.Unsorted and overlap == Overlap.Keep:
             return ms
         return self.apply_on_device(ms, order, overlap)
@@ -408,7 +411,8 @@ class FuzzyAhoCorasick:
 
     # -- many independent haystacks in one device pass (fac_search_batch)
     def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None,
-                     unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[FuzzyMatches]:
+                     unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE,
+                     anchors: Anchor = Anchor.NONE) -> List[FuzzyMatches]:
         """`[self.search(h, opts) for h in haystacks]` as one call: every haystack is staged, searched
         and ranked as a text of its own (the crate has no such entry point; its answer to many
         documents is one engine shared by threads). Errors name the first offending document
@@ -422,7 +426,7 @@ class FuzzyAhoCorasick:
         enc = [h.encode("utf-8") for h in haystacks]
         data, offsets = batch_offsets(enc)
         recs, doc_off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings,
-                                    boundaries=boundaries).search_records(opts)
+                                    boundaries=boundaries, anchors=anchors).search_records(opts)
         out = []
         for d, (hay, raw) in enumerate(zip(haystacks, enc)):
             rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
@@ -431,8 +435,29 @@ class FuzzyAhoCorasick:
             out.append(self._to_matches(hay, raw, rows))
         return out
 
+    def lookup_batch(self, texts: Sequence[str], opts: SearchOptions = None, k: int = 1,
+                     unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[List[FuzzyMatch]]:
+        """Which entries IS each text? Per text the up to `k` matches that cover the whole text, best
+        first in the order `opts` names (Unsorted is taken as Default), as one call
+        (fac_lookup_batch, StagedBatch.lookup_records): the fuzzy join of a column against the
+        dictionary. An empty list: no entry matches the text as a whole."""
+        opts = opts or SearchOptions()
+        texts = list(texts)
+        enc = [t.encode("utf-8") for t in texts]
+        data, offsets = batch_offsets(enc)
+        recs, found = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings,
+                                  boundaries=boundaries).lookup_records(opts, k)
+        out = []
+        for d, (text, raw) in enumerate(zip(texts, enc)):
+            rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
+                     int(r["insertions"]), int(r["deletions"]), int(r["substitutions"]), int(r["swaps"]),
+                     int(r["edits"])) for r in recs[d, :int(found[d])]]
+            out.append(list(self._to_matches(text, raw, rows)))
+        return out
+
     def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements,
-                      unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[str]:
+                      unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE,
+                      anchors: Anchor = Anchor.NONE) -> List[str]:
         """`[self.replace(t, opts, lambda m: replacements[m.pattern_index]) for t in texts]` as one
         call (fac_replace_batch): searched, ranked and spliced on the device. `replacements` has one
         entry per pattern, `None` = keep the matched text (the callback's None, matches.rs:180-183).
@@ -443,11 +468,12 @@ class FuzzyAhoCorasick:
         data, offsets = batch_offsets(enc)
         table = replacements if isinstance(replacements, ReplacementTable) else ReplacementTable(self, replacements)
         out, off = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings,
-                               boundaries=boundaries).replace_bytes(table, opts)
+                               boundaries=boundaries, anchors=anchors).replace_bytes(table, opts)
         return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
     def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None,
-                      unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
+                      unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE,
+                      anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         """Per text, one string per match of `self.search(t, opts)`, in its order, as one call
         (fac_extract_batch): the matched text, or with `replacements` (one entry per pattern, or a
         ReplacementTable) what replace would put in its place -- the entry, `Wrap` rendered around
@@ -456,40 +482,41 @@ class FuzzyAhoCorasick:
         if replacements is not None and not isinstance(replacements, ReplacementTable):
             table = ReplacementTable(self, replacements)
         return _extract_batch(self, [t.encode("utf-8") for t in texts], opts or SearchOptions(), table, False,
-                              unicode_mappings, boundaries)
+                              unicode_mappings, boundaries, anchors)
 
     def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None,
-                              unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
+                              unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE,
+                              anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         """`[self.search(t, opts).matched_strings() for t in texts]` as one call (matches.rs:513-515)."""
-        return self.extract_batch(texts, opts, unicode_mappings=unicode_mappings, boundaries=boundaries)
+        return self.extract_batch(texts, opts, unicode_mappings=unicode_mappings, boundaries=boundaries, anchors=anchors)
 
     # -- the other segmentation helpers of a whole batch (fac_render_batch, fac_segment_batch): each is
     # one device call; whitespace is Rust's char::is_whitespace (DESIGN.md 6a "Batched segmentation")
     def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
-                           boundaries: Boundary = Boundary.NONE) -> List[str]:
+                           boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[str]:
         """`[self.strip_prefix(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_PREFIX, opts, False, unicode_mappings, boundaries)
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_PREFIX, opts, False, unicode_mappings, boundaries, anchors)
 
     def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
-                           boundaries: Boundary = Boundary.NONE) -> List[str]:
+                           boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[str]:
         """`[self.strip_suffix(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, False, unicode_mappings, boundaries)
+        return _render_batch(self, texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, False, unicode_mappings, boundaries, anchors)
 
     def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
-                           boundaries: Boundary = Boundary.NONE) -> List[str]:
+                           boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[str]:
         """`[self.segment_text(t, opts) for t in texts]` as one call."""
-        return _render_batch(self, texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, False, unicode_mappings, boundaries)
+        return _render_batch(self, texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, False, unicode_mappings, boundaries, anchors)
 
     def segment_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
-                      boundaries: Boundary = Boundary.NONE) -> List[List[Segment]]:
+                      boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[Segment]]:
         """`[list(self.segment_iter(t, opts)) for t in texts]` as one call."""
-        return _segment_batch(self, texts, opts, False, unicode_mappings, boundaries)
+        return _segment_batch(self, texts, opts, False, unicode_mappings, boundaries, anchors)
 
     def split_batch(self, texts: Sequence[str], opts: SearchOptions, unicode_mappings: bool = False,
-                    boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
+                    boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         """`[list(self.split(t, opts)) for t in texts]` as one call."""
         return [[s.unmatched().text for s in segs if s.unmatched() is not None]
-                for segs in _segment_batch(self, texts, opts, False, unicode_mappings, boundaries)]
+                for segs in _segment_batch(self, texts, opts, False, unicode_mappings, boundaries, anchors)]
 
 
 class Prefiltered:
@@ -540,7 +567,7 @@ class Prefiltered:
         return [d for d, raw in enumerate(enc) if raw.isascii()]
 
     def search_batch(self, haystacks: Sequence[str], opts: SearchOptions = None,
-                     boundaries: Boundary = Boundary.NONE) -> List[FuzzyMatches]:
+                     boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[FuzzyMatches]:
         """`[self.search(h, opts) for h in haystacks]`: the haystacks as one pre-filtered batch
         (fac_search_batch_prefiltered; `_batch_parts`: all of them, or the ASCII ones and the others
         one by one), results in input order. `boundaries` (here and in the other batch calls): as the
@@ -553,7 +580,7 @@ class Prefiltered:
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
             sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True,
-                             boundaries=boundaries)
+                             boundaries=boundaries, anchors=anchors)
             recs, doc_off = sb.search_records(opts, prefilter=True)
             for k, d in enumerate(idx):
                 rows = [(int(r["start"]), int(r["end"]), int(r["pattern_index"]), float(r["similarity"]),
@@ -562,11 +589,11 @@ class Prefiltered:
                 out[d] = self.engine._to_matches(haystacks[d], enc[d], rows)
         for d, h in enumerate(haystacks):
             if out[d] is None:
-                out[d] = self.engine._search_bounded(h, opts.threshold_, opts.order_, opts.overlap_, True, boundaries)
+                out[d] = self.engine._search_bounded(h, opts.threshold_, opts.order_, opts.overlap_, True, boundaries, anchors)
         return out
 
     def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements,
-                      boundaries: Boundary = Boundary.NONE) -> List[str]:
+                      boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[str]:
         """`engine.replace_batch` over the pre-filtered search: the ASCII texts as one pre-filtered
         batch (fac_replace_batch_prefiltered), the others through `search` and the host splice of
         matches.rs:170-187, results in input order. `replacements`: one entry per pattern (None
@@ -583,7 +610,7 @@ class Prefiltered:
         if idx:
             data, offsets = batch_offsets([enc[d] for d in idx])
             sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True,
-                             boundaries=boundaries)
+                             boundaries=boundaries, anchors=anchors)
             buf, off = sb.replace_bytes(table, opts, prefilter=True)
             for k, d in enumerate(idx):
                 out[d] = buf[int(off[k]):int(off[k + 1])].decode("utf-8")
@@ -591,12 +618,12 @@ class Prefiltered:
         overlap = Overlap.NonOverlapping if opts.overlap_ == Overlap.Keep else opts.overlap_
         for d, t in enumerate(texts):
             if out[d] is None:
-                ms = self.engine._search_bounded(t, opts.threshold_, order, overlap, True, boundaries)
+                ms = self.engine._search_bounded(t, opts.threshold_, order, overlap, True, boundaries, anchors)
                 out[d] = ms.replace(lambda m: _rendered_entry(reps[m.pattern_index], m))
         return out
 
     def extract_batch(self, texts: Sequence[str], opts: SearchOptions, replacements=None,
-                      boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
+                      boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         """`engine.extract_batch` over the pre-filtered search: the ASCII texts as one pre-filtered
         batch (fac_extract_batch_prefiltered), the others through `search`, results in input order."""
         opts = opts or SearchOptions()
@@ -611,25 +638,25 @@ class Prefiltered:
             table = ReplacementTable(self.engine, reps) if idx and reps is not None else None
         if idx:
             for d, items in zip(idx, _extract_batch(self.engine, [enc[d] for d in idx], opts, table, True, True,
-                                                  boundaries)):
+                                                  boundaries, anchors)):
                 out[d] = items
         for d, t in enumerate(texts):
             if out[d] is None:
                 out[d] = [_item_text(reps, m) for m in self.engine._search_bounded(
-                    t, opts.threshold_, opts.order_, opts.overlap_, True, boundaries)]
+                    t, opts.threshold_, opts.order_, opts.overlap_, True, boundaries, anchors)]
         return out
 
     def matched_strings_batch(self, texts: Sequence[str], opts: SearchOptions = None,
-                              boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
+                              boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         """`[self.search(t, opts).matched_strings() for t in texts]`, batched as extract_batch is."""
-        return self.extract_batch(texts, opts, boundaries=boundaries)
+        return self.extract_batch(texts, opts, boundaries=boundaries, anchors=anchors)
 
-    def _segmented(self, haystack: str, opts: SearchOptions, boundaries=Boundary.NONE) -> FuzzyMatches:
+    def _segmented(self, haystack: str, opts: SearchOptions, boundaries=Boundary.NONE, anchors=Anchor.NONE) -> FuzzyMatches:
         order = Order.Default if opts.order_ == Order.Unsorted else opts.order_
         overlap = Overlap.NonOverlapping if opts.overlap_ == Overlap.Keep else opts.overlap_
-        return self.engine._search_bounded(haystack, opts.threshold_, order, overlap, True, boundaries)
+        return self.engine._search_bounded(haystack, opts.threshold_, order, overlap, True, boundaries, anchors)
 
-    def _rendered(self, texts, mode: int, opts: SearchOptions, host, boundaries=Boundary.NONE) -> List[str]:
+    def _rendered(self, texts, mode: int, opts: SearchOptions, host, boundaries=Boundary.NONE, anchors=Anchor.NONE) -> List[str]:
         """The ASCII texts as one pre-filtered batch (fac_render_batch_prefiltered), the others
         through `search` and the host method `host`, results in input order."""
         texts = list(texts)
@@ -637,24 +664,27 @@ class Prefiltered:
         out = [None] * len(texts)
         idx = self._batch_parts(enc)
         if idx:
-            for d, r in zip(idx, _render_batch(self.engine, [texts[d] for d in idx], mode, opts, True, True, boundaries)):
+            for d, r in zip(idx, _render_batch(self.engine, [texts[d] for d in idx], mode, opts, True, True, boundaries, anchors)):
                 out[d] = r
         for d, t in enumerate(texts):
             if out[d] is None:
-                out[d] = host(self._segmented(t, opts, boundaries))
+                out[d] = host(self._segmented(t, opts, boundaries, anchors))
         return out
 
-    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
-        return self._rendered(texts, _native.FAC_RENDER_STRIP_PREFIX, opts, lambda ms: ms.strip_prefix(), boundaries)
+    def strip_prefix_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE,
+                           anchors: Anchor = Anchor.NONE) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_STRIP_PREFIX, opts, lambda ms: ms.strip_prefix(), boundaries, anchors)
 
-    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
-        return self._rendered(texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, lambda ms: ms.strip_suffix(), boundaries)
+    def strip_suffix_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE,
+                           anchors: Anchor = Anchor.NONE) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_STRIP_SUFFIX, opts, lambda ms: ms.strip_suffix(), boundaries, anchors)
 
-    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
-        return self._rendered(texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, lambda ms: ms.segment_text(), boundaries)
+    def segment_text_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE,
+                           anchors: Anchor = Anchor.NONE) -> List[str]:
+        return self._rendered(texts, _native.FAC_RENDER_SEGMENT_TEXT, opts, lambda ms: ms.segment_text(), boundaries, anchors)
 
     def segment_batch(self, texts: Sequence[str], opts: SearchOptions,
-                      boundaries: Boundary = Boundary.NONE) -> List[List[Segment]]:
+                      boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[Segment]]:
         """The ASCII texts as one pre-filtered batch (fac_segment_batch_prefiltered), the others
         through `search` and the host's segment_iter, results in input order."""
         texts = list(texts)
@@ -662,17 +692,17 @@ class Prefiltered:
         out = [None] * len(texts)
         idx = self._batch_parts(enc)
         if idx:
-            for d, segs in zip(idx, _segment_batch(self.engine, [texts[d] for d in idx], opts, True, True, boundaries)):
+            for d, segs in zip(idx, _segment_batch(self.engine, [texts[d] for d in idx], opts, True, True, boundaries, anchors)):
                 out[d] = segs
         for d, t in enumerate(texts):
             if out[d] is None:
-                out[d] = list(self._segmented(t, opts, boundaries).segment_iter())
+                out[d] = list(self._segmented(t, opts, boundaries, anchors).segment_iter())
         return out
 
     def split_batch(self, texts: Sequence[str], opts: SearchOptions,
-                    boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
+                    boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         return [[s.unmatched().text for s in segs if s.unmatched() is not None]
-                for segs in self.segment_batch(texts, opts, boundaries)]
+                for segs in self.segment_batch(texts, opts, boundaries, anchors)]
 
 
 def _as_text(r):
@@ -687,31 +717,31 @@ def _item_text(reps, m) -> str:
 
 
 def _extract_batch(engine: "FuzzyAhoCorasick", enc, opts: SearchOptions, table, prefilter: bool,
-                   unicode_mappings: bool = False, boundaries=Boundary.NONE) -> List[List[str]]:
+                   unicode_mappings: bool = False, boundaries=Boundary.NONE, anchors=Anchor.NONE) -> List[List[str]]:
     data, offsets = batch_offsets(enc)
     sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings,
-                     boundaries=boundaries)
+                     boundaries=boundaries, anchors=anchors)
     _, doc_off, text, item_off = sb.extract(table, opts, prefilter=prefilter)
     return [[text[int(item_off[i]):int(item_off[i + 1])].decode("utf-8")
              for i in range(int(doc_off[d]), int(doc_off[d + 1]))] for d in range(len(enc))]
 
 
 def _render_batch(engine: "FuzzyAhoCorasick", texts, mode: int, opts: SearchOptions, prefilter: bool,
-                  unicode_mappings: bool = False, boundaries=Boundary.NONE) -> List[str]:
+                  unicode_mappings: bool = False, boundaries=Boundary.NONE, anchors=Anchor.NONE) -> List[str]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
     sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings,
-                     boundaries=boundaries)
+                     boundaries=boundaries, anchors=anchors)
     out, off = sb.render_bytes(mode, opts, prefilter=prefilter)
     return [out[int(off[d]):int(off[d + 1])].decode("utf-8") for d in range(len(enc))]
 
 
 def _segment_batch(engine: "FuzzyAhoCorasick", texts, opts: SearchOptions, prefilter: bool,
-                   unicode_mappings: bool = False, boundaries=Boundary.NONE) -> List[List[Segment]]:
+                   unicode_mappings: bool = False, boundaries=Boundary.NONE, anchors=Anchor.NONE) -> List[List[Segment]]:
     enc = [t.encode("utf-8") for t in texts]
     data, offsets = batch_offsets(enc)
     sb = StagedBatch(engine, data, offsets, unicode_prefilter=prefilter, unicode_mappings=unicode_mappings,
-                     boundaries=boundaries)
+                     boundaries=boundaries, anchors=anchors)
     recs, doc_off = sb.segment_records(opts, prefilter=prefilter)
     out = []
     for d, raw in enumerate(enc):
@@ -1231,7 +1261,7 @@ class StagedBatch:
     validity, is_ascii and grapheme segmentation per document)."""
 
     def __init__(self, engine: FuzzyAhoCorasick, data: bytes, offsets, unicode_prefilter: bool = False,
-                 unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE):
+                 unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE):
         import numpy as np
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
         if off.ndim != 1 or len(off) < 1:
@@ -1255,17 +1285,19 @@ class StagedBatch:
             self.allow_unicode_mappings()
         if int(boundaries):
             self.require_boundaries(boundaries)
+        if int(anchors):
+            self.require_anchors(anchors)
 
     @classmethod
     def from_device(cls, engine: FuzzyAhoCorasick, d_utf8: int, d_offsets: int, n_docs: int, total_len: int,
                     stream=None, reuse: "StagedBatch" = None, unicode_prefilter: bool = False,
-                    unicode_mappings: bool = False, boundaries: Boundary = None) -> "StagedBatch":
+                    unicode_mappings: bool = False, boundaries: Boundary = None, anchors: Anchor = None) -> "StagedBatch":
         """fac_batch_stage_device: the bytes (`d_utf8`, total_len of them) and the n_docs + 1 uint64
         offsets (`d_offsets`) are device addresses, e.g. torch tensors' data_ptr() (borrowed: keep both
         alive). `reuse`: a batch staged this way before, restaged in place and returned (it keeps its
         opt-ins and its require_boundaries mask). `unicode_prefilter`, `unicode_mappings`: opt the batch
         in (allow_unicode_prefilter, allow_unicode_mappings). `boundaries`: require_boundaries (None:
-        a reused batch keeps what it had)."""
+        a reused batch keeps what it had). `anchors`: require_anchors, likewise."""
         h = ctypes.c_void_p(reuse._h.value if reuse is not None else None)
         ed = ctypes.c_uint64(0xFFFFFFFFFFFFFFFF)
         eg = ctypes.c_uint64()
@@ -1288,6 +1320,8 @@ class StagedBatch:
             obj.allow_unicode_mappings()
         if boundaries is not None:
             obj.require_boundaries(boundaries)
+        if anchors is not None:
+            obj.require_anchors(anchors)
         return obj
 
     def __del__(self):
@@ -1323,6 +1357,52 @@ class StagedBatch:
         if rc:
             _raise(rc)
         return self
+
+    def require_anchors(self, sides) -> "StagedBatch":
+        """fac_batch_require_anchors: every later call on this batch, plain or pre-filtered, keeps only
+        the raw records that start at byte 0 of their own document (Anchor.START), end at its end
+        (Anchor.END) or both (Anchor.WHOLE; 0 = off), before ranking and overlap resolution
+        (DESIGN.md 6a "Anchored matches"). A plain call then searches only the start windows such a
+        record can come from. Sets a flag and does no work. Returns self."""
+        rc = _native.lib.fac_batch_require_anchors(self._h, int(sides))
+        if rc:
+            _raise(rc)
+        return self
+
+    def lookup_records(self, opts: SearchOptions = None, k: int = 1, out=None, stream=None, stats=None):
+        """fac_lookup_batch: (records[n_docs, k], found). Row d holds the first min(k, m_d) of document
+        d's whole-string matches (both ends anchored, whatever require_anchors says) in the order
+        `opts` names (Unsorted is taken as Default; the overlap mode is not used: such matches all
+        cover the document), the other slots `pattern_index == _native.FAC_UNMATCHED` and zeros;
+        found[d] (uint32) = min(k, m_d). `out`: a uint8 CUDA tensor of at least n_docs * k * 32 bytes
+        to leave the table in HBM: returns (its filled part, found); too small raises DeviceError
+        (FAC_E_OUTPUT_CAPACITY) with `.needed` records and writes nothing."""
+        import numpy as np
+        opts = opts or SearchOptions()
+        a = _native.fac_lookup_args()
+        a.threshold = f32(opts.threshold_)
+        a.order = opts.order_.value
+        a.k = int(k)
+        a.stream = stream or None
+        found = np.zeros(self.n_docs, dtype=np.uint32)
+        ptr = ctypes.POINTER(_native.fac_match)()
+        total = self.n_docs * int(k)
+        if out is not None:
+            a.device_out = out.data_ptr()
+            a.device_cap = out.numel() // _native.REC_BYTES
+        rc = _native.lib.fac_lookup_batch(self.engine._h, self._h, ctypes.byref(a),
+                                          None if out is not None else ctypes.byref(ptr),
+                                          found.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                          ctypes.byref(stats) if stats is not None else None)
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed = total
+                raise
+        if out is not None:
+            return out[: total * _native.REC_BYTES], found
+        return _native.take_records(ptr, total).reshape(self.n_docs, int(k)), found
 
     def grapheme_ids(self, stream=None, engine=None):
         """fac_batch_grapheme_ids: the id in the grapheme dictionary of `engine` (default: the batch's;
@@ -1719,10 +1799,17 @@ class FuzzyReplacer:
         return self.engine.replace(text, opts, self._callback)
 
     def extract_batch(self, texts: Sequence[str], opts: SearchOptions,
-                      boundaries: Boundary = Boundary.NONE) -> List[List[str]]:
+                      boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         """Per text, the replacement of every match `engine.search(t, opts)` finds, as one device pass
         (fac_extract_batch): the canonical form of each mention."""
-        return self.engine.extract_batch(texts, opts, self._device_table(), boundaries=boundaries)
+        return self.engine.extract_batch(texts, opts, self._device_table(), boundaries=boundaries, anchors=anchors)
+
+    def lookup_batch(self, texts: Sequence[str], opts: SearchOptions = None) -> List[Optional[str]]:
+        """Per text the canonical form (the replacement) of the best entry that matches the text as a
+        whole, or None where no entry does: a column normalised against the dictionary in one device
+        pass (engine.lookup_batch with k = 1). A `None` entry stands for the text itself."""
+        return [_item_text(self.replacements, ms[0]) if ms else None
+                for ms in self.engine.lookup_batch(texts, opts, 1)]
 
     def _device_table(self) -> "ReplacementTable":
         key = tuple(self.replacements)
@@ -1730,9 +1817,10 @@ class FuzzyReplacer:
             self._table = (key, ReplacementTable(self.engine, self.replacements))
         return self._table[1]
 
-    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE) -> List[str]:
+    def replace_batch(self, texts: Sequence[str], opts: SearchOptions, boundaries: Boundary = Boundary.NONE,
+                      anchors: Anchor = Anchor.NONE) -> List[str]:
         """`[self.replace(t, opts) for t in texts]` as one device pass (fac_replace_batch)."""
-        return self.engine.replace_batch(texts, opts, self._device_table(), boundaries=boundaries)
+        return self.engine.replace_batch(texts, opts, self._device_table(), boundaries=boundaries, anchors=anchors)
 
     def replace_stream(self, reader, writer, threshold: float, prefilter: bool = False,
                        boundaries: Boundary = Boundary.NONE) -> int:

@@ -282,6 +282,19 @@ class FuzzyMatches:
             self.inner = kept
         return self
 
+    def retain_anchors(self, sides) -> "FuzzyMatches":
+        """Keep the matches that start at byte 0 of the haystack (Anchor.START), end at its end
+        (Anchor.END) or both (Anchor.WHOLE): the anchor rule of DESIGN.md 6a "Anchored matches". To be
+        called between search_raw and apply, like retain_boundaries."""
+        sides = int(sides)
+        if not 0 <= sides <= 3:
+            raise ValueError("sides must be an Anchor value (0..3)")
+        n = len(self.hay_bytes)
+        if sides:
+            self.inner = [m for m in self.inner
+                          if (not sides & 1 or m.start == 0) and (not sides & 2 or m.end == n)]
+        return self
+
     def filter(self, pred) -> "FuzzyMatches":
         return FuzzyMatches(self.haystack, [m for m in self.inner if pred(m)], self.hay_bytes)
 

@@ -227,6 +227,16 @@ class Boundary(enum.IntFlag):
     WHOLE = 3
 
 
+class Anchor(enum.IntFlag):
+    """The ends of its document a match must touch (fac.h FAC_ANCHOR_*, DESIGN.md 6a "Anchored
+    matches"): START = it begins at byte 0, END = it ends at the document's end, WHOLE = both, the
+    match is the whole string. The crate's route is FuzzyMatches::retain between search_raw and apply."""
+    NONE = 0
+    START = 1
+    END = 2
+    WHOLE = 3
+
+
 DEFAULT_THRESHOLD = 0.0  # options.rs:7
 
 

@@ -529,6 +529,51 @@ int32_t fac_boundary_ok(const uint8_t* utf8, uint64_t len, uint64_t start, uint6
  * bytes are never read as a code point. */
 int32_t fac_boundary_ok_after(const uint8_t* before, uint64_t before_len, int32_t more_before, const uint8_t* utf8,
                               uint64_t len, uint64_t start, uint64_t end, int32_t sides);
+
+/* ---- Anchored matches. The batch calls answer "where in this document does a dictionary entry
+ * occur?"; for a column of names or titles the question is as often "which entry IS this string?"
+ * (a fuzzy join, normalising a column against canonical names). The crate's route is
+ * FuzzyMatches::retain between search_raw and apply (matches.rs:417); for a batch that filter runs
+ * on the device at the same point as the whole-token filter above, and it lets the search skip the
+ * start windows that cannot contribute.
+ *
+ * The rule. `sides` is a mask of FAC_ANCHOR_START and FAC_ANCHOR_END. A raw record (start, end) of a
+ * document doc[0, n) is kept when start == 0, if START is requested, and end == n, if END is
+ * requested. Offsets are bytes within the record's own document, ASCII or not. Empty spans follow
+ * the same rule; an empty document has no windows and so no records. The rule reads only the record
+ * and the document's two offsets: never the text, and it does not depend on the engine. It runs on
+ * the complete raw record set before apply(order, overlap), together with the whole-token filter
+ * when both masks are set (both are pure predicates, so their order does not matter): for every
+ * document the result of a batch call is apply(order, overlap) of {r in search_raw(doc) : rule(r)},
+ * and of {r in Prefiltered::raw(doc) : rule(r)} for a pre-filtered call.
+ *
+ * The window restriction. Start windows of one search_raw are independent (fac_search_staged:
+ * disjoint window ranges give disjoint record sets). A record with start == 0 can only come from
+ * start window 0, and a record that ends at the document's end only from the last
+ * fac_max_match_graphemes() windows. A plain (not pre-filtered) call on an engine that is not
+ * auto-beam-only therefore searches one window per non-empty document for START and WHOLE, and for
+ * END alone the last min(n, T) windows, T = fac_max_match_graphemes() + 2 (the bound and margin of
+ * fac_shard_plan's halo); fac_stats.windows reports the windows searched. The records are the
+ * unrestricted call's: the restriction only leaves out windows whose records the rule drops.
+ * Auto-beam-only engines (has_auto_beam, beam_width == 0) search every window -- the crate's
+ * running total runs over all windows in order (search.rs:1096-1103), so leaving windows out would
+ * move the switch point -- and pre-filtered calls keep their merged windows; both get the filter.
+ *
+ * fac_batch_require_anchors sets the mask of a batch (0 = off, the default; 0..3, anything else or
+ * NULL gives FAC_E_INVALID). It sets a flag and does no work; the flag survives a restage in place;
+ * not to be called concurrently with a search of the same batch. It is independent of the boundary
+ * mask and of both Unicode opt-ins, and honoured by fac_search_batch, fac_replace_batch,
+ * fac_extract_batch, fac_segment_batch, fac_render_batch and their _prefiltered forms. With the mask
+ * 0 the calls launch, allocate and upload nothing for it. Streams and fac_search_staged* are not
+ * covered (a window has no document end). */
+#define FAC_ANCHOR_START 1
+#define FAC_ANCHOR_END 2
+#define FAC_ANCHOR_WHOLE 3
+int fac_batch_require_anchors(fac_batch* batch, int32_t sides);
+/* Tests and hosts: the rule above for a record (start, end) of a document of doc_len bytes: 1 =
+ * kept, 0 = dropped; -FAC_E_INVALID for sides outside 0..3, start > end or end > doc_len. */
+int32_t fac_anchor_ok(uint64_t doc_len, uint64_t start, uint64_t end, int32_t sides);
+
 /* Tests and hosts: as fac_haystack_grapheme_ids for the graphemes of the batch's non-ASCII documents,
  * in document order (fac_batch_doc_graphemes of those documents, concatenated). An all-ASCII batch
  * writes nothing and returns 0. Needs no opt-in. */
@@ -589,6 +634,31 @@ int fac_search_batch_prefiltered(const fac_engine* engine, const fac_batch* batc
  * back to the full search, or minus the error code (every FAC_E_* that can occur here is >= 100). */
 int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* batch, float threshold, void* stream,
                                     uint64_t* out, uint64_t cap);
+
+/* ---- Dictionary lookup of a batch ("Anchored matches" above): the dense form a join wants. Row d
+ * of an n_docs x k table holds the first min(k, m_d) records of apply(order, Keep) over document d's
+ * FAC_ANCHOR_WHOLE-anchored raw records (m_d of them), start and end relative to the document; the
+ * remaining slots hold pattern_index = FAC_UNMATCHED, similarity 0, all counts 0 and start = end = 0.
+ * found (host array of n_docs entries, may be NULL) receives min(k, m_d). The three orders are total
+ * orders (matches.rs:24-81) and with WHOLE a document has at most one record per pattern, so the
+ * table is fully determined. order 0 is taken as 1 (Default), as the replace calls take it.
+ * The table goes to the host (*out, fac_matches_free; n_docs * k records) or, with device_out set,
+ * into that device buffer of device_cap records (out may then be NULL); FAC_E_OUTPUT_CAPACITY: the
+ * buffer holds fewer than n_docs * k records, and nothing was written. FAC_E_INVALID: k == 0, a NULL
+ * argument, a bad order; FAC_E_UNSUPPORTED: n_docs * k >= 2^40. The call applies WHOLE whatever the
+ * batch's own anchor mask says and does not modify the batch; the batch's boundary mask and Unicode
+ * opt-ins apply as in fac_search_batch, and so do its other errors and limits. There is no
+ * _prefiltered form: one window per document leaves the pre-filter nothing to save. */
+typedef struct fac_lookup_args {
+  float threshold;
+  int32_t order;  /* as fac_matches_apply; 0 = 1 */
+  uint32_t k;     /* slots per document, > 0 */
+  void* stream;
+  void* device_out; /* optional: the table stays in HBM */
+  uint64_t device_cap;
+} fac_lookup_args;
+int fac_lookup_batch(const fac_engine* engine, const fac_batch* batch, const fac_lookup_args* args, fac_match** out,
+                     uint32_t* found, fac_stats* stats);
 
 /* ---- Batched replace: FuzzyReplacer::replace (replacer.rs:22-25, query.rs:46-96,
  * matches.rs:165-188) of every document of a staged batch, spliced on the device.
