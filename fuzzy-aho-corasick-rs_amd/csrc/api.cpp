@@ -1636,6 +1636,160 @@ int fac_lookup_batch(const fac_engine* engine, const fac_batch* batch, const fac
   return hand_out(fin, out, &n_out);
 }
 
+// ---- term counts (fac.h "Term counts of a batch"): search + apply with the options as passed, then
+// the group-by of count_kernels.hip over the kept records in HBM
+
+// The pattern -> key table's checks, made before anything runs; *eff: the keys the totals hold
+static int count_keys_check(const uint32_t* keys, uint64_t n_patterns, uint64_t n_keys, uint64_t* eff) {
+  if (!keys) {
+    if (n_keys != 0 && n_keys != n_patterns)
+      return fail(FAC_E_INVALID, "n_keys must be 0 or the pattern count when keys is NULL");
+    *eff = n_patterns;
+    return FAC_OK;
+  }
+  if (n_keys > 0xFFFFFFFFull) return fail(FAC_E_INVALID, "n_keys must be at most 2^32 - 1");
+  for (uint64_t p = 0; p < n_patterns; ++p)
+    if (keys[p] >= n_keys) return fail(FAC_E_INVALID, "a key is not below n_keys");
+  *eff = n_keys;
+  return FAC_OK;
+}
+
+// Pass 2, the totals and the copies of a planned count: the capacity is checked first, so a refused
+// call has written to no device output.
+static int count_deliver(const fac::CountPlan& plan, uint64_t n_keys, hipStream_t st, fac_term* device_out,
+                         uint64_t device_cap, uint64_t* device_doc_offsets, fac_term_total* device_totals, fac_term** out,
+                         uint64_t* n_out, uint64_t* doc_offsets, fac_term_total* totals) {
+  const uint64_t nd = plan.n_docs, total = plan.total;
+  *n_out = total;
+  if (device_out && total > device_cap)
+    return fail(FAC_E_OUTPUT_CAPACITY, "device output buffer too small (*n_out = terms needed)");
+  std::string err;
+  DevMem tbuf(st), totbuf(st);
+  fac_term* d_terms = device_out;
+  if (!d_terms) {
+    if (int rc = tbuf.alloc(total * sizeof(fac_term), err)) return fail(rc, err);
+    d_terms = static_cast<fac_term*>(tbuf.p);
+  }
+  if (int rc = fac::count_write_device(plan, d_terms, err)) return fail(rc, err);
+  fac_term_total* d_tot = device_totals;
+  if ((totals || device_totals) && n_keys) {
+    if (!d_tot) {
+      if (int rc = totbuf.alloc(n_keys * sizeof(fac_term_total), err)) return fail(rc, err);
+      d_tot = static_cast<fac_term_total*>(totbuf.p);
+    }
+    if (int rc = fac::count_totals_device(d_terms, total, n_keys, d_tot, st, err)) return fail(rc, err);
+  }
+  fac_term* h_terms = nullptr;
+  if (!device_out) {
+    h_terms = static_cast<fac_term*>(std::malloc(std::max<uint64_t>(total, 1) * sizeof(fac_term)));
+    if (!h_terms) return fail(FAC_E_OOM, "out of host memory");
+  }
+  if ((h_terms && total && hipMemcpyAsync(h_terms, d_terms, total * sizeof(fac_term), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (doc_offsets && hipMemcpyAsync(doc_offsets, plan.d_term_off, (nd + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (device_doc_offsets &&
+       hipMemcpyAsync(device_doc_offsets, plan.d_term_off, (nd + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+      (totals && n_keys &&
+       hipMemcpyAsync(totals, d_tot, n_keys * sizeof(fac_term_total), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    std::free(h_terms);
+    return fail(FAC_E_HIP, "copy of the batch's terms failed");
+  }
+  if (h_terms) *out = h_terms;
+  return FAC_OK;
+}
+
+// The body of fac_count_batch and fac_count_batch_prefiltered (prefilter: as search_batch_impl)
+static int count_batch_impl(const fac_engine* engine, const fac_batch* batch, const fac_count_args* args, fac_term** out,
+                            uint64_t* n_out, uint64_t* doc_offsets, fac_term_total* totals, fac_stats* stats,
+                            bool prefilter) {
+  if (!engine || !batch || !args || !n_out || (!out && !args->device_out)) return fail(FAC_E_INVALID, "NULL argument");
+  if (args->order < 0 || args->order > 3 || args->overlap < 0 || args->overlap > 2)
+    return fail(FAC_E_INVALID, "bad order/overlap");
+  if (out) *out = nullptr;
+  *n_out = 0;
+  const fac::Engine& e = engine->e;
+  const fac::Batch& b = batch->b;
+  uint64_t n_keys = 0;
+  if (int rc = count_keys_check(args->keys, e.pats.size(), args->n_keys, &n_keys)) return rc;
+  if (b.h.device != e.device) return fail(FAC_E_INVALID, "batch was staged for another device");
+  if (e.has_map && !b.h.ascii && !b.unicode_map)
+    return fail(FAC_E_UNSUPPORTED, "batches with non-ASCII documents do not support multi-character mappings");
+  if (hipSetDevice(e.device) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = args->stream ? static_cast<hipStream_t>(args->stream) : e.stream;
+  std::string err;
+  BatchKept k(st);
+  if (int rc = batch_kept(e, b, args->threshold, args->order, args->overlap, args->unique_ids, prefilter, st, nullptr, stats,
+                          k, err))
+    return fail(rc, err);
+  fac::CountPlan plan;
+  if (int rc = fac::count_plan_device(k.res, k.d_doc, b.n_docs, args->keys, e.pats.size(), 0, 0, st, plan, err))
+    return fail(rc, err);
+  return count_deliver(plan, n_keys, st, static_cast<fac_term*>(args->device_out), args->device_cap,
+                       args->device_doc_offsets, args->device_totals, out, n_out, doc_offsets, totals);
+}
+
+int fac_count_batch(const fac_engine* engine, const fac_batch* batch, const fac_count_args* args, fac_term** out,
+                    uint64_t* n_out, uint64_t* doc_offsets, fac_term_total* totals, fac_stats* stats) {
+  return count_batch_impl(engine, batch, args, out, n_out, doc_offsets, totals, stats, false);
+}
+
+int fac_count_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_count_args* args,
+                                fac_term** out, uint64_t* n_out, uint64_t* doc_offsets, fac_term_total* totals,
+                                fac_stats* stats) {
+  return count_batch_impl(engine, batch, args, out, n_out, doc_offsets, totals, stats, true);
+}
+
+int64_t fac_count_records(const fac_match* recs, uint64_t n, const uint32_t* keys, uint64_t n_patterns, uint64_t n_keys,
+                          fac_term* out, uint64_t cap) {
+  if (n && !recs) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");
+  if (n >> 32) return -(int64_t)fail(FAC_E_UNSUPPORTED, "a document has 2^32 or more kept records");
+  uint64_t eff = 0;
+  if (int rc = count_keys_check(keys, n_patterns, n_keys, &eff)) return -(int64_t)rc;
+  for (uint64_t i = 0; i < n; ++i)
+    if (recs[i].pattern_index >= n_patterns) return -(int64_t)fail(FAC_E_INVALID, "a pattern_index is not below n_patterns");
+  std::vector<fac_term> terms;
+  fac::count_records_host(recs, n, keys, terms);
+  if (out) {
+    if (terms.size() > cap) return -(int64_t)fail(FAC_E_OUTPUT_CAPACITY, "term buffer too small");
+    std::copy(terms.begin(), terms.end(), out);
+  }
+  return (int64_t)terms.size();
+}
+
+int fac_diag_count_terms(const fac_match* recs, uint64_t n, const uint64_t* doc_offsets, uint64_t n_docs,
+                         const uint32_t* keys, uint64_t n_patterns, uint64_t n_keys, uint32_t lane_max, uint32_t group_max,
+                         fac_term** out, uint64_t* n_out, uint64_t* term_offsets, fac_term_total* totals) {
+  if (!doc_offsets || !out || !n_out || !term_offsets || (n && !recs)) return fail(FAC_E_INVALID, "NULL argument");
+  *out = nullptr;
+  *n_out = 0;
+  if (lane_max > fac::kCountLaneMax || group_max > fac::kCountGroupMax)
+    return fail(FAC_E_INVALID, "a tier ceiling above the built-in maximum");
+  if (n_docs > fac::kBatchMaxDocs || n >= (1ull << fac::kDocTagShift)) return fail(FAC_E_UNSUPPORTED, "at most 2^24 documents");
+  if (doc_offsets[0] != 0 || doc_offsets[n_docs] != n) return fail(FAC_E_INVALID, "doc_offsets must run from 0 to n");
+  for (uint64_t d = 0; d < n_docs; ++d)
+    if (doc_offsets[d] > doc_offsets[d + 1]) return fail(FAC_E_INVALID, "doc_offsets must ascend");
+  uint64_t eff = 0;
+  if (int rc = count_keys_check(keys, n_patterns, n_keys, &eff)) return rc;
+  for (uint64_t i = 0; i < n; ++i)
+    if (recs[i].pattern_index >= n_patterns) return fail(FAC_E_INVALID, "a pattern_index is not below n_patterns");
+  if (int rc = check_device(0)) return rc;
+  if (hipSetDevice(0) != hipSuccess) return fail(FAC_E_HIP, "hipSetDevice failed");
+  hipStream_t st = nullptr;
+  std::string err;
+  DevMem drecs(st), ddoc(st);
+  if (int rc = drecs.alloc(n * sizeof(fac_match), err)) return fail(rc, err);
+  if (int rc = ddoc.alloc((n_docs + 1) * 8, err)) return fail(rc, err);
+  if ((n && hipMemcpyAsync(drecs.p, recs, n * sizeof(fac_match), hipMemcpyHostToDevice, st) != hipSuccess) ||
+      hipMemcpyAsync(ddoc.p, doc_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess)
+    return fail(FAC_E_HIP, "upload of the records failed");
+  fac::CountPlan plan;
+  if (int rc = fac::count_plan_device(static_cast<const fac_match*>(drecs.p), static_cast<const uint64_t*>(ddoc.p), n_docs, keys,
+                                      n_patterns, lane_max, group_max, st, plan, err))
+    return fail(rc, err);
+  return count_deliver(plan, eff, st, nullptr, 0, nullptr, nullptr, out, n_out, term_offsets, totals);
+}
+
 int64_t fac_batch_prefilter_windows(const fac_engine* engine, const fac_batch* batch, float threshold, void* stream,
                                     uint64_t* out, uint64_t cap) {
   if (!engine || !batch || (cap && !out)) return -(int64_t)fail(FAC_E_INVALID, "NULL argument");

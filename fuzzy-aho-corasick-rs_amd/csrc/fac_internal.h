@@ -19,6 +19,7 @@
 
 #include <condition_variable>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <unordered_map>
@@ -673,6 +674,54 @@ int anchor_filter_device(const Batch& b, int sides, const fac_match* d_in, uint6
                          unsigned long long* d_count, hipStream_t s, uint64_t* n_kept, std::string& err);
 int lookup_table_device(const fac_match* d_recs, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t k, fac_match* d_table,
                         uint32_t* d_found, hipStream_t s, std::string& err);
+// f32 total_cmp as an unsigned key on the host (wave_util.h total_key is the device's)
+inline uint32_t total_key_host(float f) {
+  uint32_t b;
+  std::memcpy(&b, &f, 4);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// count_kernels.hip (fac.h "Term counts of a batch"): the group-by of a batch's applied records
+// (d_recs, document-relative, grouped by document, with their CSR index d_doc) by key(pattern_index).
+// Documents are handled by their record count m_d: m_d <= lane_max one lane each, m_d <= group_max
+// one workgroup each, the rest through a device merge sort. The ceilings passed at run time may be
+// lower than these built-in ones (fac_diag_count_terms), never higher.
+constexpr uint32_t kCountLaneMax = 8;      // records a lane sorts in registers
+constexpr uint32_t kCountGroupMax = 2048;  // records a workgroup sorts in LDS: 32 KiB + 16 B (count_kernels.hip)
+constexpr uint32_t kCountHistKeys = 4096;  // n_keys up to which the totals use a 32 KiB LDS histogram per workgroup
+void call_scratch_give(void* p, hipStream_t s);  // (declared with the pool below)
+struct CountPlan {
+  hipStream_t s = nullptr;
+  void* mem[8] = {};  // call scratch, given back on s
+  const fac_match* d_recs = nullptr;
+  const uint64_t* d_doc = nullptr;
+  const uint32_t* d_keys = nullptr;  // device copy of the pattern -> key table, or NULL (key = pattern)
+  uint64_t n_docs = 0;
+  uint32_t lane_max = 0, group_max = 0;
+  // documents per tier (the group tier in two lists: up to 64 records, and more), records of the sorted tier
+  uint64_t n_lane = 0, n_wave = 0, n_group = 0, n_sorted = 0, sorted_recs = 0;
+  uint32_t *d_lane = nullptr, *d_wave = nullptr, *d_group = nullptr, *d_sorted = nullptr;  // the document lists
+  uint64_t* d_term_off = nullptr;  // n_docs + 1: the CSR index into the terms
+  void* d_entries = nullptr;       // sorted tier: the sorted entries, their run ids, run heads, per-document base
+  uint64_t *d_hid = nullptr, *d_hpos = nullptr, *d_aux = nullptr;
+  uint64_t total = 0;  // terms of the whole batch
+  ~CountPlan() {
+    for (void* p : mem)
+      if (p) call_scratch_give(p, s);
+  }
+};
+// Pass 1: classifies the documents, counts every document's distinct keys, scans the counts into
+// plan.d_term_off and reads plan.total back (synchronises twice). keys: host array of n_patterns
+// entries or NULL; uploaded here. FAC_E_UNSUPPORTED: a document with 2^32 or more records.
+int count_plan_device(const fac_match* d_recs, const uint64_t* d_doc, uint64_t n_docs, const uint32_t* keys,
+                      uint64_t n_patterns, uint32_t lane_max, uint32_t group_max, hipStream_t s, CountPlan& plan,
+                      std::string& err);
+// Pass 2: writes the plan.total terms to d_terms, one 16-byte store each (asynchronous on plan.s).
+int count_write_device(const CountPlan& plan, fac_term* d_terms, std::string& err);
+// The corpus totals of n_terms terms: zeroes d_totals[0, n_keys) and adds every term (asynchronous on s).
+int count_totals_device(const fac_term* d_terms, uint64_t n_terms, uint64_t n_keys, fac_term_total* d_totals, hipStream_t s,
+                        std::string& err);
+// The rule on the host (fac.h fac_count_records): terms in ascending key order.
+void count_records_host(const fac_match* recs, uint64_t n, const uint32_t* keys, std::vector<fac_term>& out);
 // The whole-token mask of a stream task (fac.h fac_stream_open_opts) and the stream's text before
 // the task's first byte: the last before_len (<= kBoundaryCarry) bytes of it, on the host;
 // more_before: the stream has text before those.

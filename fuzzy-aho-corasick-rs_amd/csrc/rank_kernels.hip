@@ -26,16 +26,12 @@
 
 #include "fac_internal.h"
 #include "host_util.h"
+#include "wave_util.h"
 
 namespace fac {
 namespace {
 
-// f32 total_cmp as an unsigned key (ascending key order == total order)
-__device__ inline uint32_t total_key(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
+// (total_key, f32 total_cmp as an unsigned key: wave_util.h)
 struct RankCmp {  // "a before b" for Order::{Default, Greedy, CoverageWeighted}
   const uint32_t* plen;  // pattern byte length (structs.rs:628-630: Pattern::len is bytes)
   int order;             // 1 default, 2 greedy, 3 coverage-weighted
@@ -65,12 +61,7 @@ struct RankCmp {  // "a before b" for Order::{Default, Greedy, CoverageWeighted}
 
 // The same order on the host (window_owned_device's small-window path): host f32 products are
 // rounded once each like __fmul_rn (-ffp-contract=off), and the order is total, so std::sort
-// gives the device sort's result
-inline uint32_t total_key_host(float f) {
-  uint32_t b;
-  std::memcpy(&b, &f, 4);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+// gives the device sort's result (total_key_host: fac_internal.h)
 struct RankCmpHost {
   const uint32_t* plen;
   int order;

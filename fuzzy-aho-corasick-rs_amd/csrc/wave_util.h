@@ -1,5 +1,6 @@
 // wave_util.h — device-only lane and wave helpers shared by the kernel files (search_kernels.hip,
-// prefilter_kernels.hip). All force-inlined; a wave is 64 lanes (gfx950).
+// prefilter_kernels.hip, ...), and the f32 total-order key rank_kernels.hip and count_kernels.hip share.
+// A wave is 64 lanes (gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,14 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int l) {
   const uint32_t lo = shfl_u32((uint32_t)v, l), hi = shfl_u32((uint32_t)(v >> 32), l);
   return ((uint64_t)hi << 32) | lo;
 }
+
+// f32 total_cmp as an unsigned key (ascending key order == total order; rank_kernels.hip's sort
+// keys, count_kernels.hip's similarity order word), and the float's bits back from the key
+__device__ inline uint32_t total_key(float f) {
+  const uint32_t b = __float_as_uint(f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__host__ __device__ inline uint32_t total_key_bits(uint32_t k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
 
 // Wave-wide inclusive prefix sum (DPP row shifts + row broadcasts).
 __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v) {

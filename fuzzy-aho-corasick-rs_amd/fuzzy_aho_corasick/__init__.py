@@ -6,7 +6,8 @@ Segment, Similarity, SearchError. The search itself runs in HIP kernels (libfac.
 """
 from .engine import (FuzzyAhoCorasick, FuzzyAhoCorasickBuilder, FuzzyReplacer, Prefiltered, ReplacementTable,
                      StagedBatch, StagedHaystack, StreamMatch, Wrap, batch_offsets, replacement_table, template_table)
-from .matches import FuzzyMatch, FuzzyMatches, Segment, UnmatchedSegment
+from ._native import TERM_DTYPE
+from .matches import FuzzyMatch, FuzzyMatches, Segment, TermCount, UnmatchedSegment
 from .structs import (DEFAULT_THRESHOLD, Anchor, Boundary, DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge,
                       Order, Overlap, Pattern, SearchError, SearchOptions, Similarity,
                       UnsupportedConfiguration)
@@ -16,5 +17,5 @@ __all__ = [
     "StagedBatch", "batch_offsets", "ReplacementTable", "replacement_table", "Wrap", "template_table",
     "FuzzyMatch", "FuzzyMatches", "Segment", "UnmatchedSegment", "DEFAULT_THRESHOLD", "DeviceError",
     "FuzzyLimits", "FuzzyPenalties", "HaystackTooLarge", "Order", "Overlap", "Pattern", "SearchError",
-    "SearchOptions", "Similarity", "UnsupportedConfiguration", "Boundary", "Anchor",
+    "SearchOptions", "Similarity", "UnsupportedConfiguration", "Boundary", "Anchor", "TERM_DTYPE", "TermCount",
 ]

@@ -100,6 +100,35 @@ class fac_lookup_args(ctypes.Structure):
                 ("stream", ctypes.c_void_p), ("device_out", ctypes.c_void_p), ("device_cap", ctypes.c_uint64)]
 
 
+class fac_term(ctypes.Structure):
+    _fields_ = [("key", ctypes.c_uint32), ("count", ctypes.c_uint32), ("best_similarity", ctypes.c_float),
+                ("best_pattern", ctypes.c_uint32)]
+
+
+class fac_term_total(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint64), ("docs", ctypes.c_uint64)]
+
+
+class fac_count_args(ctypes.Structure):
+    _fields_ = [("threshold", ctypes.c_float), ("order", ctypes.c_int32), ("overlap", ctypes.c_int32),
+                ("unique_ids", ctypes.POINTER(ctypes.c_uint64)), ("keys", ctypes.POINTER(ctypes.c_uint32)),
+                ("n_keys", ctypes.c_uint64), ("stream", ctypes.c_void_p), ("device_out", ctypes.c_void_p),
+                ("device_cap", ctypes.c_uint64), ("device_doc_offsets", ctypes.c_void_p),
+                ("device_totals", ctypes.c_void_p)]
+
+
+def _term_dtype():
+    import numpy as np
+    return np.dtype([("key", "<u4"), ("count", "<u4"), ("best_similarity", "<f4"), ("best_pattern", "<u4")])
+
+
+TERM_DTYPE = _term_dtype()  # the 16-byte fac_term
+TERM_BYTES = 16
+COUNT_LANE_MAX = 8       # kCountLaneMax: records of a document one lane groups
+COUNT_GROUP_MAX = 2048   # kCountGroupMax: records of a document one workgroup groups
+COUNT_HIST_KEYS = 4096   # kCountHistKeys: n_keys up to which the totals use the LDS histogram
+
+
 class fac_replace_args(ctypes.Structure):
     _fields_ = [("threshold", ctypes.c_float), ("order", ctypes.c_int32), ("overlap", ctypes.c_int32),
                 ("unique_ids", ctypes.POINTER(ctypes.c_uint64)), ("stream", ctypes.c_void_p),
@@ -270,6 +299,15 @@ SIGNATURES = {
     "fac_anchor_ok": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32]),
     "fac_lookup_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_lookup_args), _P(_P(fac_match)),
                                         _P(ctypes.c_uint32), _P(fac_stats)]),
+    "fac_count_batch": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_count_args), _P(_P(fac_term)), _u64p, _u64p,
+                                       ctypes.c_void_p, _P(fac_stats)]),
+    "fac_count_batch_prefiltered": (ctypes.c_int, [_engine_p, ctypes.c_void_p, _P(fac_count_args), _P(_P(fac_term)), _u64p,
+                                                   _u64p, ctypes.c_void_p, _P(fac_stats)]),
+    "fac_count_records": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]),
+    "fac_diag_count_terms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                            ctypes.c_uint32, _P(_P(fac_term)), _u64p, ctypes.c_void_p, ctypes.c_void_p]),
     "fac_boundary_class": (ctypes.c_int32, [ctypes.c_uint32]),
     "fac_boundary_ok": (ctypes.c_int32, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                          ctypes.c_int32]),
@@ -362,6 +400,42 @@ def take_records(ptr, n):
     buf = (ctypes.c_uint8 * (n * 32)).from_address(addr)
     weakref.finalize(buf, lib.fac_matches_free, ctypes.cast(addr, ctypes.POINTER(fac_match)))
     return np.frombuffer(buf, dtype=MATCH_DTYPE)
+
+
+def take_terms(ptr, n):
+    """Copy a library-allocated fac_term array into a NumPy TERM_DTYPE array and free it."""
+    import numpy as np
+    try:
+        if n == 0:
+            return np.zeros(0, dtype=TERM_DTYPE)
+        addr = ctypes.cast(ptr, ctypes.c_void_p).value
+        return np.frombuffer((ctypes.c_uint8 * (n * TERM_BYTES)).from_address(addr), dtype=TERM_DTYPE).copy()
+    finally:
+        lib.fac_buffer_free(ctypes.cast(ptr, ctypes.c_void_p))
+
+
+def count_records(recs, keys=None, n_patterns=None, n_keys=None):
+    """fac_count_records (host only): the terms (TERM_DTYPE, ascending key) of one document's records
+    (a MATCH_DTYPE array). `keys`: one key per pattern (then n_patterns = len(keys)) or None
+    (key = pattern index; n_patterns must be given). Raises ValueError with the library's message."""
+    import numpy as np
+    recs = np.ascontiguousarray(recs, dtype=MATCH_DTYPE)
+    karr = None
+    if keys is not None:
+        karr = np.ascontiguousarray(np.asarray(keys, dtype=np.int64).astype(np.uint32))
+        if (np.asarray(keys, dtype=np.int64) != karr).any():
+            raise ValueError("keys must be 32-bit unsigned")
+        n_patterns = len(karr)
+    if n_keys is None:
+        n_keys = 0 if karr is None else (int(karr.max()) + 1 if len(karr) else 0)
+    out = np.zeros(max(1, len(recs)), dtype=TERM_DTYPE)
+    n = lib.fac_count_records(recs.ctypes.data if len(recs) else None, len(recs), karr.ctypes.data if karr is not None else None,
+                              int(n_patterns), int(n_keys), out.ctypes.data, len(out))
+    if n < 0:
+        err = ValueError(last_error())
+        err.code = int(-n)
+        raise err
+    return out[: int(n)]
 
 
 def take_matches(ptr, n):

@@ -6,12 +6,12 @@ import ctypes
 import os
 import sys
 import time
-from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple, Union
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 from . import _native
 
 _TIMING = bool(os.environ.get("FAC_TIMING"))  # diagnostics: host-side phase times
-from .matches import FuzzyMatch, FuzzyMatches, Segment, UnmatchedSegment
+from .matches import FuzzyMatch, FuzzyMatches, Segment, TermCount, UnmatchedSegment
 from .structs import (Anchor, Boundary, DeviceError, FuzzyLimits, FuzzyPenalties, HaystackTooLarge, Order, Overlap,
                       Pattern, SearchError, SearchOptions, Similarity, UnsupportedConfiguration, f32)
 
@@ -455,6 +455,19 @@ class FuzzyAhoCorasick:
             out.append(list(self._to_matches(text, raw, rows)))
         return out
 
+    def count_batch(self, texts: Sequence[str], opts: SearchOptions = None, keys=None, n_keys=None,
+                    unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE,
+                    anchors: Anchor = Anchor.NONE) -> List[Dict[int, TermCount]]:
+        """Which entries does each text mention, and how often? `[self.search(t, opts).term_counts(keys,
+        n_keys) for t in texts]` as one call (fac_count_batch, StagedBatch.count_records): per text
+        {key: TermCount(count, best_similarity, best_pattern)} in ascending key order, grouped on the
+        device. `keys`: one key per pattern (None: key = pattern index)."""
+        enc = [t.encode("utf-8") for t in texts]
+        data, offsets = batch_offsets(enc)
+        terms, doc_off, _ = StagedBatch(self, data, offsets, unicode_mappings=unicode_mappings, boundaries=boundaries,
+                                        anchors=anchors).count_records(opts, keys, n_keys)
+        return _term_dicts(terms, doc_off)
+
     def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements,
                       unicode_mappings: bool = False, boundaries: Boundary = Boundary.NONE,
                       anchors: Anchor = Anchor.NONE) -> List[str]:
@@ -592,6 +605,31 @@ class Prefiltered:
                 out[d] = self.engine._search_bounded(h, opts.threshold_, opts.order_, opts.overlap_, True, boundaries, anchors)
         return out
 
+    def count_batch(self, texts: Sequence[str], opts: SearchOptions = None, keys=None, n_keys=None,
+                    boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[Dict[int, TermCount]]:
+        """`engine.count_batch` over the pre-filtered search (fac_count_batch_prefiltered), routed as
+        `search_batch` routes: the texts of `_batch_parts` as one batch, the others one by one through
+        the host's FuzzyMatches.term_counts; results in input order."""
+        opts = opts or SearchOptions()
+        karr, nk = _key_table(self.engine, keys, n_keys)  # checked once, whichever route the texts take
+        texts = list(texts)
+        enc = [t.encode("utf-8") for t in texts]
+        out = [None] * len(texts)
+        idx = self._batch_parts(enc)
+        if idx:
+            data, offsets = batch_offsets([enc[d] for d in idx])
+            sb = StagedBatch(self.engine, data, offsets, unicode_prefilter=True, unicode_mappings=True,
+                             boundaries=boundaries, anchors=anchors)
+            terms, doc_off, _ = sb.count_records(opts, keys, n_keys, prefilter=True)
+            for d, terms_d in zip(idx, _term_dicts(terms, doc_off)):
+                out[d] = terms_d
+        if len(idx) < len(texts):
+            for d, t in enumerate(texts):
+                if out[d] is None:
+                    out[d] = self.engine._search_bounded(t, opts.threshold_, opts.order_, opts.overlap_, True, boundaries,
+                                                         anchors).term_counts(karr, nk if karr is not None else None)
+        return out
+
     def replace_batch(self, texts: Sequence[str], opts: SearchOptions, replacements,
                       boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[str]:
         """`engine.replace_batch` over the pre-filtered search: the ASCII texts as one pre-filtered
@@ -703,6 +741,37 @@ class Prefiltered:
                     boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[List[str]]:
         return [[s.unmatched().text for s in segs if s.unmatched() is not None]
                 for segs in self.segment_batch(texts, opts, boundaries, anchors)]
+
+
+def _key_table(engine: "FuzzyAhoCorasick", keys, n_keys):
+    """(uint32 array or None, size of the key space) of a pattern -> key table for fac_count_batch,
+    checked as the library checks it (fac.h "Term counts of a batch"): without a table the key space is
+    the pattern count, whether `n_keys` is None, 0 or that count; with one, every key is below
+    `n_keys` (None: the greatest key + 1). Every buffer sized by the caller uses the size returned
+    here, which is also what the library is given."""
+    import numpy as np
+    n_pat = len(engine.patterns_)
+    if keys is None:
+        if n_keys is not None and int(n_keys) not in (0, n_pat):
+            raise DeviceError(_native.FAC_E_INVALID, "n_keys must be 0 or the pattern count when keys is None")
+        return None, n_pat
+    wide = np.asarray(keys, dtype=np.int64)
+    if wide.shape != (n_pat,):
+        raise ValueError("keys needs one entry per pattern")
+    top = int(wide.max()) if len(wide) else -1
+    if len(wide) and (int(wide.min()) < 0 or top > 0xFFFFFFFF):
+        raise DeviceError(_native.FAC_E_INVALID, "keys must be 32-bit unsigned")
+    nk = top + 1 if n_keys is None else int(n_keys)
+    if not 0 <= nk <= 0xFFFFFFFF or top >= nk:
+        raise DeviceError(_native.FAC_E_INVALID, "a key is not below n_keys (at most 2^32 - 1)")
+    return np.ascontiguousarray(wide.astype(np.uint32)), nk
+
+
+def _term_dicts(terms, doc_off) -> List[Dict[int, TermCount]]:
+    """count_records' (terms, doc_offsets) as one {key: TermCount} per document."""
+    key, cnt, sim, pat = (terms[f].tolist() for f in ("key", "count", "best_similarity", "best_pattern"))
+    off = [int(x) for x in doc_off]
+    return [{key[i]: TermCount(cnt[i], sim[i], pat[i]) for i in range(off[d], off[d + 1])} for d in range(len(off) - 1)]
 
 
 def _as_text(r):
@@ -1496,6 +1565,96 @@ class StagedBatch:
             return out[: n.value * _native.REC_BYTES], doc_off
         return _native.take_records(ptr, n.value), doc_off
 
+    def count_records(self, opts: SearchOptions = None, keys=None, n_keys=None, out=None, stream=None, stats=None,
+                      doc_offsets_out=None, totals=False, prefilter: bool = False):
+        """fac_count_batch (`prefilter`: fac_count_batch_prefiltered): (terms, doc_offsets, totals), the
+        per-document term counts of `search_records(opts)` grouped on the device. Terms (TERM_DTYPE:
+        key, count, best_similarity, best_pattern) are grouped by document, ascending key inside a
+        document; doc_offsets (n_docs + 1) indexes them. `keys`: one key per pattern, folding surface
+        forms into entities (None: key = pattern index); `n_keys`: the size of the key space (None:
+        the greatest key + 1; without `keys` it is the pattern count, and None, 0 and that count all
+        mean it -- the totals always have that many rows). `out`: a uint8 CUDA tensor to leave the terms in
+        HBM (16 bytes each): returns its filled part; too small raises DeviceError
+        (FAC_E_OUTPUT_CAPACITY) with `.needed` terms, nothing written. `doc_offsets_out`: an int64
+        CUDA tensor of n_docs + 1 entries that also receives the index. `totals`: False (None is
+        returned), True (an (n_keys, 2) uint64 array of (count, documents) per key), or an int64 CUDA
+        tensor of at least n_keys * 2 entries that receives them in HBM and is returned."""
+        import numpy as np
+        opts = opts or SearchOptions()
+        karr, nk = _key_table(self.engine, keys, n_keys)
+        a = _native.fac_count_args()
+        a.threshold = f32(opts.threshold_)
+        a.order = opts.order_.value
+        a.overlap = opts.overlap_.value
+        a.unique_ids = self.engine._unique_ids()
+        a.keys = karr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if karr is not None else None
+        a.n_keys = nk
+        a.stream = stream or None
+        doc_off = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        ptr = ctypes.POINTER(_native.fac_term)()
+        if out is not None:
+            a.device_out = out.data_ptr()
+            a.device_cap = out.numel() // _native.TERM_BYTES
+        if doc_offsets_out is not None:
+            if doc_offsets_out.numel() < self.n_docs + 1 or doc_offsets_out.element_size() != 8:
+                raise ValueError("doc_offsets_out needs n_docs + 1 64-bit entries")
+            a.device_doc_offsets = doc_offsets_out.data_ptr()
+        h_tot = None
+        if totals is True:
+            h_tot = np.zeros((max(nk, 1), 2), dtype=np.uint64)
+        elif totals is not False and totals is not None:
+            if totals.numel() < 2 * nk or totals.element_size() != 8:
+                raise ValueError("totals needs n_keys * 2 64-bit entries")
+            a.device_totals = totals.data_ptr()
+        fn = _native.lib.fac_count_batch_prefiltered if prefilter else _native.lib.fac_count_batch
+        rc = fn(self.engine._h, self._h, ctypes.byref(a), None if out is not None else ctypes.byref(ptr), ctypes.byref(n),
+                doc_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                ctypes.c_void_p(h_tot.ctypes.data) if h_tot is not None else None,
+                ctypes.byref(stats) if stats is not None else None)
+        if rc:
+            try:
+                _raise(rc)
+            except DeviceError as ex:
+                ex.needed = int(n.value)
+                raise
+        tot = h_tot[:nk] if h_tot is not None else (totals if a.device_totals else None)
+        if out is not None:
+            return out[: n.value * _native.TERM_BYTES], doc_off, tot
+        return _native.take_terms(ptr, n.value), doc_off, tot
+
+    def term_matrix(self, opts: SearchOptions = None, keys=None, n_keys=None, values: str = "count",
+                    prefilter: bool = False):
+        """The document-term matrix of the batch as a torch.sparse_csr_tensor of shape (n_docs, n_keys)
+        on the engine's device: row d holds document d's terms (count_records), as float32 counts
+        (`values="count"`) or each term's best similarity (`values="similarity"`). The terms and their
+        index stay in HBM; the tensor is built from them with torch ops only. The term buffer starts at
+        max(1024, 2 * n_docs) terms; a batch with more terms runs the whole call (search, apply and
+        count) a second time with a buffer of the size the first run reported."""
+        import torch
+        if values not in ("count", "similarity"):
+            raise ValueError('values must be "count" or "similarity"')
+        _, nk = _key_table(self.engine, keys, n_keys)
+        dev = torch.device("cuda", self.engine.device)
+        crow = torch.empty(self.n_docs + 1, dtype=torch.int64, device=dev)
+        cap = max(1024, 2 * self.n_docs)
+        while True:
+            buf = torch.empty(cap * _native.TERM_BYTES, dtype=torch.uint8, device=dev)
+            try:
+                filled, _, _ = self.count_records(opts, keys, nk, out=buf, doc_offsets_out=crow, prefilter=prefilter)
+                break
+            except DeviceError as ex:
+                if ex.code != _native.FAC_E_OUTPUT_CAPACITY:
+                    raise
+                cap = ex.needed
+        words = filled.view(torch.int32).view(filled.numel() // _native.TERM_BYTES, 4)
+        col = words[:, 0].to(torch.int64) & 0xFFFFFFFF
+        if values == "count":
+            val = (words[:, 1].to(torch.int64) & 0xFFFFFFFF).to(torch.float32)
+        else:
+            val = words[:, 2].contiguous().view(torch.float32)
+        return torch.sparse_csr_tensor(crow, col, val, size=(self.n_docs, nk), device=dev)
+
     def segment_records(self, opts: SearchOptions = None, out=None, stream=None, stats=None, doc_offsets_out=None,
                         prefilter: bool = False):
         """fac_segment_batch (`prefilter`: fac_segment_batch_prefiltered): (segments, doc_offsets), the
@@ -1810,6 +1969,35 @@ class FuzzyReplacer:
         pass (engine.lookup_batch with k = 1). A `None` entry stands for the text itself."""
         return [_item_text(self.replacements, ms[0]) if ms else None
                 for ms in self.engine.lookup_batch(texts, opts, 1)]
+
+    @staticmethod
+    def term_keys(replacements, patterns=None) -> Tuple[List[int], List[str]]:
+        """(keys, forms): keys[p] is the index of pattern p's replacement among the distinct
+        replacements, in order of first appearance, and forms[k] the canonical form of key k. A `None`
+        entry (the matched text stays) stands for its own pattern's text, a `Wrap` for that text
+        wrapped; `patterns` (the engine's) is only needed for those."""
+        keys, forms, seen = [], [], {}
+        for p, r in enumerate(replacements):
+            if r is None or isinstance(r, Wrap):
+                if patterns is None:
+                    raise ValueError("a None or Wrap replacement needs the patterns")
+                r = patterns[p].pattern if r is None else r.render(patterns[p].pattern)
+            form = _as_text(r)
+            if form not in seen:
+                seen[form] = len(forms)
+                forms.append(form)
+            keys.append(seen[form])
+        return keys, forms
+
+    def count_batch(self, texts: Sequence[str], opts: SearchOptions = None, unicode_mappings: bool = False,
+                    boundaries: Boundary = Boundary.NONE, anchors: Anchor = Anchor.NONE) -> List[Dict[str, int]]:
+        """Per text, how often each canonical form (replacement) is mentioned: the matches
+        `engine.search(t, opts)` finds, counted per distinct replacement on the device
+        (engine.count_batch with `term_keys`)."""
+        keys, forms = self.term_keys(self.replacements, self.engine.patterns_)
+        return [{forms[k]: t.count for k, t in terms.items()}
+                for terms in self.engine.count_batch(texts, opts, keys, len(forms), unicode_mappings=unicode_mappings,
+                                                     boundaries=boundaries, anchors=anchors)]
 
     def _device_table(self) -> "ReplacementTable":
         key = tuple(self.replacements)

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import struct
 from dataclasses import dataclass
-from typing import Callable, Iterator, List, Optional
+from typing import Callable, Dict, Iterator, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -36,6 +36,14 @@ class FuzzyMatch:
 
     def sim_bits(self) -> int:
         return struct.unpack("<I", struct.pack("<f", self.similarity))[0]
+
+
+class TermCount(NamedTuple):
+    """One term of a document (fac.h fac_term): the records of one key, the greatest similarity among
+    them under total_cmp, and the least pattern index that reaches it."""
+    count: int
+    best_similarity: float
+    best_pattern: int
 
 
 @dataclass
@@ -294,6 +302,20 @@ class FuzzyMatches:
             self.inner = [m for m in self.inner
                           if (not sides & 1 or m.start == 0) and (not sides & 2 or m.end == n)]
         return self
+
+    def term_counts(self, keys=None, n_keys=None) -> "Dict[int, TermCount]":
+        """The matches grouped by key(pattern_index) (fac.h "Term counts of a batch", on the host
+        through fac_count_records): {key: TermCount(count, best_similarity, best_pattern)} in
+        ascending key order. `keys`: one key per pattern, folding surface forms into entities (None:
+        key = pattern index); `n_keys`: every key must be below it (None: no further bound)."""
+        from . import _native
+        recs = np.zeros(len(self.inner), dtype=_native.MATCH_DTYPE)
+        recs["pattern_index"] = [m.pattern_index for m in self.inner]
+        recs["similarity"] = [m.similarity for m in self.inner]
+        n_pat = None if keys is not None else (int(recs["pattern_index"].max()) + 1 if len(recs) else 0)
+        terms = _native.count_records(recs, keys, n_pat, 0 if keys is None else n_keys)
+        return {int(t["key"]): TermCount(int(t["count"]), float(t["best_similarity"]), int(t["best_pattern"]))
+                for t in terms}
 
     def filter(self, pred) -> "FuzzyMatches":
         return FuzzyMatches(self.haystack, [m for m in self.inner if pred(m)], self.hay_bytes)

@@ -406,6 +406,9 @@ int fac_matches_apply(const fac_engine* engine, fac_match* matches, uint64_t n, 
  * ASCII or opted in (fac_search_batch_prefiltered, fac_replace_batch_prefiltered, fac_segment_batch_prefiltered,
  * fac_render_batch_prefiltered below). The matched strings of a batch, or each match's replacement,
  * come from fac_extract_batch and fac_extract_batch_prefiltered. Multi-GPU batches are not provided.
+ * Which entry a document is as a whole comes from fac_lookup_batch, and which entries each document
+ * mentions and how often (per-document term counts, grouped on the device) from fac_count_batch and
+ * fac_count_batch_prefiltered.
  *
  * Limits of the pre-filtered forms: where the filter runs, the batch must be all ASCII or opted in
  * with fac_batch_allow_unicode_prefilter. Without the opt-in one non-ASCII document gives
@@ -659,6 +662,74 @@ typedef struct fac_lookup_args {
 } fac_lookup_args;
 int fac_lookup_batch(const fac_engine* engine, const fac_batch* batch, const fac_lookup_args* args, fac_match** out,
                      uint32_t* found, fac_stats* stats);
+
+/* ---- Term counts of a batch: "which entries does each document mention, and how often" -- the
+ * document-term matrix of a column against the dictionary, grouped on the device.
+ *
+ * For every document d, ms = engine.search(doc_d, opts) exactly as fac_search_batch computes it: the
+ * options are taken as passed (no `segmented` normalisation, as in fac_extract_batch), the batch's
+ * boundary mask, anchor mask and both Unicode opt-ins are honoured, and errors and limits are
+ * fac_search_batch's. A pattern -> key table folds surface forms into entities: with keys == NULL,
+ * key(p) = p and n_keys must be 0 or the engine's pattern count; otherwise keys is a host array of
+ * one uint32_t per pattern, each < n_keys, and n_keys <= 2^32 - 1. A key >= n_keys gives
+ * FAC_E_INVALID before anything runs. keys is uploaded per call.
+ * Document d's terms are the groups of ms by key(pattern_index), in ascending key order. A document
+ * without kept records owns an empty range. The term set does not depend on the order of ms, so
+ * Unsorted + Keep is fully determined here; the order only matters through the overlap walk. A
+ * document with 2^32 or more kept records gives FAC_E_UNSUPPORTED; a partial result is never returned. */
+typedef struct fac_term {
+  uint32_t key;
+  uint32_t count;          /* records of the group */
+  float    best_similarity;/* the greatest similarity of the group under f32::total_cmp (bits, as matches.rs:28 compares) */
+  uint32_t best_pattern;   /* least pattern_index among the group's records whose similarity has exactly those bits */
+} fac_term;
+
+/* Corpus totals (optional): a dense array of n_keys entries. count: the key's term counts summed
+ * over the batch; docs: the documents that have a term of that key (the document frequency). */
+typedef struct fac_term_total {
+  uint64_t count;
+  uint64_t docs;
+} fac_term_total;
+
+typedef struct fac_count_args {
+  float threshold;
+  int32_t order;               /* as fac_matches_apply */
+  int32_t overlap;             /* as fac_matches_apply */
+  const uint64_t* unique_ids;  /* as fac_matches_apply (host array, one key per pattern) */
+  const uint32_t* keys;        /* host array, one key per pattern, or NULL (key = pattern index) */
+  uint64_t n_keys;
+  void* stream;
+  void* device_out;            /* optional: terms stay in HBM */
+  uint64_t device_cap;         /* in terms */
+  uint64_t* device_doc_offsets; /* optional: n_docs+1 entries on the device, the CSR index into the terms */
+  fac_term_total* device_totals; /* optional: n_keys entries on the device */
+} fac_count_args;
+
+/* Terms grouped by document, ascending document index, ascending key within a document. They go to
+ * the host (*out, fac_buffer_free) or, with device_out set, into that device buffer of device_cap
+ * terms (out may then be NULL); *n_out is the term count either way. doc_offsets (host array of
+ * n_docs+1 entries, may be NULL) is the CSR index into the terms. totals (host array of n_keys
+ * entries -- the engine's pattern count when keys == NULL -- may be NULL) receives the corpus totals;
+ * when neither totals nor device_totals is given, nothing is launched or allocated for them.
+ * FAC_E_OUTPUT_CAPACITY: device_cap is too small, *n_out holds the terms needed and nothing was
+ * written to any device output (the counts are known before any term is written). */
+int fac_count_batch(const fac_engine* engine, const fac_batch* batch, const fac_count_args* args, fac_term** out,
+                    uint64_t* n_out, uint64_t* doc_offsets, fac_term_total* totals, fac_stats* stats);
+
+/* fac_count_batch over fac_search_batch_prefiltered's search: the same relation as every other
+ * _prefiltered pair, with its "all ASCII, or opted in" limit. */
+int fac_count_batch_prefiltered(const fac_engine* engine, const fac_batch* batch, const fac_count_args* args,
+                                fac_term** out, uint64_t* n_out, uint64_t* doc_offsets, fac_term_total* totals,
+                                fac_stats* stats);
+
+/* Tests and hosts: the rule above on the host for one document's n records (no device). keys: one
+ * entry per pattern (n_patterns of them) or NULL, n_keys as above. Returns the term count, writing
+ * the terms in ascending key order to out (cap terms; out == NULL: count only), or minus the error
+ * code: FAC_E_INVALID for a key >= n_keys, a pattern_index >= n_patterns or a wrong n_keys with
+ * keys == NULL; FAC_E_OUTPUT_CAPACITY (nothing written) when cap is too small; FAC_E_UNSUPPORTED for
+ * n >= 2^32. */
+int64_t fac_count_records(const fac_match* recs, uint64_t n, const uint32_t* keys, uint64_t n_patterns, uint64_t n_keys,
+                          fac_term* out, uint64_t cap);
 
 /* ---- Batched replace: FuzzyReplacer::replace (replacer.rs:22-25, query.rs:46-96,
  * matches.rs:165-188) of every document of a staged batch, spliced on the device.
@@ -951,6 +1022,18 @@ void fac_edge_order(const uint32_t* cps, const uint64_t* off, uint64_t n, uint32
  * perm[a*bw .. a*bw + bw). sel_limit < 0: core's 16 partition rounds. Uses device 0. */
 int fac_diag_beam_select(const float* keys, const uint64_t* offs, uint64_t count, uint32_t bw, int32_t lds,
                          int32_t sel_limit, uint32_t* perm);
+
+/* Diagnostics (tests): the device reduce of fac_count_batch alone, with no engine and no search.
+ * recs: n records grouped by document, document d's being recs[doc_offsets[d] .. doc_offsets[d+1])
+ * (n_docs + 1 ascending offsets from 0 to n, n_docs <= 2^24); only pattern_index (< n_patterns) and
+ * similarity are read. keys, n_keys: as fac_count_records. lane_max, group_max: the greatest record
+ * counts a document may have to be grouped by one lane / by one workgroup (0: the library's
+ * defaults, 8 and 2048; above them: FAC_E_INVALID); larger documents go through the device sort.
+ * The terms come back in *out (fac_buffer_free) with *n_out, term_offsets (n_docs + 1 entries) and
+ * totals (n_keys entries -- n_patterns when keys == NULL; may be NULL: nothing runs for them). Uses device 0. */
+int fac_diag_count_terms(const fac_match* recs, uint64_t n, const uint64_t* doc_offsets, uint64_t n_docs,
+                         const uint32_t* keys, uint64_t n_patterns, uint64_t n_keys, uint32_t lane_max, uint32_t group_max,
+                         fac_term** out, uint64_t* n_out, uint64_t* term_offsets, fac_term_total* totals);
 
 /* Diagnostics (tests): what a search does with its engine's snapshot store, from the store's host state
  * alone (no device): 0 carries over, else the reason it starts the store empty (1 fresh, 2 signature,
